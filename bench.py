@@ -21,6 +21,18 @@ next leaf, position-cache probe) and the net evaluates the shard's leaf batch.  
 The run FAILS (non-zero exit, no JSON line) if fewer than concurrent_games games finished inside the window or a slot's
 game stream ran dry: such a number would not be the metric.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up (the pipeline probe
+included), pre-roll, warm-up, the window, the line.  `--full` adds everything else the line used to carry, each in the
+process it ran in before: the leaf net's numerics on the committed fixture, the tile alone on the chip, the secondary
+measurements, the CPU baseline, and BASELINE configs[2] / configs[4] (Tawlbwrdd, StarGambit) beside the headline.
+
+`--dump-outputs DIR`: after the window, one game in every slot is played to its end on the timed path (same driver, net,
+search settings and seeds, engines of their own) and its samples - canonical planes, value and policy targets, and their keys
+(global slot, game of the slot, turn, player) - are written as DIR/<name>.npy, sorted by key; above 60 MB a seeded choice of
+whole slots is kept.  The same arguments give the same arrays, so two builds can be compared output for output.  (A timed
+step's own rows would not do: the pipeline ends an epoch by the GPU's timing, so which games finish inside a step varies
+from run to run; each slot's game stream is fixed by its seed.)
+
 Multi-GPU: one process per GPU (RANK/LOCAL_RANK/WORLD_SIZE from the launcher; `--gpus N` without a launcher spawns the
 N processes itself, before anything touches a GPU), every rank runs the same workload on its own engines and weights
 (weak scaling), the window's samples are gathered to rank 0 over RCCL and the statistics are summed with one all-reduce.
@@ -44,6 +56,7 @@ FLOP_PER_EVAL = 37.7e6     # Connect4 6b64c k3 (conv + linear MACs 
 MFMA_PEAK_TFLOPS = 2500.0  # dense bf16, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
 B_SIM = 1300.0             # algorithmic bytes per simulation of the tree step
+DUMP_BYTES = 60_000_000    # --dump-outputs: data bytes at most (the .npy headers stay well inside 64 MB)
 
 
 def parse(argv=None):
@@ -79,16 +92,22 @@ def parse(argv=None):
     ap.add_argument("--profile-window", action="store_true",
                     help="for rocprofv3 runs: a short window is allowed (no validity gate); the line is marked profile_window and its value is not the metric")
     ap.add_argument("--no-tawlbwrdd", action="store_true",
-                    help="the default run (1 GPU, Connect4) also measures BASELINE configs[2] - Tawlbwrdd 2048 games x 400 sims, PUCT and Gumbel, with its "
+                    help="the --full run (1 GPU, Connect4) also measures BASELINE configs[2] - Tawlbwrdd 2048 games x 400 sims, PUCT and Gumbel, with its "
                          "CPU baseline - and reports it as the `tawlbwrdd` block of the line; this flag skips that")
     ap.add_argument("--no-stargambit", action="store_true",
                     help="... and BASELINE configs[4] per GPU - star_gambit_unified 1024 games x 800 sims, 200 k-entry device cache - as the `stargambit` block; this flag skips that")
     ap.add_argument("--allow-fallback", action="store_true",
                     help="driver auto: when the pipeline probe fails on this box, measure the lock-step driver instead of failing (the line then carries fallbacks = 1)")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)    # a measurement process started by the default run
+    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)    # a measurement process started by the --full run
     ap.add_argument("--probe", action="store_true", help=argparse.SUPPRESS)     # child process of the default driver choice: exit 0 when the pipeline runs here
     ap.add_argument("--dry", action="store_true",
                     help="CPU dry run of the launch / distributed plumbing (gloo, no device, a stand-in engine): used by the tests")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: net numerics on the fixture, tile alone, secondary measurements, CPU baseline, "
+                         "and (1 GPU, Connect4) the Tawlbwrdd and StarGambit blocks; off = the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the window: play one game per slot on the timed path and write its samples (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB")
     return ap.parse_args(argv)
 
 
@@ -219,6 +238,25 @@ def fixture_numerics(az, torch_net, game, precision, device_index):
             "numerics_fixture": "tests/golden/" + fname}
 
 
+def dump_outputs(dirname, rows, slots, seed=0):
+    """--dump-outputs: samples (canonical, v, pi, keys = slot, game of the slot, turn, player) as DIR/<name>.npy, sorted by key;
+    float32, the keys float64.  Above DUMP_BYTES the rows of a seeded choice of whole slots are kept (slots in the order of a
+    fixed permutation while they fit), so that two runs keep the same slots."""
+    import numpy as np
+    canon, v, pi, keys = (r.cpu().numpy() for r in rows)
+    keys = keys.astype(np.int64)
+    arrays = {"canonical": canon.astype(np.float32), "v": v.astype(np.float32), "pi": pi.astype(np.float32), "keys": keys.astype(np.float64)}
+    order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+    row_bytes = sum(a.itemsize * int(np.prod(a.shape[1:])) for a in arrays.values())
+    if len(order) * row_bytes > DUMP_BYTES:
+        perm = np.random.default_rng(seed).permutation(slots)
+        fits = np.cumsum(np.bincount(keys[:, 0], minlength=slots)[perm]) * row_bytes <= DUMP_BYTES
+        order = order[np.isin(keys[order, 0], perm[:int(fits.sum())])]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a[order])
+
+
 def host_cores():
     cores = len(os.sched_getaffinity(0))
     try:                                   # a cgroup CPU quota is the real core count of a container
@@ -335,19 +373,24 @@ class DryEngine:
     def __init__(self, rank, S):
         import torch
         self.torch, self.rank, self.S = torch, rank, S
-        self.games = self.sims = self.evals = 0
+        self.games = self.sims = self.evals = self.steps = 0
         self.rows = []
 
     def step(self, rounds):
         self.games += self.S // 4
         self.sims += self.S * rounds
         self.evals += self.S * rounds // 3
+        self.steps += 1
         n = 8 + self.rank
-        self.rows.append((self.torch.full((n, 4, 6, 7), float(self.rank)), self.torch.zeros(n, 3), self.torch.zeros(n, 7)))
+        t = self.torch
+        # keys as the engines give them: slot, game of the slot, turn, player
+        meta = t.stack([t.arange(n), t.full((n,), self.steps), t.zeros(n, dtype=t.long), t.zeros(n, dtype=t.long)], 1).int()
+        self.rows.append((t.full((n, 4, 6, 7), float(self.rank)), t.zeros(n, 3), t.zeros(n, 7), meta))
 
     def take_rows(self):
         t = self.torch
-        out = tuple(t.cat([r[i] for r in self.rows], 0) for i in range(3)) if self.rows else (t.zeros(0, 4, 6, 7), t.zeros(0, 3), t.zeros(0, 7))
+        out = (tuple(t.cat([r[i] for r in self.rows], 0) for i in range(4)) if self.rows else
+               (t.zeros(0, 4, 6, 7), t.zeros(0, 3), t.zeros(0, 7), t.zeros((0, 4), dtype=t.int32)))
         self.rows = []
         return out
 
@@ -367,7 +410,7 @@ def run_worker(extra, timeout):
 
 
 def orchestrate(args):
-    """The default run: the headline (Connect4, BASELINE configs[1]) and, beside it in the same line, BASELINE configs[2] -
+    """The --full run: the headline (Connect4, BASELINE configs[1]) and, beside it in the same line, BASELINE configs[2] -
     Tawlbwrdd 11x11, 2048 concurrent games, 400 sims, the configs/tawlbwrdd.yaml net - with PUCT and with Gumbel
     (configs/tawlbwrdd.yaml:24-25) and its own CPU baseline (play_manager_bench.cc:171-181 methodology).  Each measurement is a
     process of its own, one after the other on the one GPU; this process never touches it."""
@@ -378,7 +421,7 @@ def orchestrate(args):
         sys.stderr.write("bench.py: the headline measurement failed: " + json.dumps(head) + "\n")
         return 3
     # windows long enough for more than 2048 games to finish (the validity gate of a run): ~200 / ~145 games per 2048-round step
-    common = ["--game", "tawlbwrdd", "--warmup", "1", "--no-secondary", "--preroll-factor", "1.0", "--cpu-seconds", "12"]
+    common = ["--game", "tawlbwrdd", "--full", "--warmup", "1", "--no-secondary", "--preroll-factor", "1.0", "--cpu-seconds", "12"]
     if args.no_cpu_baseline:
         common.append("--no-cpu-baseline")
     puct = run_worker(common + ["--steps", "13"], 600)
@@ -396,7 +439,7 @@ def orchestrate(args):
     # BASELINE configs[4] (per GPU): star_gambit_unified, 1024 concurrent games, 800 sims, device-side S3-FIFO of 200 000 entries
     # (configs/star_gambit_unified.yaml:5-15,23-24); round 6: a 10 s CPU leg (its rate = the sample's simulations/s over the GPU run's simulations per game)
     if not args.no_stargambit:
-        sgb = run_worker(["--game", "stargambit", "--warmup", "1", "--no-secondary", "--preroll-factor", "0.5", "--steps", "100", "--cpu-seconds", "10"]
+        sgb = run_worker(["--game", "stargambit", "--full", "--warmup", "1", "--no-secondary", "--preroll-factor", "0.5", "--steps", "100", "--cpu-seconds", "10"]
                          + (["--no-cpu-baseline"] if args.no_cpu_baseline else []), 700)
         head["stargambit"] = trim(sgb)
     head["config"]["bench_wall_s"] = time.perf_counter() - t0
@@ -481,7 +524,7 @@ def main():
         sys.exit(0 if _pipeline_probe(int(os.environ.get("LOCAL_RANK", "0")), args.games or 4096) else 7)
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
-    if (not args.dry and not args.worker and not args.no_tawlbwrdd and args.gpus == 1 and "RANK" not in os.environ and args.game == "connect4"
+    if (args.full and not args.dry and not args.worker and not args.no_tawlbwrdd and args.gpus == 1 and "RANK" not in os.environ and args.game == "connect4"
             and not args.gumbel and not args.playout_cap and not args.profile_window):
         sys.exit(orchestrate(args))
     if args.hwq:
@@ -596,10 +639,10 @@ def main():
         # 8 x concurrent for the same purpose); the finished samples leave the engines' ring every step (hist_saver's job)
         STREAM = 1 << 30
 
-        def make_engines(cache, playout_cap, seed0):
+        def make_engines(cache, playout_cap, seed0, games=STREAM):
             out = []
             for i in range(K):
-                pp = selfplay_params(az, Se, sims, STREAM, cache=cache // K, playout_cap=playout_cap, gumbel=args.gumbel)
+                pp = selfplay_params(az, Se, sims, games, cache=cache // K, playout_cap=playout_cap, gumbel=args.gumbel)
                 if sg:   # configs/star_gambit_unified.yaml: self_play_temp 1.2, final_temp 0.2, per-variant half lives 3 / 4 / 5 / 8 turns
                     pp.start_temp, pp.final_temp, pp.temp_decay_half_life_by_variant = 1.2, 0.2, [3.0, 4.0, 5.0, 8.0]
                 out.append(az.PlayManager(Game(), pp, seed=seed0 + 7919 * rank + 104729 * i, device=local_rank, max_inline=args.inline,
@@ -620,7 +663,7 @@ def main():
             net = net.to(memory_format=torch.channels_last)
 
         def evaluate(group, i):
-            canon, v_buf, pi_buf = io[i]
+            canon, v_buf, pi_buf = io[i] if group is pms else group[i].io_tensors()
             if hip_net is not None:
                 group[i].net_forward(hip_net, sps[i])
             else:
@@ -703,6 +746,23 @@ def main():
 
         def take_rows():
             return take_rows_of(pms)
+
+        def dump_games():
+            """--dump-outputs: one game in every slot, played to its end on the timed path (this driver, net, search settings, cache
+            size and seed rule, on engines of their own after the window): the samples a caller of the path receives for them, with
+            their keys (global slot, game of the slot, turn, player).  Fixed in number and content for given arguments, unlike the
+            rows of a timed step: the pipeline ends an epoch when the GPU has run its simulations, so which games finish inside a
+            step follows the GPU's timing, while each slot's game stream is fixed by its seed."""
+            group = make_engines(args.cache, args.playout_cap, 20240601, games=Se)
+            used = 0
+            while any(pm.poll()[1] for pm in group):
+                run_rounds_on(group, R)
+                used += R
+                if used > 400 * R:
+                    raise RuntimeError(f"--dump-outputs: the games did not end in {used} rounds")
+            parts = [pm.take_history_device(dev) for pm in group]
+            keys = torch.cat([p[3] + p[3].new_tensor([i * Se, 0, 0, 0]) for i, p in enumerate(parts)], 0)
+            return tuple(torch.cat([p[j] for p in parts], 0) for j in range(3)) + (keys,)
 
         def stat_vector():
             """what self_play() reads from the PlayManager (game_runner.py:2073-2145) as raw sums: scores [P+1], resign scores
@@ -808,7 +868,6 @@ def main():
         if use_dist:
             dist.destroy_process_group()
         sys.exit(3)
-
     if rank == 0:
         hit_rate = n_hits / max(1.0, n_hits + n_miss)
         st = stats.tolist()
@@ -876,7 +935,7 @@ def main():
             achieved = flop_per_eval * rows_evaluated / dt / 1e12
             per_launch = (flop_per_eval * rows_evaluated / launches) / (nn_ms * 1e-3) / 1e12 if nn_ms > 0 else 0.0
             out["config"].update({"tree_kernel_ms": tree_ms, "net_ms": nn_ms})
-            if hip_net is not None:
+            if hip_net is not None and args.full:
                 out["config"].update(fixture_numerics(az, torch_net, args.game, args.precision, local_rank))
             if use_pipe:
                 out["config"]["pipeline_errors"] = list(PIPE_ERRORS)      # recovered pipeline errors of this process (normally none)
@@ -908,7 +967,7 @@ def main():
                               "and share the chip with each other and with the tree kernels, so the whole-GPU rate is aggregate_achieved = "
                               "FLOPs of all launches of the region / wall time of the region (rank 0's GPU)",
             }
-            if use_pipe and hip_net is not None and world == 1:
+            if use_pipe and hip_net is not None and world == 1 and args.full:
                 # the same tiles ALONE on the chip (no tree wavefronts beside them, every workgroup with work from the first cycle): 3072
                 # rows = 512 six-board tiles, two per CU, 200 launches timed with events - what the kernel itself does, beside what it does
                 # in the mix (profiles/r3_leafnet_pmc_3072.csv has the counters of this launch)
@@ -1036,7 +1095,7 @@ def main():
                         out["roofline"]["traffic_commit"] = f[4] if len(f) > 4 else None
                         out["roofline"]["traffic_note"] = ("bytes per k_leafnet launch at the L2-to-fabric counters (2 x FETCH_SIZE + WRITE_SIZE, "
                                                            + os.path.relpath(pmc_net, ROOT) + ")")
-            if world == 1 and hip_net is not None and not args.no_secondary and not tafl and not args.playout_cap:
+            if world == 1 and hip_net is not None and args.full and not args.no_secondary and not tafl and not args.playout_cap:
                 # short secondary measurements of the same workload, reported beside the headline, never as it:
                 #  (a) playout-cap randomisation at the reference's self-play defaults (fast_mcts_visits 25 on 75 % of
                 #      moves, config.py:86,100): what self_play() runs by default
@@ -1116,11 +1175,13 @@ def main():
                         out["config"][name]["games_per_s"] = ((s1 - s0) / dt2) / (n_sims / n_games)
                         out["config"][name]["note"] += f"; games/s = this window's simulations/s / the headline's {n_sims / n_games:.0f} simulations per game (a cold-start window of {dt2:.1f}s)"
                     del pms2, tot2, run2
-            if world == 1 and not args.no_cpu_baseline and not args.gumbel:
+            if world == 1 and args.full and not args.no_cpu_baseline and not args.gumbel:
                 sys.stderr.write("bench.py: cpu baseline ...\n"); sys.stderr.flush()
                 # the reference's own cache size: 200 000 entries (config.py:197); Tawlbwrdd: off, as in its GPU run
                 out["cpu_baseline"] = cpu_baseline(az, sims, args.cpu_seconds, S, hip_net, 200_000 if (sg or not tafl) else 0, game=args.game,
                                                    sims_per_game=(n_sims / n_games) if n_games else None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, window_rows[-1] if dry else dump_games(), S)
         print(json.dumps(out))
     if use_dist:
         dist.barrier()

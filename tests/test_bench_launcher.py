@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -62,3 +64,19 @@ def test_gpus_8_dry_run_of_the_whole_node():
     assert j["config"]["games_in_window"] == 8 * 5 * 4096 // 4
     assert j["config"]["samples_gathered"] == 5 * sum(8 + k for k in range(8)) == j["config"]["samples_in_window"]
     assert j["config"]["node_stats"]["sum"] == [36.0 * i for i in range(16)]
+
+
+def test_dump_outputs_writes_the_last_timed_steps_samples(tmp_path):
+    """--dump-outputs DIR: samples with their keys (rank 0) as DIR/<name>.npy in float32 / float64, identical from run to run; in
+    --dry the stand-in engine's last step is written: 8 rows keyed (slot, step, 0, 0), after 8 pre-roll + 1 warm-up + 5 timed steps"""
+    dumps = []
+    for d in ("a", "b"):
+        r = _run("--steps", "5", "--warmup", "1", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr
+        assert _json_line(r.stdout)["steps"] == 5
+        dumps.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("canonical", "v", "pi", "keys")})
+    a, b = dumps
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert a["canonical"].shape == (8, 4, 6, 7) and a["v"].shape == (8, 3) and a["pi"].shape == (8, 7)
+    assert a["keys"].tolist() == [[s, 14, 0, 0] for s in range(8)]
+    assert all(np.array_equal(a[n], b[n]) for n in a)

@@ -1,9 +1,10 @@
 """CPU: pins the oracle (oracle/) against the reference's known answers.
 
 Sources: tests/golden/known_answers.json (outputs of the reference itself recorded in SURVEY §8c and
-the known-answer assertions of the reference's own gtest files) and, when built, the real libstdc++ +
-reference pcg header (oracle/_ref/librngref.so).
+the known-answer assertions of the reference's own gtest files) and the streams of the real libstdc++ +
+reference pcg header (oracle/_ref/librngref.so), recorded in tests/golden/ref_rng_libstdcxx.npz.
 """
+import hashlib
 import json
 import os
 
@@ -23,22 +24,34 @@ def test_rng_known_answers(oracle):
     assert np.allclose(oracle.gumbel(12345, 2), KA["extreme_value_seed_12345_first2"], rtol=1e-6)
 
 
+def _sha256(a):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
 def test_rng_against_real_libstdcxx(oracle):
-    """Integer paths are bit-exact; gamma / gumbel differ from glibc's float libm by a few ulp in < 0.2 % / 2 % of draws."""
-    ref = oracle.ref_rng()
-    if ref is None:
-        pytest.skip("oracle/_ref/librngref.so not built (reference tree absent)")
-    assert np.array_equal(oracle.pcg32_outputs(7, 100000), oracle.pcg32_outputs(7, 100000, which=ref))
+    """Integer paths are bit-exact; gamma / gumbel differ from glibc's float libm by a few ulp in < 0.2 % / 2 % of draws.
+    The reference's streams are those of tests/golden/ref_rng_libstdcxx.npz (tests/golden/make_ref_rng_fixture.py): a SHA-256
+    per stream, and for gamma / Gumbel the draws where the reference differs from the oracle."""
+    fx = np.load(os.path.join(HERE, "golden", "ref_rng_libstdcxx.npz"))
+
+    def ref(name, a):
+        """the reference's stream `name`: the oracle's stream `a` with the recorded differences, checked against its digest"""
+        b = a.copy()
+        b[fx["idx." + name]] = fx["val." + name]
+        assert np.array_equal(_sha256(b), fx["sha." + name]), f"{name}: the oracle's stream is not the one the fixture was recorded against"
+        return b
+    assert np.array_equal(_sha256(oracle.pcg32_outputs(7, 100000)), fx["sha.pcg32"])
     for n in (1, 2, 3, 4, 5, 6, 7, 8, 33, 112, 113, 250, 1000):
-        assert np.array_equal(oracle.shuffle_iota(99 + n, n, 100), oracle.shuffle_iota(99 + n, n, 100, which=ref)), n
-    assert np.array_equal(oracle.uniform01(5, 500000), oracle.uniform01(5, 500000, which=ref))
-    for alpha in (10.83 / 7, 10.83 / 2, 0.3, 0.77, 5.0):
+        assert np.array_equal(_sha256(oracle.shuffle_iota(99 + n, n, 100)), fx[f"sha.shuffle_{n}"]), n
+    assert np.array_equal(_sha256(oracle.uniform01(5, 500000)), fx["sha.uniform01"])
+    for k, alpha in enumerate((10.83 / 7, 10.83 / 2, 0.3, 0.77, 5.0)):
         for fresh in (False, True):
             a = oracle.gamma(77, alpha, 100000, fresh)
-            b = oracle.gamma(77, alpha, 100000, fresh, which=ref)
+            b = ref(f"gamma_{k}_{int(fresh)}", a)
             assert (a != b).mean() < 2e-3, (alpha, fresh)
             assert np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-30)) < 2e-6
-    a, b = oracle.gumbel(77, 100000), oracle.gumbel(77, 100000, which=ref)
+    a = oracle.gumbel(77, 100000)
+    b = ref("gumbel", a)
     assert (a != b).mean() < 0.03 and np.max(np.abs(a - b)) < 1e-5
 
 
