@@ -557,6 +557,166 @@ class MCTS:
         check(lib.azmi_mcts_reset_batch(self._h))
 
 
+class MCTSBatch:
+    """N independent search trees on N positions of one game, advanced together on the device (azmi_search_*): the job of the
+    reference's evaluation tools, which hold a list of MCTS objects, step them in lock step and batch the leaves into one net
+    call (frozen_eval.py:545-660, mcts_analysis.py:923-1049, play.py:292-343).  Tree i is bit for bit the stand-alone
+    `MCTS(..., seed=seeds[i])` driven call by call from states[i] with the same evaluator values.  The constructor takes the
+    MCTS constructor's search arguments; `max_simulations` (required) sizes every tree's arena.  No move is played on a batch:
+    call reset() with the new positions.  Read-outs return one row per tree."""
+
+    def __init__(self, game, n, cpuct, epsilon=0.0, root_policy_temp=1.0, fpu_reduction=0.0, root_fpu_zero=False,
+                 shaped_dirichlet=False, gumbel_enabled=False, gumbel_m=16, gumbel_c_visit=50.0, gumbel_c_scale=1.0,
+                 gumbel_full=False, *, max_simulations, seeds=None, device=0):
+        game = game if isinstance(game, type) else type(game)
+        P, M, chw = game._info()
+        cfg = _capi.MctsConfigC(cpuct, P, M, epsilon, root_policy_temp, fpu_reduction, int(game.GAME_ID == StarGambitUnifiedGS.GAME_ID),
+                                int(root_fpu_zero), int(shaped_dirichlet), int(gumbel_enabled), gumbel_m, gumbel_c_visit,
+                                gumbel_c_scale, int(gumbel_full), int(max_simulations))
+        h = C.c_void_p()
+        check(lib.azmi_search_create(game.GAME_ID, C.byref(cfg), int(n), int(device), C.byref(h)))
+        self._h, self._game, self._n, self._P, self._M, self._chw = h, game, int(n), P, M, tuple(chw)
+        self._gumbel, self._device = bool(gumbel_enabled), int(device)
+        self._vec = max(M, 64)
+        self._seeds = None if seeds is None else self._seed_array(seeds)
+        self._rows = None          # rows of the pending find_leaves() batch
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib.azmi_search_destroy(self._h)
+            self._h = None
+
+    def __len__(self):
+        return self._n
+
+    def _seed_array(self, seeds):
+        a = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+        if a.shape != (self._n,):
+            raise RuntimeError(f"seeds: one per tree ({self._n}), got {a.shape}")
+        return a
+
+    def reset(self, states, seeds=None):
+        """Positions + streams; the trees are emptied.  `states`: n GameState objects of the batch's game, any mix of positions.
+        `seeds` (default: the constructor's, else fresh random ones): tree i's stream is that of MCTS(seed=seeds[i])."""
+        states = list(states)
+        if len(states) != self._n:
+            raise RuntimeError(f"reset: {self._n} positions expected, got {len(states)}")
+        for g in states:
+            if getattr(g, "GAME_ID", None) != self._game.GAME_ID:
+                raise RuntimeError("reset: every position must be a state of the batch's game")
+        if seeds is not None:
+            self._seeds = self._seed_array(seeds)
+        sd = self._seeds if self._seeds is not None else np.frombuffer(__import__("os").urandom(8 * self._n), np.uint64).copy()
+        offs = np.zeros(self._n + 1, np.uint32)
+        offs[1:] = np.cumsum([len(g._moves) for g in states])
+        moves = np.ascontiguousarray([m for g in states for m in g._moves], dtype=np.int32)
+        init, stride = None, 0
+        if any(g._init is not None for g in states):
+            # one image per tree, zero-padded to a common stride; a state without one starts from its class's fresh image
+            images = [bytes(g._init) if g._init is not None else type(g)().to_bytes() for g in states]
+            stride = max(len(b) for b in images)
+            init = np.zeros((self._n, stride), np.uint8)
+            for i, b in enumerate(images):
+                init[i, : len(b)] = np.frombuffer(b, np.uint8)
+        self._rows = None
+        check(lib.azmi_search_reset(self._h, None if init is None else init.ctypes.data, stride, moves.ctypes.data if moves.size else None,
+                                    offs.ctypes.data, sd.ctypes.data))
+
+    def search(self, visits, net=None, cache=None, root_noise=False):
+        """`visits` simulations of every tree, enqueued without host synchronisation (the read-outs and synchronize() wait).
+        net: a HipLeafNet (None = EvalType.RANDOM, dumb_eval); cache: a ShardedS3FIFOCache shared by all trees."""
+        if net is not None and (net.desc.num_moves != self._M or (net.desc.in_channels, net.desc.height, net.desc.width) != self._chw):
+            raise RuntimeError("search: the net's shape does not match the game")
+        if cache is not None:
+            cache._ensure_engine_layout()
+        check(lib.azmi_search_run(self._h, None if net is None else net._h, None if cache is None else cache._h, int(visits),
+                                  int(bool(root_noise)), C.c_void_p(-1)))
+
+    def synchronize(self):
+        check(lib.azmi_search_sync(self._h))
+
+    # ---- step API: any evaluator --------------------------------------------------------------------
+    def find_leaves(self, numpy=None):
+        """One simulation's descent of every tree -> (canonical [n_rows, C, H, W], tree_index [n_rows]): the leaves that need
+        an evaluation, rows in ascending tree order (terminal leaves are backed up at once and take no row).  Device tensors
+        (views of the object's buffers, valid until the next find_leaves) when torch is importable, numpy arrays otherwise or
+        with numpy=True."""
+        pc, pt, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        check(lib.azmi_search_find_leaves(self._h, C.c_void_p(-1), C.byref(pc), C.byref(pt), C.byref(n)))
+        self._rows = n.value
+        if numpy is None:
+            try:
+                import torch  # noqa: F401
+                numpy = False
+            except ImportError:
+                numpy = True
+        if numpy or n.value == 0:
+            canon = np.zeros((n.value,) + self._chw, np.float32)
+            idx = np.zeros(n.value, np.uint32)
+            check(lib.azmi_search_leaves_to_host(self._h, canon.ctypes.data, idx.ctypes.data))
+            if numpy:
+                return canon, idx
+            import torch
+            dev = torch.device("cuda", self._device)
+            return torch.from_numpy(canon).to(dev), torch.from_numpy(idx.astype(np.int32)).to(dev)
+        import torch
+        from ._torch_view import device_tensor
+        dev = torch.device("cuda", self._device)
+        return (device_tensor(pc.value, (n.value,) + self._chw, torch.float32, dev),
+                device_tensor(pt.value, (n.value,), torch.int32, dev))
+
+    def process_results(self, v, pi, root_noise=False):
+        """The evaluator's answers for the rows of the last find_leaves(): v [n_rows, P+1], pi [n_rows, M] probabilities,
+        device tensors or numpy arrays."""
+        if self._rows is None:
+            raise RuntimeError("process_results: no leaf batch is pending; call find_leaves first")
+        rows = self._rows
+        if tuple(v.shape) != (rows, self._P + 1) or tuple(pi.shape) != (rows, self._M):
+            raise RuntimeError(f"process_results: v must be [{rows}, {self._P + 1}] and pi [{rows}, {self._M}], "
+                               f"got {tuple(v.shape)} and {tuple(pi.shape)}")
+        if isinstance(v, np.ndarray) or isinstance(pi, np.ndarray):
+            vv = np.ascontiguousarray(v, dtype=np.float32); pp = np.ascontiguousarray(pi, dtype=np.float32)
+            check(lib.azmi_search_process_results_host(self._h, vv.ctypes.data, pp.ctypes.data, int(bool(root_noise))))
+        else:
+            import torch
+            vv = v.contiguous().float(); pp = pi.contiguous().float()
+            torch.cuda.current_stream(vv.device).synchronize()       # the evaluator ran on torch's stream, the trees on the engine's
+            check(lib.azmi_search_process_results(self._h, vv.data_ptr(), pp.data_ptr(), int(bool(root_noise)), C.c_void_p(-1)))
+            self.synchronize()                                       # vv / pp may be temporaries
+        self._rows = None
+
+    # ---- read-outs: one row per tree -------------------------------------------------------------------
+    def _query(self, kind, temp=0.0, arg=0):
+        f = np.zeros((self._n, self._vec), np.float32); u = np.zeros((self._n, self._vec + 64), np.uint32)
+        check(lib.azmi_search_query(self._h, kind, float(temp), int(arg), f.ctypes.data, u.ctypes.data))
+        return f, u
+
+    def counts(self): return self._query(0)[1][:, : self._M].copy()
+    def probs(self, temp): return self._query(1, temp)[0][:, : self._M].copy()
+    def probs_pruned(self, temp): return self._query(2, temp)[0][:, : self._M].copy()
+    def root_values(self): return self._query(3)[0][:, :3].copy()
+    def root_q_values(self): return self._query(4)[0][:, : self._M].copy()
+    def depths(self): return self._query(5)[1][:, 0].copy()
+    def root_ns(self): return self._query(5)[1][:, 1].copy()
+    def avg_leaf_depths(self): return self._query(5)[0][:, 0].copy()
+    def normalized_root_entropies(self): return self._query(5)[0][:, 1].copy()
+    def gumbel_enabled(self): return self._gumbel
+    def gumbel_improved_policies(self): return self._query(6)[0][:, : self._M].copy()
+    def gumbel_final_actions(self): return self._query(7)[1][:, 0].copy()
+    def set_gumbel_num_sims(self, n): check(lib.azmi_search_query(self._h, 12, 0.0, int(n), None, None))
+
+    def principal_variations(self, depth=5):
+        u = self._query(11, arg=depth)[1]
+        return [u[i, 1: 1 + int(u[i, 0])].copy() for i in range(self._n)]
+
+    def stats(self):
+        """launches: kernel launches the object has enqueued since creation (the net's own not included); net_calls; steps;
+        simulations / evaluator_leaves / terminal_leaves since the last reset, summed over the trees."""
+        out = np.zeros(6, np.uint64)
+        check(lib.azmi_search_stats(self._h, out.ctypes.data))
+        return dict(zip(("launches", "net_calls", "steps", "simulations", "evaluator_leaves", "terminal_leaves"), (int(x) for x in out)))
+
+
 def dumb_eval(gs):
     """game_state.h:160-173: uniform policy over the legal moves (u8 sum wraps), value 1/(P+1) each."""
     valids = gs.valid_moves()

@@ -192,6 +192,17 @@ SYMBOLS = {
     "azmi_mcts_reset_batch": (C.c_int, [_VP]),
     "azmi_mcts_update_root": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32]),
     "azmi_mcts_query": (C.c_int, [_VP, C.c_uint32, C.c_float, C.c_uint32, _VP, _VP, _VP]),
+    "azmi_search_create": (C.c_int, [C.c_int, _VP, C.c_uint32, C.c_int, _PP(C.c_void_p)]),
+    "azmi_search_destroy": (None, [_VP]),
+    "azmi_search_reset": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP]),
+    "azmi_search_find_leaves": (C.c_int, [_VP, _VP, _PP(C.c_void_p), _PP(C.c_void_p), _PP(C.c_uint32)]),
+    "azmi_search_process_results": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP]),
+    "azmi_search_leaves_to_host": (C.c_int, [_VP, _VP, _VP]),
+    "azmi_search_process_results_host": (C.c_int, [_VP, _VP, _VP, C.c_int]),
+    "azmi_search_run": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_int, _VP]),
+    "azmi_search_query": (C.c_int, [_VP, C.c_uint32, C.c_float, C.c_uint32, _VP, _VP]),
+    "azmi_search_sync": (C.c_int, [_VP]),
+    "azmi_search_stats": (C.c_int, [_VP, _VP]),
     "azmi_game_replay_ex": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32]),
     "azmi_game_replay_from": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "azmi_playout_eval": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP]),

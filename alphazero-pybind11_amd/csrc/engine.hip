@@ -1916,19 +1916,20 @@ uint32_t mcts_init_bytes(int game) {
 }
 }  // namespace
 
-int azmi_mcts_create(int game, const azmi_mcts_config* cfg, uint64_t seed, int device, azmi_mcts** out) {
-  if (!cfg || !out) return fail(AZMI_ERR_INVALID, "null argument");
+// the PlayParams of the engine behind MCTS(...) ctor arguments: `sims` simulations of arena per tree, every seat on model group 0
+// (shared with the batched search, search_batch.hip)
+int azmi_host_mcts_params(int game, const azmi_mcts_config* cfg, uint32_t sims, azmi_play_params* out_p) {
+  if (!cfg || !out_p) return fail(AZMI_ERR_INVALID, "null argument");
   GameInfo gi;
   if (!game_info(game, &gi)) return fail(AZMI_ERR_INVALID, "unknown game id %d", game);
   if (cfg->num_players != gi.P || cfg->num_moves != gi.M) return fail(AZMI_ERR_INVALID, "MCTS(num_players, num_moves) do not match the game");
   // MCTS(..., relative_values, ...) (mcts.h:54): on the device the rotation is part of the game's instantiation
   if ((cfg->relative_values != 0) != (game == AZMI_GAME_STARGAMBIT))
     return fail(AZMI_ERR_INVALID, "relative_values must be the game's relative_values() (true for StarGambit only)");
-  azmi_play_params p;
+  azmi_play_params& p = *out_p;
   azmi_play_params_default(&p);
   p.games_to_play = 1; p.concurrent_games = 1; p.max_batch_size = 1;
   p.num_mcts_visits = gi.P;
-  const uint32_t sims = cfg->max_simulations ? cfg->max_simulations : 50000u;
   // Connect4: arena = (21 * visits + 42) * 7 nodes >= sims * 7.  Wide games: two halves of 4 x (visits + 16) x 240 nodes,
   // compacted after update_root when the active half fills up
   for (uint32_t i = 0; i < gi.P; ++i) p.mcts_visits[i] = game == AZMI_GAME_CONNECT4 ? (sims + 20) / 21 : std::min<uint32_t>(sims, 8000u);
@@ -1938,11 +1939,24 @@ int azmi_mcts_create(int game, const azmi_mcts_config* cfg, uint64_t seed, int d
   p.gumbel_c_scale = cfg->gumbel_c_scale; p.gumbel_full = cfg->gumbel_full;
   p.num_model_groups_given = gi.P;
   for (uint32_t i = 0; i < gi.P; ++i) p.model_groups[i] = 0;
+  return AZMI_OK;
+}
+int azmi_host_check_init_rows(int game, const uint8_t* init, uint32_t init_stride, uint32_t n, uint32_t* extra_reps) {
+  return check_init_rows(game, init, init_stride, n, extra_reps);
+}
+
+int azmi_mcts_create(int game, const azmi_mcts_config* cfg, uint64_t seed, int device, azmi_mcts** out) {
+  if (!cfg || !out) return fail(AZMI_ERR_INVALID, "null argument");
+  GameInfo gi;
+  if (!game_info(game, &gi)) return fail(AZMI_ERR_INVALID, "unknown game id %d", game);
+  azmi_play_params p;
+  int rc = azmi_host_mcts_params(game, cfg, cfg->max_simulations ? cfg->max_simulations : 50000u, &p);
+  if (rc != AZMI_OK) return rc;
   azmi_engine_opts o;
   azmi_engine_opts_default(&o);
   o.seed = seed; o.device = device;
   auto m = new azmi_mcts();
-  int rc = azmi_pm_create(game, &p, &o, &m->pm);
+  rc = azmi_pm_create(game, &p, &o, &m->pm);
   if (rc != AZMI_OK) { delete m; return rc; }
   // the slot's stream is the object's stream; seed it directly (not through slot_seed) so that `seed` means what
   // MCTS::seed_thread_rng(seed) means in the reference tests

@@ -23,6 +23,11 @@ int azmi_host_fail(int code, const char* fmt, ...);
                             hipGetErrorString(e_));                                       \
   } while (0)
 
+// shared with search_batch.hip (defined in engine.hip): the PlayParams of the engine behind MCTS(...) constructor arguments with
+// room for `sims` simulations per tree, and the host-side check of a batch of serialized start positions
+extern "C" int azmi_host_mcts_params(int game, const azmi_mcts_config* cfg, uint32_t sims, azmi_play_params* out_p);
+extern "C" int azmi_host_check_init_rows(int game, const uint8_t* init, uint32_t init_stride, uint32_t n, uint32_t* extra_reps);
+
 namespace azmi {
 struct GameInfo {
   uint32_t P, M, C, H, W, maxk, max_turns, state_words;

@@ -154,17 +154,16 @@ enum MctsQuery : uint32_t {
   kQGumbelFinal = 7, kQAddRootNoise = 8, kQApplyRootTemp = 9, kQPickMove = 10, kQPrincipalVariation = 11, kQSetGumbelSims = 12, kQRootChildren = 13
 };
 
-// every read-out / small mutation of the root: dense [M] vectors go to out_f / out_u (lane m writes entry m)
+// every read-out / small mutation of the root: dense [M] vectors go to out_f / out_u (lane m writes entry m).
+// mcts_query_slot: the read-out of ONE slot's seat-0 tree by its lane group (the object: slot 0; the batched search: every slot)
 template <class GM>
-__global__ void k_mcts_query(EngineParams ep, EngineArrays ar, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
-  constexpr int G = GM::GROUP;
+__device__ __forceinline__ void mcts_query_slot(const EngineParams& ep, const EngineArrays& ar, uint32_t slot, uint32_t lane, uint32_t kind,
+                                                float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
   constexpr int P = GM::P;
   constexpr int M = GM::M;
-  const uint32_t lane = threadIdx.x;
-  if (lane >= static_cast<uint32_t>(G)) return;
-  SlotCtx<GM> c(ep, ar, 0, lane);
+  SlotCtx<GM> c(ep, ar, slot, lane);
   c.load();
-  if (ar.sstate[0] == kSlotFresh) c.start_game();   // first call: empty tree (root = node 0, arena bump = 1)
+  if (ar.sstate[slot] == kSlotFresh) c.start_game();   // first call: empty tree (root = node 0, arena bump = 1)
   c.sync_lanes();
   const size_t tb = c.tree_base(0);
   const uint32_t root = c.t_root[0];
@@ -263,6 +262,13 @@ __global__ void k_mcts_query(EngineParams ep, EngineArrays ar, uint32_t kind, fl
     default: break;
   }
   c.store(kSlotWaitEval);
+}
+
+template <class GM>
+__global__ void k_mcts_query(EngineParams ep, EngineArrays ar, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
+  const uint32_t lane = threadIdx.x;
+  if (lane >= static_cast<uint32_t>(GM::GROUP)) return;
+  mcts_query_slot<GM>(ep, ar, 0, lane, kind, temp, arg, out_f, out_u);
 }
 
 }  // namespace azmi
@@ -439,15 +445,15 @@ __global__ __launch_bounds__(64) void k_mcts_big_update_root(EngineParams ep, En
   if (lane == 0) ar.plen[0] = 0;
 }
 
+// mcts_big_query_slot: the read-out of ONE slot's seat-0 tree by its wavefront (the object: slot 0; the batched search: every slot)
 template <class GM>
-__global__ __launch_bounds__(64) void k_mcts_big_query(EngineParams ep, EngineArrays ar, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
-  __shared__ BigScratch<GM> sm;
+__device__ __forceinline__ void mcts_big_query_slot(const EngineParams& ep, const EngineArrays& ar, BigScratch<GM>& sm, uint32_t slot, uint32_t lane,
+                                                    uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
   constexpr int P = GM::P;
   constexpr uint32_t M = GM::M;
-  const uint32_t lane = threadIdx.x;
-  BigSlot<GM> c(ep, ar, sm, 0, lane);
+  BigSlot<GM> c(ep, ar, sm, slot, lane);
   c.load();
-  if (ar.sstate[0] == kSlotFresh) c.start_game();
+  if (ar.sstate[slot] == kSlotFresh) c.start_game();
   const size_t tb = c.tree_base(0);
   const uint32_t root = c.t_root[0];
   const uint64_t rmeta = ar.META[tb + root];
@@ -557,6 +563,12 @@ __global__ __launch_bounds__(64) void k_mcts_big_query(EngineParams ep, EngineAr
   }
   c.sync();
   c.store(kSlotWaitEval);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_mcts_big_query(EngineParams ep, EngineArrays ar, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
+  __shared__ BigScratch<GM> sm;
+  mcts_big_query_slot<GM>(ep, ar, sm, 0, threadIdx.x, kind, temp, arg, out_f, out_u);
 }
 
 }  // namespace azmi

@@ -1,0 +1,365 @@
+// Batched position search (azmi_search_*, include/azmi.h): N search trees on N different positions in ONE engine arena, all of
+// them advanced by one simulation per (find-leaves, process-results) launch pair, the leaf net and the position cache on the
+// device.  Host side of csrc/search_batch_kernels.h.  The engine behind it is a PlayManager engine with N slots built from the
+// MCTS constructor's arguments (azmi_host_mcts_params, as azmi_mcts_create does for its one slot); no game is ever played on it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/azmi.h"
+#include "cache_host.h"
+#include "engine_host.h"
+#define AZMI_KERNELS_NO_ASSIGN      // k_assign, the one plain kernel of engine_kernels.h, belongs to engine.hip
+#include "search_batch_kernels.h"
+
+using namespace azmi;
+
+#define SB_FAIL azmi_host_fail
+#define SB_TRY AZMI_HIP_TRY
+
+struct azmi_search {
+  azmi_pm* pm = nullptr;
+  uint32_t n = 0, max_sims = 0, sims_done = 0;
+  uint32_t chw = 0, vec_f = 0, vec_u = 0;
+  bool ready = false;          // reset() has given every tree a position
+  bool step_pending = false;   // find_leaves() without its process_results()
+  bool gumbel = false;
+  uint32_t step_rows = 0;
+  SbArrays sb{};
+  uint64_t* d_keys = nullptr;     // [N] ar.cache_keys of a search with a cache attached
+  float* d_batch = nullptr;       // [N, C, H, W] compacted leaf batch of the step API
+  float* d_vrows = nullptr;       // [N, P+1] / [N, M]: host evaluator answers staged for the step API
+  float* d_pirows = nullptr;
+  float* d_qf = nullptr;          // [N, vec_f] / [N, vec_u] read-out buffers
+  uint32_t* d_qu = nullptr;
+  uint64_t launches = 0, net_calls = 0, steps = 0;
+};
+
+namespace {
+
+constexpr uint32_t kSmallThreads = 256;
+inline uint32_t small_blocks(uint32_t n) { return (n * static_cast<uint32_t>(Connect4::GROUP) + kSmallThreads - 1) / kSmallThreads; }
+
+// SMALL / BIG: statements that use the game type GM (lane-group engine / one wavefront per tree)
+#define SB_DISPATCH(game, SMALL, BIG)                                            \
+  switch (game) {                                                                \
+    case AZMI_GAME_CONNECT4: { using GM = Connect4; SMALL; break; }              \
+    case AZMI_GAME_TAWLBWRDD: { using GM = Tawlbwrdd; BIG; break; }              \
+    case AZMI_GAME_BRANDUBH: { using GM = Brandubh; BIG; break; }                \
+    case AZMI_GAME_OPENTAFL: { using GM = OpenTafl; BIG; break; }                \
+    default: { using GM = StarGambit; BIG; break; }                              \
+  }
+
+void launch_find(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t eval_random, hipStream_t st) {
+  const uint32_t n = s->n;
+  SB_DISPATCH(s->pm->game, (k_sb_find<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, eval_random)),
+              (k_sb_big_find<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, eval_random)));
+  k_sb_compact<<<1, 1024, 0, st>>>(s->sb, n);
+  s->launches += 2;
+}
+
+void launch_process(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, const float* v_rows, const float* pi_rows,
+                    hipStream_t st) {
+  const uint32_t n = s->n;
+  SB_DISPATCH(s->pm->game, (k_sb_process<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows)),
+              (k_sb_big_process<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows)));
+  s->launches += 1;
+}
+
+void launch_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, hipStream_t st) {
+  const uint32_t n = s->n;
+  const EngineParams& ep = s->pm->ep;
+  const EngineArrays& ar = s->pm->ar;
+  SB_DISPATCH(s->pm->game, (k_sb_query<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u)),
+              (k_sb_big_query<GM><<<n, 64, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u)));
+  s->launches += 1;
+}
+
+// the answers of the step's net call go into the cache (PlayManager::update_inferences -> insert_many, play_manager.cc:631-640):
+// keys left by the find kernel, slot-indexed (pi, v) rows; ceil(N / kApplyMax) launches
+void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, hipStream_t st) {
+  for (uint32_t off = 0; off < s->n; off += kApplyMax) {
+    const uint32_t m = std::min<uint32_t>(kApplyMax, s->n - off);
+    SB_DISPATCH(s->pm->game, (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)),
+                (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)));
+    s->launches += 1;
+  }
+}
+
+// synchronises `st` and turns a stopped tree / a raised overflow bit into an error that names the tree
+int check_device(azmi_search* s, hipStream_t st) {
+  Control c;
+  std::vector<int32_t> status(s->n);
+  SB_TRY(hipMemcpyAsync(&c, s->pm->ar.ctl, sizeof(c), hipMemcpyDeviceToHost, st));
+  SB_TRY(hipMemcpyAsync(status.data(), s->sb.status, static_cast<size_t>(s->n) * 4, hipMemcpyDeviceToHost, st));
+  SB_TRY(hipStreamSynchronize(st));
+  for (uint32_t i = 0; i < s->n; ++i)
+    if (status[i] != 0)
+      return SB_FAIL(status[i] == -1 ? AZMI_ERR_INVALID : AZMI_ERR_OVERFLOW, "tree %u: %s (device overflow mask 0x%x)", i,
+                     status[i] == -1 ? "illegal move in the game record or malformed start position" : "find_leaf failed (tree arena or path capacity)",
+                     c.overflow);
+  if (c.overflow) return SB_FAIL(AZMI_ERR_OVERFLOW, "device search stopped: overflow mask 0x%x", c.overflow);
+  return AZMI_OK;
+}
+
+int begin_step(azmi_search* s, const char* what) {
+  if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (!s->ready) return SB_FAIL(AZMI_ERR_STATE, "%s: the trees have no positions; call reset first", what);
+  return AZMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, int device, azmi_search** out) {
+  if (!cfg || !out) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (n_trees == 0) return SB_FAIL(AZMI_ERR_INVALID, "n_trees must be > 0");
+  if (cfg->max_simulations == 0)
+    return SB_FAIL(AZMI_ERR_INVALID, "max_simulations is required for a batched search (it sizes every tree's arena; the one-tree default "
+                   "of 50000 times n_trees would not fit)");
+  azmi_play_params p;
+  int rc = azmi_host_mcts_params(game, cfg, cfg->max_simulations, &p);
+  if (rc != AZMI_OK) return rc;
+  if (game != AZMI_GAME_CONNECT4 && cfg->max_simulations > 8000u)
+    return SB_FAIL(AZMI_ERR_INVALID, "max_simulations: at most 8000 per tree for the wide games, got %u", cfg->max_simulations);
+  p.history_enabled = 0;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SB_FAIL(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  if (device < 0 || device >= ndev) return SB_FAIL(AZMI_ERR_INVALID, "device %d out of range", device);
+  SB_TRY(hipSetDevice(device));
+  azmi_engine_opts o;
+  azmi_engine_opts_default(&o);
+  o.device = device;
+  // does it fit?  Every array of the engine scales with the slot count: a one-slot engine tells the bytes per tree
+  {
+    azmi_pm* probe = nullptr;
+    rc = azmi_pm_create(game, &p, &o, &probe);
+    if (rc != AZMI_OK) return rc;
+    const size_t per_tree = probe->bytes;
+    azmi_pm_destroy(probe);
+    size_t free_b = 0, total_b = 0;
+    SB_TRY(hipMemGetInfo(&free_b, &total_b));
+    const unsigned long long need = static_cast<unsigned long long>(per_tree) * n_trees;
+    if (need > free_b)
+      return SB_FAIL(AZMI_ERR_OOM, "%u trees x %u simulations need %llu bytes of device memory (%llu per tree), %llu are free", n_trees,
+                     cfg->max_simulations, need, static_cast<unsigned long long>(per_tree), static_cast<unsigned long long>(free_b));
+  }
+  p.concurrent_games = n_trees; p.games_to_play = n_trees; p.max_batch_size = n_trees;
+  auto s = new azmi_search();
+  rc = azmi_pm_create(game, &p, &o, &s->pm);
+  if (rc != AZMI_OK) { delete s; return rc; }
+  azmi_pm* pm = s->pm;
+  s->n = n_trees; s->max_sims = cfg->max_simulations; s->gumbel = cfg->gumbel_enabled != 0;
+  s->chw = pm->gi.C * pm->gi.H * pm->gi.W;
+  s->vec_f = std::max<uint32_t>(pm->gi.M, 64u);
+  s->vec_u = s->vec_f + 64u;
+  const size_t N = n_trees;
+  auto A = [&](auto*& ptr, size_t cnt) { return pm->alloc(ptr, cnt, true); };
+  rc = A(s->sb.pend, N); if (rc == AZMI_OK) rc = A(s->sb.status, N); if (rc == AZMI_OK) rc = A(s->sb.row_of, N);
+  if (rc == AZMI_OK) rc = A(s->sb.rows, N); if (rc == AZMI_OK) rc = A(s->sb.n_rows, 1); if (rc == AZMI_OK) rc = A(s->sb.n_term, N);
+  if (rc == AZMI_OK) rc = A(s->d_keys, N);
+  if (rc == AZMI_OK) rc = A(s->d_batch, N * s->chw);
+  if (rc == AZMI_OK) rc = A(s->d_vrows, N * (pm->gi.P + 1)); if (rc == AZMI_OK) rc = A(s->d_pirows, N * pm->gi.M);
+  if (rc == AZMI_OK) rc = A(s->d_qf, N * s->vec_f); if (rc == AZMI_OK) rc = A(s->d_qu, N * s->vec_u);
+  if (rc != AZMI_OK) { azmi_pm_destroy(pm); delete s; return rc; }
+  *out = s;
+  return AZMI_OK;
+}
+
+void azmi_search_destroy(azmi_search* s) {
+  if (!s) return;
+  azmi_pm_destroy(s->pm);
+  delete s;
+}
+
+int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride, const int32_t* moves, const uint32_t* move_offsets,
+                      const uint64_t* seeds) {
+  if (!s || !move_offsets || !seeds) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  azmi_pm* pm = s->pm;
+  const uint32_t n = s->n;
+  if (move_offsets[0] != 0) return SB_FAIL(AZMI_ERR_INVALID, "move_offsets[0] must be 0");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (move_offsets[i + 1] < move_offsets[i]) return SB_FAIL(AZMI_ERR_INVALID, "tree %u: move_offsets must not decrease", i);
+    if (move_offsets[i + 1] - move_offsets[i] > pm->gi.max_turns + 8) return SB_FAIL(AZMI_ERR_INVALID, "tree %u: game record too long", i);
+  }
+  const uint32_t total = move_offsets[n];
+  if (total && !moves) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (init) {
+    uint32_t extra = 0;
+    const int rc = azmi_host_check_init_rows(pm->game, init, init_stride, n, &extra);
+    if (rc != AZMI_OK) return rc;
+  }
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->stream;
+  s->ready = false; s->step_pending = false; s->sims_done = 0;
+  std::vector<void*> tmp;
+  auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); };
+  auto up = [&](void** d, const void* h, size_t bytes) {
+    hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess) return e;
+    tmp.push_back(*d);
+    return bytes ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  };
+#define SB_TRY2(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); cleanup(); return SB_FAIL(AZMI_ERR_NO_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
+  uint8_t* d_init = nullptr; int32_t* d_moves = nullptr; uint32_t* d_offs = nullptr; uint64_t* d_seeds = nullptr;
+  if (init) SB_TRY2(up(reinterpret_cast<void**>(&d_init), init, static_cast<size_t>(n) * init_stride));
+  SB_TRY2(up(reinterpret_cast<void**>(&d_moves), moves, static_cast<size_t>(total) * 4));
+  SB_TRY2(up(reinterpret_cast<void**>(&d_offs), move_offsets, (static_cast<size_t>(n) + 1) * 4));
+  SB_TRY2(up(reinterpret_cast<void**>(&d_seeds), seeds, static_cast<size_t>(n) * 8));
+  SB_TRY2(hipMemsetAsync(pm->ar.ctl, 0, sizeof(Control), st));       // a stopped search does not outlive its positions
+  SB_DISPATCH(pm->game, (k_sb_seed<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds)),
+              (k_sb_big_seed<GM><<<n, 64, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds)));
+  s->launches += 1;
+  SB_TRY2(hipGetLastError());
+  pm->last = st;
+  const int rc = check_device(s, st);
+  cleanup();
+#undef SB_TRY2
+  if (rc != AZMI_OK) return rc;
+  s->ready = true;
+  return AZMI_OK;
+}
+
+int azmi_search_find_leaves(azmi_search* s, void* stream, float** dev_canonical, uint32_t** dev_tree_index, uint32_t* n_rows) {
+  int rc = begin_step(s, "find_leaves"); if (rc) return rc;
+  if (!n_rows) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "find_leaves: the previous step's process_results has not been called");
+  if (s->sims_done + 1 > s->max_sims) return SB_FAIL(AZMI_ERR_OVERFLOW, "find_leaves: max_simulations = %u reached", s->max_sims);
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->pick(stream);
+  launch_find(s, pm->ep, pm->ar, 0u, st);
+  k_sb_gather<<<s->n, 256, 0, st>>>(s->sb, s->n, pm->ar.canon, s->chw, s->d_batch);
+  s->launches += 1;
+  SB_TRY(hipGetLastError());
+  uint32_t rows = 0;
+  SB_TRY(hipMemcpyAsync(&rows, s->sb.n_rows, 4, hipMemcpyDeviceToHost, st));
+  rc = check_device(s, st); if (rc) return rc;
+  s->step_pending = true; s->step_rows = rows;
+  if (dev_canonical) *dev_canonical = s->d_batch;
+  if (dev_tree_index) *dev_tree_index = s->sb.rows;
+  *n_rows = rows;
+  return AZMI_OK;
+}
+
+int azmi_search_leaves_to_host(azmi_search* s, float* canonical, uint32_t* tree_index) {
+  if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "no leaf batch: call find_leaves first");
+  SB_TRY(hipSetDevice(s->pm->device));
+  hipStream_t st = s->pm->last;
+  if (canonical && s->step_rows) SB_TRY(hipMemcpyAsync(canonical, s->d_batch, static_cast<size_t>(s->step_rows) * s->chw * 4, hipMemcpyDeviceToHost, st));
+  if (tree_index && s->step_rows) SB_TRY(hipMemcpyAsync(tree_index, s->sb.rows, static_cast<size_t>(s->step_rows) * 4, hipMemcpyDeviceToHost, st));
+  SB_TRY(hipStreamSynchronize(st));
+  return AZMI_OK;
+}
+
+int azmi_search_process_results(azmi_search* s, const float* dev_v, const float* dev_pi, int root_noise_enabled, void* stream) {
+  int rc = begin_step(s, "process_results"); if (rc) return rc;
+  if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "process_results: no leaf batch is pending; call find_leaves first");
+  if (s->step_rows && (!dev_v || !dev_pi)) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->pick(stream);
+  // (with no rows the pointers are not read: every pending tree is a terminal leaf already backed up)
+  launch_process(s, pm->ep, pm->ar, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
+  SB_TRY(hipGetLastError());
+  s->step_pending = false;
+  s->sims_done += 1; s->steps += 1;
+  return AZMI_OK;
+}
+
+int azmi_search_process_results_host(azmi_search* s, const float* v, const float* pi, int root_noise_enabled) {
+  int rc = begin_step(s, "process_results"); if (rc) return rc;
+  if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "process_results: no leaf batch is pending; call find_leaves first");
+  if (s->step_rows && (!v || !pi)) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->last;
+  if (s->step_rows) {
+    SB_TRY(hipMemcpyAsync(s->d_vrows, v, static_cast<size_t>(s->step_rows) * (pm->gi.P + 1) * 4, hipMemcpyHostToDevice, st));
+    SB_TRY(hipMemcpyAsync(s->d_pirows, pi, static_cast<size_t>(s->step_rows) * pm->gi.M * 4, hipMemcpyHostToDevice, st));
+  }
+  rc = azmi_search_process_results(s, s->d_vrows, s->d_pirows, root_noise_enabled, st);
+  if (rc) return rc;
+  SB_TRY(hipStreamSynchronize(st));     // the host arrays may be reused by the caller
+  return AZMI_OK;
+}
+
+int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream) {
+  int rc = begin_step(s, "search"); if (rc) return rc;
+  if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "search: a find_leaves step is pending; call process_results first");
+  if (visits > s->max_sims - s->sims_done)
+    return SB_FAIL(AZMI_ERR_OVERFLOW, "search of %u visits: %u of max_simulations = %u are already used", visits, s->sims_done, s->max_sims);
+  azmi_pm* pm = s->pm;
+  EngineParams ep = pm->ep;
+  EngineArrays ar = pm->ar;
+  if (cache && net) {
+    if (cache->device != pm->device) return SB_FAIL(AZMI_ERR_INVALID, "cache lives on another device");
+    if (cache->c.np != pm->gi.M || cache->c.nv != pm->gi.P + 1) return SB_FAIL(AZMI_ERR_INVALID, "cache: num_policy / num_value do not match the game");
+    if (cache->c.cap != kWaveCap)
+      return SB_FAIL(AZMI_ERR_INVALID, "cache: the engine probes 64-entry shards; create the cache with shards = max_size / 64 "
+                     "(ShardedS3FIFOCache.for_engine)");
+    ep.cache_on = 1; ep.num_groups = 1;
+    ar.cache = cache->c; ar.cache_keys = s->d_keys;
+  }
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->pick(stream);
+  if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
+  const uint32_t rn = root_noise_enabled ? 1u : 0u;
+  // `visits` step pairs, enqueued back to back: the row count of a step never leaves the device
+  for (uint32_t i = 0; i < visits; ++i) {
+    launch_find(s, ep, ar, net ? 0u : 1u, st);
+    if (net) {
+      rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
+      if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
+      s->net_calls += 1;
+      if (ep.cache_on) launch_cache_insert(s, ep, ar, st);
+    }
+    launch_process(s, ep, ar, rn, nullptr, nullptr, st);
+  }
+  SB_TRY(hipGetLastError());
+  s->sims_done += visits; s->steps += visits;
+  return AZMI_OK;
+}
+
+int azmi_search_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
+  int rc = begin_step(s, "query"); if (rc) return rc;
+  if (!(kind <= kQGumbelFinal || kind == kQPrincipalVariation || kind == kQSetGumbelSims))
+    return SB_FAIL(AZMI_ERR_INVALID, "query kind %u is not available on a batched search", kind);
+  if (kind == kQPrincipalVariation && arg > 60) arg = 60;
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->last;
+  launch_query(s, kind, temp, arg, st);
+  SB_TRY(hipGetLastError());
+  if (out_f) SB_TRY(hipMemcpyAsync(out_f, s->d_qf, static_cast<size_t>(s->n) * s->vec_f * 4, hipMemcpyDeviceToHost, st));
+  if (out_u) SB_TRY(hipMemcpyAsync(out_u, s->d_qu, static_cast<size_t>(s->n) * s->vec_u * 4, hipMemcpyDeviceToHost, st));
+  return check_device(s, st);
+}
+
+int azmi_search_sync(azmi_search* s) {
+  if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  SB_TRY(hipSetDevice(s->pm->device));
+  return check_device(s, s->pm->last);
+}
+
+int azmi_search_stats(azmi_search* s, uint64_t out[6]) {
+  if (!s || !out) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  std::vector<uint64_t> sims(s->n), evals(s->n);
+  std::vector<uint32_t> term(s->n);
+  SB_TRY(hipStreamSynchronize(pm->last));
+  SB_TRY(hipMemcpy(sims.data(), pm->ar.c_sims, static_cast<size_t>(s->n) * 8, hipMemcpyDeviceToHost));
+  SB_TRY(hipMemcpy(evals.data(), pm->ar.c_evals, static_cast<size_t>(s->n) * 8, hipMemcpyDeviceToHost));
+  SB_TRY(hipMemcpy(term.data(), s->sb.n_term, static_cast<size_t>(s->n) * 4, hipMemcpyDeviceToHost));
+  uint64_t a = 0, b = 0, t = 0;
+  for (uint32_t i = 0; i < s->n; ++i) { a += sims[i]; b += evals[i]; t += term[i]; }
+  out[0] = s->launches; out[1] = s->net_calls; out[2] = s->steps; out[3] = a; out[4] = b; out[5] = t;
+  return AZMI_OK;
+}
+
+}  // extern "C"

@@ -346,6 +346,51 @@ int azmi_mcts_reset_batch(azmi_mcts* m);
  * 12 set_gumbel_num_sims(arg).  out_f / out_u are HOST arrays of at least max(M, 64) entries (may be NULL if unused). */
 int azmi_mcts_query(azmi_mcts* m, uint32_t kind, float temp, uint32_t arg, const float* in_f, float* out_f, uint32_t* out_u);
 
+/* ---- batched position search: `n_trees` independent MCTS trees, each on its own position, advanced together - what the
+ * reference's evaluation tools do with a list of MCTS objects stepped in lock step, leaves batched into one net call and one
+ * shared S3FIFOCache, no move played (frozen_eval.py:545-660, mcts_analysis.py:923-1049, play.py:292-343).  All five games.
+ * Tree i is bit for bit the stand-alone azmi_mcts created with seed seeds[i] and driven call by call from the same position
+ * with the same evaluator values.  Every tree runs exactly one simulation per step (a terminal leaf or a cache hit is one
+ * too, mcts.cc:500-555), so a search of `visits` is `visits` step pairs.
+ *   create   cfg as for azmi_mcts_create; cfg->max_simulations sizes EVERY tree's arena and is required (0 is an error; at
+ *            most 8000 for the wide games); a size that does not fit the device fails with the byte count in the message
+ *   reset    positions + streams, trees emptied: tree i = start position init + i * init_stride (NULL = the initial position;
+ *            images as in azmi_game_replay_from, rows zero-padded to one stride) + moves[move_offsets[i] .. move_offsets[i + 1]);
+ *            its pcg32 stream is seeded seeds[i] the way azmi_mcts_create seeds its one stream.  HOST arrays.  An illegal move
+ *            or a malformed image fails the call with AZMI_ERR_INVALID naming the (first) tree; call reset again to go on
+ *   run      `visits` x (find leaves -> leaf net over the compacted row list -> cache insert -> process results), enqueued on
+ *            `stream` with no host synchronisation: the row count of a step stays on the device.  net == NULL: every leaf is
+ *            evaluated with dumb_eval (EvalType::RANDOM).  cache (or NULL; ignored without a net): an azmi_cache in the
+ *            engine's layout (shards = max_size / 64) probed by every leaf and fed with every net answer; a hit takes no row.
+ *            Asynchronous: errors of the device side (arena overflow) surface at the next query / sync.  Running past
+ *            max_simulations fails with AZMI_ERR_OVERFLOW before anything is enqueued.
+ *   find_leaves / process_results   the step API for any evaluator: one simulation's descent of every tree; terminal leaves
+ *            are backed up at once, every other leaf's canonical planes become one row of *dev_canonical [*n_rows, C, H, W]
+ *            (device memory owned by the object, rows in ascending tree order) with its tree index in *dev_tree_index
+ *            [*n_rows]; synchronises `stream` to report *n_rows.  process_results takes the evaluator's answers by row:
+ *            dev_v [n_rows, P+1], dev_pi [n_rows, M] probabilities (device memory), asynchronous on `stream`.
+ *            leaves_to_host / process_results_host: the same through HOST arrays.
+ *   query    the read-outs of azmi_mcts_query for all trees in one launch; kinds 0-7 and 11, and 12 set_gumbel_num_sims(arg)
+ *            (run does that itself with arg = visits).  out_f is a HOST array [n_trees, max(M, 64)], out_u
+ *            [n_trees, max(M, 64) + 64], row i laid out as azmi_mcts_query lays out its one row (either may be NULL)
+ *   sync     waits for everything enqueued and reports a device-side error
+ *   stats    out[6] = kernel launches enqueued by the object since creation (the net's own launches not included), net calls,
+ *            steps, simulations / leaves given to the evaluator / terminal leaves since the last reset (summed over the trees) */
+typedef struct azmi_search azmi_search;
+int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, int device, azmi_search** out);
+void azmi_search_destroy(azmi_search* s);
+int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride, const int32_t* moves, const uint32_t* move_offsets,
+                      const uint64_t* seeds);
+int azmi_search_find_leaves(azmi_search* s, void* stream, float** dev_canonical, uint32_t** dev_tree_index, uint32_t* n_rows);
+int azmi_search_process_results(azmi_search* s, const float* dev_v, const float* dev_pi, int root_noise_enabled, void* stream);
+int azmi_search_leaves_to_host(azmi_search* s, float* canonical, uint32_t* tree_index);
+int azmi_search_process_results_host(azmi_search* s, const float* v, const float* pi, int root_noise_enabled);
+typedef struct azmi_net azmi_net;
+int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream);
+int azmi_search_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u);
+int azmi_search_sync(azmi_search* s);
+int azmi_search_stats(azmi_search* s, uint64_t out[6]);
+
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
  *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------
  * `blob` is the BatchNorm-folded, MFMA-fragment-ordered weight image produced by
