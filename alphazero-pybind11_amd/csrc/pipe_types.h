@@ -93,7 +93,7 @@ struct PipeEpoch {        // an allocation of its own, zeroed before every epoch
   uint32_t tree_arrived, net_arrived;   // census: workgroups that started
   uint32_t tree_late, net_late;   // census: the latest start of a tree / net workgroup, in 100 MHz ticks after the first workgroup of the epoch
   uint32_t tree_late_n, net_late_n;   // calibration launches: workgroups that only started when the others had left
-  uint32_t svc_arrived, svc_late_n;   // conveyor: its service workgroups that started / that only started when the others had left (calibration)
+  uint32_t reserved[2];   // (the census words of the removed conveyor experiment: kept so that no other word's offset moves)
   uint32_t pad1[20];
   // ---- line 2: words the tree wavefronts WRITE all the time (round 5: off the polled line - an atomic on a line that hundreds of idle
   // workgroups read every microsecond waits behind them)

@@ -25,13 +25,6 @@
 #include "engine_kernels.h"
 #include "leafnet_c4.h"
 #include "pipe_types.h"
-// The conveyor (round 5's weight-stationary net side: bit-identical to the tile kernel, slower - DESIGN 4.5b) is an EXPERIMENT since
-// round 6: its device code lives in scripts/experiments/conveyor_c4.h and is compiled in only with -DAZMI_WITH_CONVEYOR
-// (AZMI_HIPCC_EXTRA=-DAZMI_WITH_CONVEYOR python -c "import __graft_entry__ as g; g.build()"); the default library carries the host
-// plumbing and answers AZMI_PIPE_NET=conveyor with an error.
-#ifdef AZMI_WITH_CONVEYOR
-#include "../../scripts/experiments/conveyor_c4.h"
-#endif
 
 using namespace azmi;
 
@@ -1318,50 +1311,6 @@ __global__ void k_pair_wait(uint32_t* flag) {
 }
 __global__ void k_pair_set(uint32_t* flag) { g_st(flag, 1u); }
 
-#ifdef AZMI_WITH_CONVEYOR
-// ---- the conveyor (conveyor_c4.h): its service kernel, and the launch-order helper --------------------------------------------------------
-namespace cvn = azmi_net_dev::cv;
-struct C4KeyFn {      // Connect4::key of a packed position (what k_pipe_net computes for the answer table)
-  __device__ unsigned long long operator()(unsigned long long b0, unsigned long long b1, uint32_t pl) const {
-    Connect4::State s_; s_.bb[0] = b0; s_.bb[1] = b1; s_.player = pl; s_.turn = 0;
-    return Connect4::key(s_);
-  }
-};
-// census of a calibration launch (pipe_calibrate): the workgroup announces itself, holds its place until `hold` ticks after the
-// epoch's first workgroup and leaves; returns true in that case
-__device__ __forceinline__ bool cv_census(PipeEpoch* pe, uint32_t hold, uint32_t* arrived, uint32_t* late_n) {
-  const uint64_t t_start = wall_clock64();
-  if (threadIdx.x == 0) {
-    unsigned long long t0 = atomicCAS(&pe->t0, 0ull, static_cast<unsigned long long>(t_start));
-    if (t0 == 0ull) t0 = t_start;
-    atomicMax(&pe->net_late, static_cast<uint32_t>(t_start > t0 ? t_start - t0 : 0ull));
-    atomicAdd(arrived, 1u);
-    if (hold != 0u && t_start > t0 && t_start - t0 >= hold) atomicAdd(late_n, 1u);
-  }
-  if (hold == 0u) return false;
-  __syncthreads();
-  const unsigned long long t0 = g_ld(&pe->t0);
-  while (wall_clock64() < t0 + hold) __builtin_amdgcn_s_sleep(32);
-  return true;
-}
-__global__ __launch_bounds__(256, 1) void k_cv_line_pipe(cvn::CvArgs a, PipeEpoch* pe, uint32_t hold) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds_cvl[];
-  if (cv_census(pe, hold, &pe->net_arrived, &pe->net_late_n)) return;
-  cvn::line_wg(a, lds_cvl);
-}
-__global__ __launch_bounds__(cvn::SVC_THREADS, 2) void k_cv_service(cvn::CvArgs a, cvn::SvcPipe sp, PipeEpoch* pe, uint32_t hold) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds_cvs[];
-  if (cv_census(pe, hold, &pe->svc_arrived, &pe->svc_late_n)) return;
-  cvn::service_wg<C4KeyFn, 4, 16>(a, sp, lds_cvs, C4KeyFn{});
-}
-#endif   // AZMI_WITH_CONVEYOR
-// the tree kernel is launched behind this one: the conv workgroups (a whole CU each) take their places first, the tree workgroups
-// pack into what is left (two per CU).  Gives up after 0.5 ms: placement is speed, never correctness
-__global__ void k_cv_wait_started(PipeEpoch* pe, uint32_t want) {
-  const uint64_t t0 = wall_clock64();
-  while (g_ld(&pe->net_arrived) < want && wall_clock64() - t0 < 50000ull) __builtin_amdgcn_s_sleep(32);
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 struct PipeState {
   PipeArrays pa{};
@@ -1381,7 +1330,6 @@ struct PipeState {
   azmi_net_dev::NetPtrs np1{};
   int kind = 0;                     // PipePlan::kind of the current call (which tree kernel)
   bool calibrated = false;          // net_wgs has been measured beside the tree workgroups (pipe_calibrate)
-  bool svc_paired = false; hipStream_t svc_paired_with = nullptr;      // the conveyor's service stream runs beside `svc_paired_with` and net_stream
   uint32_t calib_rounds = 0;
   // balance between the two sides (pipe_balance): rings are allocated for tree_wgs_alloc workgroups, `places` = tree + net workgroups
   // the chip was measured to hold, the cumulative counters are those of the previous call
@@ -1389,13 +1337,6 @@ struct PipeState {
   bool balance = false;
   unsigned long long bal_sims = 0, bal_boards = 0;
   uint32_t lost_seen = 0;           // PipeCtl::lost_total already reported
-  // the conveyor (conveyor_c4.h): the net side as lines of weight-stationary conv workgroups + one service workgroup per line
-  bool cv_on = false;               // this call runs it (else: the tile kernel k_pipe_net)
-  hipStream_t svc_stream = nullptr;
-  hipEvent_t ev_svc = nullptr;
-  uint32_t cv_lines = 0, cv_lines_alloc = 0, cv_nwg = 0, cv_heads = 2;
-  uint32_t* cv_xh = nullptr; uint8_t* cv_xt = nullptr; uint8_t* cv_xs = nullptr; uint32_t* cv_meta = nullptr; unsigned long long* cv_stat = nullptr;
-  bool cv_calibrated = false;
   const void* l0_nets[2] = {nullptr, nullptr};      // the weight images the answer table's entries were computed with (group 0, group 1)
   // CU split (AZMI_PIPE_CU_SPLIT=T): the tree kernel on a stream masked to T CUs, the net kernel on the others
   uint32_t cu_split = 0, cu_total = 0;
@@ -1406,10 +1347,8 @@ void pipe_state_free(PipeState* p) {
   if (!p) return;
   for (void* q : p->allocs) (void)hipFree(q);
   if (p->net_stream) (void)hipStreamDestroy(p->net_stream);
-  if (p->svc_stream) (void)hipStreamDestroy(p->svc_stream);
   if (p->tree_stream) (void)hipStreamDestroy(p->tree_stream);
   if (p->ev_tree) (void)hipEventDestroy(p->ev_tree);
-  if (p->ev_svc) (void)hipEventDestroy(p->ev_svc);
   for (hipStream_t q : p->parked) (void)hipStreamDestroy(q);
   if (p->ev_go) (void)hipEventDestroy(p->ev_go);
   if (p->ev_net) (void)hipEventDestroy(p->ev_net);
@@ -1613,167 +1552,7 @@ int pipe_pair_streams(PipeState* ps, hipStream_t st) {
                         "the pipeline needs its tree and net kernels on the chip together - use azmi_run_rounds");
 }
 
-// The conveyor's service kernel is a THIRD persistent kernel: its stream must share a hardware queue with neither the caller's stream
-// nor net_stream (the runtime deals streams onto a few queues round-robin; a kernel queued behind a persistent one starts when the
-// epoch is over).  Same probe as above, against both partners; streams that fail are parked.
-int pipe_pair_svc(PipeState* ps, hipStream_t st) {
-  if (ps->svc_paired && ps->svc_paired_with == st) return AZMI_OK;
-  if (!ps->pair_flag) { const int rc = pipe_alloc(ps, ps->pair_flag, 4); if (rc != AZMI_OK) return rc; }
-  for (int attempt = 0; attempt < 12; ++attempt) {
-    bool ok = true;
-    for (hipStream_t partner : {st, ps->net_stream}) {
-      AZMI_HIP_TRY(hipMemsetAsync(ps->pair_flag, 0, 4 * sizeof(uint32_t), partner));
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_go, partner));
-      AZMI_HIP_TRY(hipStreamWaitEvent(ps->svc_stream, ps->ev_go, 0));
-      k_pair_wait<<<1, 1, 0, partner>>>(ps->pair_flag);
-      AZMI_HIP_TRY(hipGetLastError());
-      k_pair_set<<<1, 1, 0, ps->svc_stream>>>(ps->pair_flag);
-      AZMI_HIP_TRY(hipGetLastError());
-      uint32_t h[2] = {0, 0};
-      AZMI_HIP_TRY(hipStreamSynchronize(ps->svc_stream));
-      AZMI_HIP_TRY(hipMemcpyAsync(h, ps->pair_flag, sizeof(h), hipMemcpyDeviceToHost, partner));
-      AZMI_HIP_TRY(hipStreamSynchronize(partner));
-      if (h[1] != 0u) { ok = false; break; }
-    }
-    if (ok) { ps->svc_paired = true; ps->svc_paired_with = st; return AZMI_OK; }
-    ps->parked.push_back(ps->svc_stream);
-    ps->svc_stream = nullptr;
-    AZMI_HIP_TRY(hipStreamCreateWithFlags(&ps->svc_stream, hipStreamNonBlocking));
-  }
-  return azmi_host_fail(AZMI_ERR_STATE, "azmi_run_pipeline: no third stream runs beside the caller's and the net side's (GPU_MAX_HW_QUEUES < 3?): the conveyor "
-                        "needs three kernels on the chip together; AZMI_PIPE_NET=tiles runs the tile kernel");
-}
-
 void pipe_launch_tree(azmi_pm* pm, PipeState* ps, const PipeArrays& pa, hipStream_t st, bool prof);
-#ifdef AZMI_WITH_CONVEYOR
-// ---- the conveyor's host side ---------------------------------------------------------------------------------------------------------
-// When the net side can be the conveyor (conveyor_c4.h): the bf16 tier, one model group, an even number of residual blocks (a conv
-// workgroup = two blocks).  Round 5: opt-in (AZMI_PIPE_NET=conveyor; an error where it cannot run) - bit for bit the tile kernel's
-// answers, but at 0.25 of the MFMA peak alone on the chip against the tile kernel's 0.45 (DESIGN section 4.5b says what is missing).
-bool cv_eligible(const azmi_pm* pm, const PipePlan& plan) {
-  const char* e = getenv("AZMI_PIPE_NET");
-  if (!e || strcmp(e, "conveyor") != 0) return false;
-  const azmi_net_dev::NetDesc& nd = plan.view[0].nd;
-  return !plan.tree_only && plan.kind == 1 && plan.net_groups == 1u && pm->ep.num_groups == 1u && plan.view[0].x3 == 0 && nd.depth >= 2 && nd.depth % 2 == 0;
-}
-uint32_t cv_default_lines(uint32_t cus, uint32_t nwg, uint32_t tree_wgs) {
-  // CUs: a conv workgroup each (it takes its CU's registers whole), a service workgroup each (two would fit a CU, but the dispatcher
-  // deals them one per CU while CUs are free), two tree workgroups per CU - inside nine tenths of the chip: the three kernels' workgroups
-  // are dealt at the same time, and a conv workgroup needs a CU that nothing else has touched (cv_calibrate gives lines up from there)
-  uint32_t lines = 1;
-  while ((lines + 1u) * (nwg + 1u) + (tree_wgs + 1u) / 2u <= cus - cus / 10u) ++lines;
-  return lines;
-}
-int cv_setup(azmi_pm* pm, PipeState* ps, const azmi_net_c4_view& view) {
-  const uint32_t nwg = static_cast<uint32_t>(view.nd.depth) / 2u;
-  hipDeviceProp_t prop;
-  AZMI_HIP_TRY(hipGetDeviceProperties(&prop, pm->device));
-  const uint32_t cus = static_cast<uint32_t>(prop.multiProcessorCount);
-  if (!ps->svc_stream) {
-    AZMI_HIP_TRY(hipStreamCreateWithFlags(&ps->svc_stream, hipStreamNonBlocking));
-    AZMI_HIP_TRY(hipEventCreateWithFlags(&ps->ev_svc, hipEventDisableTiming));
-    AZMI_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cv_line_pipe), hipFuncAttributeMaxDynamicSharedMemorySize, cvn::LINE_LDS_BYTES));
-    AZMI_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cv_service), hipFuncAttributeMaxDynamicSharedMemorySize, cvn::SVC_LDS_BYTES));
-  }
-  const uint32_t want_alloc = std::max<uint32_t>(1u, cus / nwg);
-  if (ps->cv_nwg != nwg || ps->cv_lines_alloc < want_alloc) {
-    // (buffers of an earlier net shape stay in ps->allocs until the engine goes: a change of depth on one engine is rare)
-    const size_t rings = static_cast<size_t>(want_alloc) * (nwg + 1u);
-    int rc = pipe_alloc(ps, ps->cv_xh, rings * 128);
-    if (rc == AZMI_OK) rc = pipe_alloc(ps, ps->cv_xt, rings * cvn::X_T);
-    if (rc == AZMI_OK) rc = pipe_alloc(ps, ps->cv_xs, rings * cvn::X_S);
-    if (rc == AZMI_OK) rc = pipe_alloc(ps, ps->cv_meta, static_cast<size_t>(want_alloc) * cvn::MGRP * 32);
-    if (rc == AZMI_OK && !ps->cv_stat) rc = pipe_alloc(ps, ps->cv_stat, 32);
-    if (rc != AZMI_OK) return rc;
-    ps->cv_nwg = nwg; ps->cv_lines_alloc = want_alloc; ps->cv_calibrated = false;
-    ps->cv_lines = 0;
-  }
-  if (ps->cv_lines == 0) {
-    uint32_t lines = cv_default_lines(cus, nwg, ps->tree_wgs);
-    if (const char* e = getenv("AZMI_CV_LINES")) lines = static_cast<uint32_t>(std::max(1, atoi(e)));
-    ps->cv_lines = std::min(lines, ps->cv_lines_alloc);
-    ps->cv_heads = getenv("AZMI_CV_HEADS") ? static_cast<uint32_t>(std::min(2, std::max(1, atoi(getenv("AZMI_CV_HEADS"))))) : 2u;
-  }
-  return AZMI_OK;
-}
-cvn::CvArgs cv_args(const PipeState* ps, const azmi_net_c4_view& view, const PipeArrays& pa) {
-  cvn::CvArgs a{};
-  a.nd = view.nd; a.np = view.np;
-  a.xh = ps->cv_xh; a.xt = ps->cv_xt; a.xs = ps->cv_xs; a.meta = ps->cv_meta;
-  a.lines = ps->cv_lines; a.nwg = ps->cv_nwg;
-  a.dbg_flags = getenv("AZMI_CV_DBG") ? static_cast<uint32_t>(atoi(getenv("AZMI_CV_DBG"))) : 0u;
-  a.err = &pa.ctl->err; a.stop = &pa.ep->stop; a.cap_ticks = pa.cap_ticks; a.stat = ps->cv_stat;
-  return a;
-}
-cvn::SvcPipe cv_svc(const PipeState* ps, const PipeArrays& pa) {
-  cvn::SvcPipe sp{};
-  sp.ring = pa.ring; sp.head = &pa.ctl->head; sp.tail = &pa.ctl->tail;
-  sp.stop = &pa.ep->stop; sp.tree_done = &pa.ep->tree_done; sp.tree_arrived = &pa.ep->tree_arrived;
-  sp.res = pa.res; sp.l0 = pa.l0; sp.l0_mask = pa.l0_mask;
-  sp.rring = pa.rring; sp.rshift = pa.rshift; sp.n_tree_wgs = pa.n_tree_wgs; sp.wg_rtail = reinterpret_cast<uint32_t*>(pa.wg);
-  sp.tiles = &pa.ctl->tiles; sp.tile_boards = &pa.ctl->tile_boards; sp.lost = &pa.ep->lost; sp.lost_total = &pa.ctl->lost_total;
-  sp.dbg = pa.ctl->dbg; sp.n_heads = ps->cv_heads;
-  return sp;
-}
-// one epoch's conveyor launches: the ring headers are zeroed on `st` (ahead of ev_go), the conv lines go to net_stream, the service
-// workgroups to svc_stream; both streams are joined back into `st` by the caller (ev_net, ev_svc)
-int cv_launch(PipeState* ps, const azmi_net_c4_view& view, const PipeArrays& pa, uint32_t hold) {
-  const cvn::CvArgs a = cv_args(ps, view, pa);
-  k_cv_line_pipe<<<ps->cv_lines * ps->cv_nwg, 256, cvn::LINE_LDS_BYTES, ps->net_stream>>>(a, pa.ep, hold);
-  AZMI_HIP_TRY(hipGetLastError());
-  k_cv_service<<<ps->cv_lines, cvn::SVC_THREADS, cvn::SVC_LDS_BYTES, ps->svc_stream>>>(a, cv_svc(ps, pa), pa.ep, hold);
-  AZMI_HIP_TRY(hipGetLastError());
-  return AZMI_OK;
-}
-int cv_zero_headers(PipeState* ps, hipStream_t st) {
-  AZMI_HIP_TRY(hipMemsetAsync(ps->cv_xh, 0, static_cast<size_t>(ps->cv_lines) * (ps->cv_nwg + 1u) * 512u, st));
-  return AZMI_OK;
-}
-// Measures how many LINES run beside the tree workgroups (pipe_calibrate's census, for the conveyor): every workgroup of the three
-// kernels holds its place; a conv workgroup that the chip has no CU for starts late and is counted, and the line count gives way.
-int cv_calibrate(azmi_pm* pm, PipeState* ps, hipStream_t st, const azmi_net_c4_view& view) {
-  if (ps->cv_calibrated || getenv("AZMI_PIPE_NO_CALIBRATE")) { ps->cv_calibrated = true; return AZMI_OK; }
-  PipeArrays pa = ps->pa;
-  pa.census_hold = 100000u;
-  for (int attempt = 0; attempt < 24; ++attempt) {
-    AZMI_HIP_TRY(hipMemsetAsync(pa.ep, 0, sizeof(PipeEpoch), st));
-    { const int rc = cv_zero_headers(ps, st); if (rc != AZMI_OK) return rc; }
-    AZMI_HIP_TRY(hipEventRecord(ps->ev_go, st));
-    AZMI_HIP_TRY(hipStreamWaitEvent(ps->net_stream, ps->ev_go, 0));
-    AZMI_HIP_TRY(hipStreamWaitEvent(ps->svc_stream, ps->ev_go, 0));
-    { const int rc = cv_launch(ps, view, pa, pa.census_hold); if (rc != AZMI_OK) return rc; }
-    k_cv_wait_started<<<1, 1, 0, st>>>(pa.ep, ps->cv_lines * ps->cv_nwg);
-    pipe_launch_tree(pm, ps, pa, st, false);
-    AZMI_HIP_TRY(hipGetLastError());
-    AZMI_HIP_TRY(hipEventRecord(ps->ev_net, ps->net_stream));
-    AZMI_HIP_TRY(hipEventRecord(ps->ev_svc, ps->svc_stream));
-    AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_net, 0));
-    AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_svc, 0));
-    PipeEpoch he;
-    AZMI_HIP_TRY(hipMemcpyAsync(&he, pa.ep, sizeof(he), hipMemcpyDeviceToHost, st));
-    AZMI_HIP_TRY(hipStreamSynchronize(st));
-    ps->calib_rounds = static_cast<uint32_t>(attempt) + 1u;
-    const uint32_t late = he.tree_late_n + he.net_late_n + he.svc_late_n;
-    if (late == 0u && he.tree_arrived == ps->tree_wgs && he.net_arrived == ps->cv_lines * ps->cv_nwg && he.svc_arrived == ps->cv_lines) {
-      ps->cv_calibrated = true;
-      return AZMI_OK;
-    }
-    if (ps->cv_lines <= 1u) break;
-    const uint32_t give = std::max<uint32_t>(1u, (late + ps->cv_nwg - 1u) / ps->cv_nwg);
-    ps->cv_lines = ps->cv_lines > give ? ps->cv_lines - give : 1u;
-  }
-  return azmi_host_fail(AZMI_ERR_STATE, "azmi_run_pipeline: the chip does not hold %u tree workgroups beside one conveyor line (another tenant on the GPU? no third "
-                        "hardware queue?); AZMI_PIPE_NET=tiles runs the tile kernel", ps->tree_wgs);
-}
-#else      // the default library: the conveyor is not compiled in (scripts/experiments/conveyor_c4.h)
-static int cv_absent() { return azmi_host_fail(AZMI_ERR_STATE, "this build has no conveyor (an experiment since round 6: build with -DAZMI_WITH_CONVEYOR); the tile kernel is the net side"); }
-bool cv_eligible(const azmi_pm*, const PipePlan&) { return false; }
-uint32_t cv_default_lines(uint32_t, uint32_t, uint32_t) { return 0u; }
-int cv_setup(azmi_pm*, PipeState*, const azmi_net_c4_view&) { return cv_absent(); }
-int cv_launch(PipeState*, const azmi_net_c4_view&, const PipeArrays&, uint32_t) { return cv_absent(); }
-int cv_zero_headers(PipeState*, hipStream_t) { return cv_absent(); }
-int cv_calibrate(azmi_pm*, PipeState*, hipStream_t, const azmi_net_c4_view&) { return cv_absent(); }
-#endif     // AZMI_WITH_CONVEYOR
 
 // Measures how many net workgroups run BESIDE the tree workgroups: both persistent kernels are launched as they are in an epoch, with
 // PipeArrays::census_hold set - every workgroup that gets a place holds it until 1 ms after the first one started (far longer than the
@@ -1855,6 +1634,12 @@ PipePlan pipe_plan(const azmi_pm* pm, azmi_net* const* nets, uint32_t num_nets) 
   pl.kind = getenv("AZMI_PIPE_GENERIC") == nullptr ? 1 : 2;
   return pl;
 }
+// The conveyor (round 5's weight-stationary net side: bit-identical to the tile kernel, slower) was an experiment build in round 6 and
+// is gone: what asks for it is refused by name, never served by the tile kernel in silence.
+int pipe_no_conveyor() {
+  return azmi_host_fail(AZMI_ERR_STATE, "this library has no conveyor: the weight-stationary net side of round 5 measured slower than the tile kernel and was "
+                        "removed (DESIGN.md 4.5b; git history, last present at commit 18a52a1); the tile kernel is the net side");
+}
 }  // namespace
 extern "C" int azmi_pipeline_supported(azmi_pm* pm, azmi_net* net) {
   if (!pm) return 0;
@@ -1873,17 +1658,14 @@ namespace {
 //   m = 0.29 (32 M entries, first half):                                  80 /  96 / 112 / 128 -> 70 / 78 / 80 / 77
 //   m = 0.55 (200 k entries, first half):                                 48 /  64 /  80 / 128 -> 43 / 51 / 52 / 39
 // i.e. the best count falls about linearly with m: tree workgroups = places x (0.342 - 0.367 m), between a third and 1.5 x the
-// default (AZMI_PIPE_BALANCE_A / _B set other coefficients).  m is taken over the PREVIOUS call; the count moves 8 workgroups per call,
+// default (ca = 0.342, cb = 0.367; AZMI_PIPE_BALANCE_A / _B set other coefficients).  m is taken over the PREVIOUS call; the count moves 8 workgroups per call,
 // between epochs only (a slot's home is slot % tree workgroups for one epoch at a time; between epochs a slot is whole in HBM).  The
 // games do not depend on it (a slot's game is a function of its seed alone).
-void pipe_balance(PipeState* ps, const PipeCtl& hc) {
+void pipe_balance(PipeState* ps, const PipeCtl& hc, double ca, double cb) {
   if (!ps->balance || !ps->calibrated || ps->places == 0u) return;
   const unsigned long long ds = hc.sims_total - ps->bal_sims, db = hc.tile_boards - ps->bal_boards;
   ps->bal_sims = hc.sims_total; ps->bal_boards = hc.tile_boards;
   if (ds < 4096ull || db == 0ull) return;
-  double ca = 0.342, cb = 0.367;
-  if (const char* e = getenv("AZMI_PIPE_BALANCE_A")) ca = atof(e);
-  if (const char* e = getenv("AZMI_PIPE_BALANCE_B")) cb = atof(e);
   const double m = static_cast<double>(db) / static_cast<double>(ds);
   const double share = std::max(0.02, ca - cb * m);
   uint32_t want = static_cast<uint32_t>(static_cast<double>(ps->places) * share + 0.5);
@@ -1917,24 +1699,57 @@ extern "C" int azmi_run_pipeline_groups(azmi_pm* pm, azmi_net* const* nets, uint
                                         uint64_t* out_stats) {
   return run_pipeline_impl(pm, nets, num_nets, epochs, sims_per_epoch, stream, out_stats);
 }
-static int run_pipeline_impl(azmi_pm* pm, azmi_net* const* nets, uint32_t num_nets, uint32_t epochs, uint64_t sims_per_epoch, void* stream, uint64_t* out_stats) {
-  if (!pm) return azmi_host_fail(AZMI_ERR_INVALID, "null argument");
-  std::lock_guard<std::recursive_mutex> lock_(pm->mu);
-  std::lock_guard<std::mutex> turn_(pipeline_turn_of(pm->device));
-  const PipePlan plan = pipe_plan(pm, nets, num_nets);
-  if (plan.kind == 0)
-    return azmi_host_fail(AZMI_ERR_STATE, "azmi_run_pipeline: the pipeline drives the Connect4 engine (no PLAYOUT seats, at most two model groups, at most %u "
-                          "concurrent games) with a Connect4-family matrix-core net of one precision tier behind every model group that evaluates with a net "
-                          "(or no net at all when every seat uses EvalType::RANDOM) - azmi_pipeline_supported; use azmi_run_rounds for everything else", kPipeRing / 2u);
+namespace {
+// The environment knobs of ONE call, parsed once at its top (per call, not per process: tests and scripts set them between calls).  The
+// knobs that shape the pipeline state when it is created, sized or measured are read there (pipe_create, pipe_size_net, pipe_calibrate).
+struct PipeKnobs {
+  bool net_conveyor = false;                 // AZMI_PIPE_NET=conveyor: refused (pipe_no_conveyor)
+  bool no_l0 = false;                        // AZMI_PIPE_NO_L0: no answer table
+  int l0_log2 = -1;                          // AZMI_PIPE_L0_LOG2: log2 of the answer table's entries (-1: from the S3-FIFO's size)
+  uint32_t l0_wb = 0;                        // AZMI_PIPE_L0_WB
+  uint32_t idle_num = 0;                     // AZMI_PIPE_IDLE_FRAC (0.125), in 1024ths: an epoch ends when this share of the slots waits for the move step
+  unsigned long long cap_ticks = 0;          // AZMI_PIPE_CAP_MS (250), in 100 MHz ticks: the wall-clock cap of an epoch, a stall detector
+  unsigned long long soft_ticks = 0;         // AZMI_PIPE_SOFT_MS (a quarter of the cap): an epoch that runs long simply ends here
+  uint32_t test_drop = 0;                    // AZMI_PIPE_TEST_DROP (the error-path test)
+  // AZMI_PIPE_TILE, the net kernel's tile selection: 0 = by what a window brings within its patience (<= 3 requests: the 3-board tile), 1 = 6-board tiles only,
+  // 2 = 3-board tiles only.  At 4096 slots 0 and 2 measure the same (the net side has places to spare); at 16384 slots the
+  // 3-board tile's capacity (19.5 M evaluations/s on 416 workgroups) is the limit, so 0 it is.
+  int tile = 0;
+  bool net_all = false;                      // AZMI_PIPE_NET_ALL: launch every net workgroup the chip holds
+  bool prof = false, hist = false;           // AZMI_PIPE_PROF, AZMI_PIPE_HIST
+  bool debug = false;                        // AZMI_PIPE_DEBUG: read the error word back after every epoch
+  double balance_a = 0.342, balance_b = 0.367;      // AZMI_PIPE_BALANCE_A / _B (pipe_balance)
+};
+PipeKnobs pipe_read_knobs() {
+  PipeKnobs k;
+  if (const char* e = getenv("AZMI_PIPE_NET")) k.net_conveyor = strcmp(e, "conveyor") == 0;
+  k.no_l0 = getenv("AZMI_PIPE_NO_L0") != nullptr;
+  if (const char* e = getenv("AZMI_PIPE_L0_LOG2")) k.l0_log2 = std::min(26, std::max(4, atoi(e)));
+  if (const char* e = getenv("AZMI_PIPE_L0_WB")) k.l0_wb = static_cast<uint32_t>(atoi(e));
+  double idle_frac = 0.125;
+  if (const char* e = getenv("AZMI_PIPE_IDLE_FRAC")) idle_frac = atof(e);
+  k.idle_num = std::max<uint32_t>(1u, std::min<uint32_t>(1024u, static_cast<uint32_t>(idle_frac * 1024.0)));
+  double cap_ms = 250.0;
+  if (const char* e = getenv("AZMI_PIPE_CAP_MS")) cap_ms = atof(e);
+  k.cap_ticks = static_cast<unsigned long long>(cap_ms * 1e5);
+  // (the error-path test asks for a soft limit beyond the cap)
+  k.soft_ticks = getenv("AZMI_PIPE_SOFT_MS") ? static_cast<unsigned long long>(atof(getenv("AZMI_PIPE_SOFT_MS")) * 1e5) : k.cap_ticks / 4u;
+  if (const char* e = getenv("AZMI_PIPE_TEST_DROP")) k.test_drop = static_cast<uint32_t>(strtoul(e, nullptr, 0));
+  if (const char* e = getenv("AZMI_PIPE_TILE")) k.tile = atoi(e);
+  k.net_all = getenv("AZMI_PIPE_NET_ALL") != nullptr;
+  k.prof = getenv("AZMI_PIPE_PROF") != nullptr;
+  k.hist = getenv("AZMI_PIPE_HIST") != nullptr;
+  k.debug = getenv("AZMI_PIPE_DEBUG") != nullptr;
+  if (const char* e = getenv("AZMI_PIPE_BALANCE_A")) k.balance_a = atof(e);
+  if (const char* e = getenv("AZMI_PIPE_BALANCE_B")) k.balance_b = atof(e);
+  return k;
+}
+
+// Everything of a call that comes before its first epoch: the pipeline state on first use, the net side sized and measured for this
+// call's net, the insert log, the locks and the answer table, the epoch's limits, and the restarts the first epoch starts from.
+int pipe_prepare_call(azmi_pm* pm, const PipePlan& plan, const PipeKnobs& k, uint32_t epochs, uint64_t sims_per_epoch, hipStream_t st) {
   const azmi_net_c4_view& view = plan.view[0];
   const bool tree_only = plan.tree_only;
-  if (sims_per_epoch == 0) return azmi_host_fail(AZMI_ERR_INVALID, "azmi_run_pipeline: sims_per_epoch must be > 0");
-  if (pm->stopped.load(std::memory_order_relaxed)) {     // PlayManager::stop(): the workers leave their loop (play_manager.cc:272)
-    if (out_stats) for (int i = 0; i < 16; ++i) out_stats[i] = 0;
-    return AZMI_OK;
-  }
-  AZMI_HIP_TRY(hipSetDevice(pm->device));
-  hipStream_t st = pm->pick(stream);
   if (!pm->pipe) {
     const int rc = pipe_create(pm, view.lds_bytes > azmi_net_dev::c4::TileBig::LDS_BYTES ? view.lds_bytes : azmi_net_dev::c4::TileBig::LDS_BYTES);
     if (rc != AZMI_OK) return rc;
@@ -1952,36 +1767,15 @@ static int run_pipeline_impl(azmi_pm* pm, azmi_net* const* nets, uint32_t num_ne
   }
   if (!tree_only) { const int rc = pipe_pair_streams(ps, st); if (rc != AZMI_OK) return rc; }
   if (!tree_only) { const int rc = pipe_size_net(pm, ps, view); if (rc != AZMI_OK) return rc; }
-  // the net side: the conveyor where it can run (conveyor_c4.h), else the tile kernel
-  ps->cv_on = cv_eligible(pm, plan);
-  if (const char* e = getenv("AZMI_PIPE_NET")) if (strcmp(e, "conveyor") == 0 && !ps->cv_on && !tree_only)
-#ifdef AZMI_WITH_CONVEYOR
-    return azmi_host_fail(AZMI_ERR_STATE, "AZMI_PIPE_NET=conveyor: the conveyor runs the bf16 tier behind one model group with an even number of residual blocks");
-#else
-    return cv_absent();
-#endif
-  if (ps->cv_on) {
-    if (ps->balance) { ps->tree_wgs = ps->tree_wgs_default; pa.n_tree_wgs = ps->tree_wgs; }      // (the 512-place balance rule is the tile kernel's)
-    pa.cap_ticks = static_cast<unsigned long long>((getenv("AZMI_PIPE_CAP_MS") ? atof(getenv("AZMI_PIPE_CAP_MS")) : 250.0) * 1e5);
-    int rc = cv_setup(pm, ps, view);
-    if (rc == AZMI_OK) rc = pipe_pair_svc(ps, st);
-    if (rc == AZMI_OK) rc = cv_calibrate(pm, ps, st, view);
-    if (rc != AZMI_OK) {
-      if (getenv("AZMI_PIPE_NET")) return rc;
-      fprintf(stderr, "azmi_run_pipeline: the conveyor does not run here (%s); the tile kernel takes the net side\n", azmi_last_error());
-      ps->cv_on = false;
-    }
-  }
-  if (!tree_only && !ps->cv_on) { const int rc = pipe_calibrate(pm, ps, st, view); if (rc != AZMI_OK) return rc; }
+  if (!tree_only) { const int rc = pipe_calibrate(pm, ps, st, view); if (rc != AZMI_OK) return rc; }
   // the insert log holds an epoch's answers: at most one per simulation, in practice a third of them
   // (the quota is checked between passes: an epoch overshoots it by what the passes under way still finish)
   const uint64_t want_log = pm->ep.cache_on ? std::min<uint64_t>(std::min<uint64_t>(sims_per_epoch, 1024ull * pm->ep.S) + 2ull * pm->ep.S + static_cast<uint64_t>(ps->tree_wgs) * 32u * (pa.max_inline + 1u), 1ull << 24) : 0ull;
   if (want_log > pa.ins_cap) {
-    PipeState* p = ps;
-    int rc = pipe_alloc(p, pa.ins_key, want_log);
-    if (rc == AZMI_OK) rc = pipe_alloc(p, pa.ins_pi, want_log * Connect4::M);
-    if (rc == AZMI_OK) rc = pipe_alloc(p, pa.ins_v, want_log * (Connect4::P + 1));
-    if (rc == AZMI_OK && pa.n_groups > 1u) rc = pipe_alloc(p, pa.ins_grp, want_log);
+    int rc = pipe_alloc(ps, pa.ins_key, want_log);
+    if (rc == AZMI_OK) rc = pipe_alloc(ps, pa.ins_pi, want_log * Connect4::M);
+    if (rc == AZMI_OK) rc = pipe_alloc(ps, pa.ins_v, want_log * (Connect4::P + 1));
+    if (rc == AZMI_OK && pa.n_groups > 1u) rc = pipe_alloc(ps, pa.ins_grp, want_log);
     if (rc != AZMI_OK) return rc;
     pa.ins_cap = static_cast<uint32_t>(want_log);
   }
@@ -1993,7 +1787,7 @@ static int run_pipeline_impl(azmi_pm* pm, azmi_net* const* nets, uint32_t num_ne
     const int rc = pipe_alloc(ps, pa.locks, total);
     if (rc != AZMI_OK) return rc;
   }
-  if (pm->ep.cache_on && !pa.l0 && !tree_only && plan.kind == 1 && getenv("AZMI_PIPE_NO_L0") == nullptr) {
+  if (pm->ep.cache_on && !pa.l0 && !tree_only && plan.kind == 1 && !k.no_l0) {
     // the answer table: a power of two of 128-byte entries, an eighth of the S3-FIFO's entries, between 4 Ki and 4 Mi (512 MB: an
     // epoch of the headline brings ~200 k answers).  Measured and dropped: a table of half the S3-FIFO's entries (64 Mi = 8 GB at the
     // headline's cache) with shard hits copied into it - a table hit costs the probe one round trip instead of two, but 8 GB more of
@@ -2001,11 +1795,11 @@ static int run_pipeline_impl(azmi_pm* pm, azmi_net* const* nets, uint32_t num_ne
     uint64_t want = static_cast<uint64_t>(pm->ar.cache.shards) * kWaveCap / 8u;
     uint32_t sh = 12;
     while (sh < 22u && (1ull << sh) < want) ++sh;
-    if (const char* e = getenv("AZMI_PIPE_L0_LOG2")) sh = static_cast<uint32_t>(std::min(26, std::max(4, atoi(e))));
+    if (k.l0_log2 >= 0) sh = static_cast<uint32_t>(k.l0_log2);
     const int rc = pipe_alloc(ps, pa.l0, (static_cast<size_t>(1) << sh) * kResStride);
     if (rc != AZMI_OK) return rc;
     pa.l0_mask = (1u << sh) - 1u;
-    pa.l0_wb = getenv("AZMI_PIPE_L0_WB") ? static_cast<uint32_t>(atoi(getenv("AZMI_PIPE_L0_WB"))) : 0u;
+    pa.l0_wb = k.l0_wb;
   }
   if (pa.l0) {
     // the table's entries are answers of the nets the LAST call ran with: another net behind a group (or the groups' nets swapped)
@@ -2022,97 +1816,180 @@ static int run_pipeline_impl(azmi_pm* pm, azmi_net* const* nets, uint32_t num_ne
   // so the quota is held to 1024 simulations per slot (~50 ms at the slowest per-slot rate measured)
   pa.quota = std::min<uint64_t>(sims_per_epoch, 1024ull * pm->ep.S);
   pa.net_needed = std::max<uint32_t>(8u, (pm->ep.S + 2u) / 3u + 8u);
-  // an epoch also ends when this share of the slots waits for the move step (all of them: the start of a run)
-  double idle_frac = 0.125;
-  if (const char* e = getenv("AZMI_PIPE_IDLE_FRAC")) idle_frac = atof(e);
-  pa.idle_num = std::max<uint32_t>(1u, std::min<uint32_t>(1024u, static_cast<uint32_t>(idle_frac * 1024.0)));
-  double cap_ms = 250.0;
-  if (const char* e = getenv("AZMI_PIPE_CAP_MS")) cap_ms = atof(e);
-  pa.cap_ticks = static_cast<unsigned long long>(cap_ms * 1e5);
-  // (an epoch that runs long simply ends at a quarter of the cap; AZMI_PIPE_SOFT_MS sets another limit - the error-path test asks for
-  // one beyond the cap)
-  pa.test_drop = getenv("AZMI_PIPE_TEST_DROP") ? static_cast<uint32_t>(strtoul(getenv("AZMI_PIPE_TEST_DROP"), nullptr, 0)) : 0u;
-  pa.soft_ticks = getenv("AZMI_PIPE_SOFT_MS") ? static_cast<unsigned long long>(atof(getenv("AZMI_PIPE_SOFT_MS")) * 1e5) : pa.cap_ticks / 4u;
-  // the lock-step kernels leave the key of a round's leaf in cache_keys for the next round's insert: none of that here
-  if (pm->ep.cache_on) AZMI_HIP_TRY(hipMemsetAsync(pm->ar.cache_keys, 0, sizeof(uint64_t) * pm->ep.S, st));
-  int rc = azmi_host_launch_assign(pm, st, 1u);
-  if (rc != AZMI_OK) return rc;
-  const uint32_t settle_blocks = (pm->ep.S + 255u) / 256u;
-  // tile selection: 0 = by what a window brings within its patience (<= 3 requests: the 3-board tile), 1 = 6-board tiles only,
-  // 2 = 3-board tiles only.  At 4096 slots 0 and 2 measure the same (the net side has places to spare); at 16384 slots the
-  // 3-board tile's capacity (19.5 M evaluations/s on 416 workgroups) is the limit, so 0 it is.
-  const int net_mode = getenv("AZMI_PIPE_TILE") ? atoi(getenv("AZMI_PIPE_TILE")) : 0;
+  pa.idle_num = k.idle_num;
+  pa.cap_ticks = k.cap_ticks;
+  pa.test_drop = k.test_drop;
+  pa.soft_ticks = k.soft_ticks;
+  // A slot has at most one request out and a tile takes three: more than S / 3 net workgroups (+ 8 of slack) can never all have work.
+  // A small engine therefore does not launch the ~500 the chip holds: idle persistent workgroups are not free - they poll - and
+  // the rare seconds-long stalls of the tree side (DESIGN 2.1, round 5) were only ever seen with hundreds of them idle.
+  ps->net_launch = std::min<uint32_t>(ps->net_wgs, std::max<uint32_t>(8u, (pm->ep.S + 2u) / 3u + 8u));
+  if (k.net_all) ps->net_launch = ps->net_wgs;
   while (ps->tev.size() < 4ull * epochs) {
     hipEvent_t ev;
     AZMI_HIP_TRY(hipEventCreate(&ev));
     ps->tev.push_back(ev);
   }
-  // A slot has at most one request out and a tile takes three: more than S / 3 net workgroups (+ 8 of slack) can never all have work.
-  // A small engine therefore does not launch the ~500 the chip holds: idle persistent workgroups are not free - they poll - and
-  // the rare seconds-long stalls of the tree side (DESIGN 2.1, round 5) were only ever seen with hundreds of them idle.
-  ps->net_launch = std::min<uint32_t>(ps->net_wgs, std::max<uint32_t>(8u, (pm->ep.S + 2u) / 3u + 8u));
-  if (getenv("AZMI_PIPE_NET_ALL")) ps->net_launch = ps->net_wgs;
-  const bool prof = getenv("AZMI_PIPE_PROF") != nullptr;
+  // the lock-step kernels leave the key of a round's leaf in cache_keys for the next round's insert: none of that here
+  if (pm->ep.cache_on) AZMI_HIP_TRY(hipMemsetAsync(pm->ar.cache_keys, 0, sizeof(uint64_t) * pm->ep.S, st));
+  return azmi_host_launch_assign(pm, st, 1u);
+}
+
+// ONE epoch's launches and event edges, in the order each stream sees them.  `st` is the caller's stream (the tree side, and everything
+// between epochs); net_stream runs the net kernel beside it, tree_stream (CU split only) the tree kernel.  The order is load-bearing
+// (DESIGN 2.1): change nothing here without measuring.
+int pipe_enqueue_epoch(azmi_pm* pm, const PipePlan& plan, const PipeKnobs& k, uint32_t e, hipStream_t st) {
+  PipeState* ps = pm->pipe;
+  const PipeArrays& pa = ps->pa;
+  const bool tree_only = plan.tree_only;
+  const uint32_t settle_blocks = (pm->ep.S + 255u) / 256u;
+  AZMI_HIP_TRY(hipMemsetAsync(pa.ep, 0, sizeof(PipeEpoch), st));
+  k_pipe_seed<<<settle_blocks, 256, 0, st>>>(pm->ep, pm->ar, pa);
+  AZMI_HIP_TRY(hipGetLastError());
+  if (!tree_only) {
+    AZMI_HIP_TRY(hipEventRecord(ps->ev_go, st));
+    AZMI_HIP_TRY(hipStreamWaitEvent(ps->net_stream, ps->ev_go, 0));
+  }
+  // the tree kernel goes first: its workgroups take their places per shader engine, the net kernel is sized for what is left
+  // (CU split: on its own stream, masked to the tree side's CUs; the caller's stream waits for it)
+  hipStream_t ts = ps->tree_stream && !tree_only ? ps->tree_stream : st;
+  if (ts != st) AZMI_HIP_TRY(hipStreamWaitEvent(ts, ps->ev_go, 0));
+  AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 2], ts));
+  pipe_launch_tree(pm, ps, pa, ts, k.prof);
+  AZMI_HIP_TRY(hipGetLastError());
+  AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 3], ts));
+  if (ts != st) { AZMI_HIP_TRY(hipEventRecord(ps->ev_tree, ts)); AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_tree, 0)); }
+  if (pm->ep.cache_on) {      // behind the tree kernel, beside the net side's last tiles
+    k_pipe_cache_insert<<<2048, 256, 0, st>>>(pm->ar, pa, 0u);
+    AZMI_HIP_TRY(hipGetLastError());
+  }
+  if (!tree_only) {
+    AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 0], ps->net_stream));
+    const int rc = pipe_launch_net(ps, plan.view[0], k.tile, ps->net_launch, ps->net_stream, pa);
+    if (rc != AZMI_OK) return rc;
+    AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 1], ps->net_stream));
+    AZMI_HIP_TRY(hipEventRecord(ps->ev_net, ps->net_stream));
+    AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_net, 0));
+  }
+  k_pipe_settle<<<settle_blocks, 256, 0, st>>>(pm->ep, pm->ar, pa);
+  AZMI_HIP_TRY(hipGetLastError());
+  int rc = azmi_host_launch_move_step(pm, st);
+  if (rc != AZMI_OK) return rc;
+  rc = azmi_host_launch_assign(pm, st, 1u);
+  if (rc != AZMI_OK) return rc;
+  if (pm->ep.cache_on) {
+    k_pipe_cache_insert<<<256, 256, 0, st>>>(pm->ar, pa, 1u);
+    AZMI_HIP_TRY(hipGetLastError());
+  }
+  return AZMI_OK;
+}
+
+// After the last epoch: the control blocks read back (the call is synchronous - a pipeline error must not go unseen), the balance
+// rule for the next call, out_stats, and the error report - which leaves the engine whole.
+int pipe_finish_call(azmi_pm* pm, const PipePlan& plan, const PipeKnobs& k, uint32_t epochs, uint64_t host_enqueue_us, hipStream_t st, uint64_t* out_stats) {
+  PipeState* ps = pm->pipe;
+  PipeArrays& pa = ps->pa;
+  const bool tree_only = plan.tree_only;
+  PipeCtl hc;
+  PipeEpoch he;
+  AZMI_HIP_TRY(hipMemcpyAsync(&hc, pa.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
+  AZMI_HIP_TRY(hipMemcpyAsync(&he, pa.ep, sizeof(he), hipMemcpyDeviceToHost, st));
+  AZMI_HIP_TRY(hipStreamSynchronize(st));
+  if (hc.lost_total != ps->lost_seen) {
+    fprintf(stderr, "azmi_run_pipeline: %u request(s) were given up by the net side and sent again (a net workgroup fell more than half a ring behind)\n", hc.lost_total - ps->lost_seen);
+    ps->lost_seen = hc.lost_total;
+  }
+  if (!tree_only && !hc.err) pipe_balance(ps, hc, k.balance_a, k.balance_b);       // (takes effect with the next call's first epoch)
+  if (out_stats) {
+    out_stats[0] = hc.tiles; out_stats[1] = hc.tile_boards; out_stats[2] = he.sims; out_stats[3] = he.tree_arrived;
+    out_stats[4] = he.net_arrived; out_stats[5] = he.ins_count; out_stats[6] = ps->net_launch; out_stats[7] = ps->tree_wgs;
+    out_stats[8] = he.tree_late / 100u; out_stats[9] = he.net_late / 100u;
+    double net_us = 0.0, tree_us = 0.0;
+    for (uint32_t e = 0; e < epochs; ++e) {
+      float ms = 0.0f;
+      if (!tree_only && hipEventElapsedTime(&ms, ps->tev[4 * e + 0], ps->tev[4 * e + 1]) == hipSuccess) net_us += 1e3 * ms;
+      if (hipEventElapsedTime(&ms, ps->tev[4 * e + 2], ps->tev[4 * e + 3]) == hipSuccess) tree_us += 1e3 * ms;
+    }
+    out_stats[10] = static_cast<uint64_t>(net_us); out_stats[11] = static_cast<uint64_t>(tree_us); out_stats[12] = epochs; out_stats[13] = host_enqueue_us;
+    out_stats[14] = static_cast<uint64_t>(ps->calib_rounds & 0xFFu) | (static_cast<uint64_t>(std::min<unsigned long long>(hc.freezes, 0xFFFFFFull)) << 8) | (static_cast<uint64_t>(hc.lost_total) << 32);
+    out_stats[15] = hc.l0_hits;
+    if (k.prof) {
+      fprintf(stderr, "pipe prof:");
+      for (int i = 0; i < 16; ++i) fprintf(stderr, " %llu", hc.prof[i]);
+      fprintf(stderr, "\n");
+    }
+    if (k.prof || k.hist) {
+      fprintf(stderr, "pipe tile hist (tiles of 1 .. 6 boards since creation):");
+      for (int i = 0; i < 6; ++i) fprintf(stderr, " %llu", hc.tile_hist[i]);
+      fprintf(stderr, "\n");
+    }
+  }
+  if (!hc.err) return AZMI_OK;
+  fprintf(stderr, "pipeline dbg:");
+  for (int i = 0; i < 18; ++i) fprintf(stderr, " %u", hc.dbg[i]);
+  fprintf(stderr, "\n");
+  if (plan.kind == 2) {      // the generic tree kernel: where each of its wavefronts was last (phase, 10 us units since its start)
+    std::vector<PipeWg> hw(ps->tree_wgs);
+    if (hipMemcpy(hw.data(), pa.wg, hw.size() * sizeof(PipeWg), hipMemcpyDeviceToHost) == hipSuccess) {
+      fprintf(stderr, "pipeline generic tree kernel, workgroup: rhead rtail | phase@10us of its four wavefronts | their entry times, us after wavefront 0's:");
+      for (uint32_t w = 0; w < ps->tree_wgs; ++w)
+        fprintf(stderr, "  [%u: %u %u | %u@%u %u@%u %u@%u %u@%u | %d %d %d]", w, hw[w].rhead, hw[w].rtail, hw[w].pad[2] & 255u, hw[w].pad[2] >> 8, hw[w].pad[3] & 255u, hw[w].pad[3] >> 8,
+                hw[w].pad[4] & 255u, hw[w].pad[4] >> 8, hw[w].pad[5] & 255u, hw[w].pad[5] >> 8,
+                static_cast<int32_t>(hw[w].pad[7] - hw[w].pad[6]) / 100, static_cast<int32_t>(hw[w].pad[8] - hw[w].pad[6]) / 100, static_cast<int32_t>(hw[w].pad[9] - hw[w].pad[6]) / 100);
+      fprintf(stderr, "\n  wavefront 0's longest interval between two looks: wall clock x10us | SQ clock >> 10 | 0 poll loop, 1 a pass | after polls | polls in all:");
+      for (uint32_t w = 0; w < ps->tree_wgs; ++w) fprintf(stderr, "  [%u: %u | %u | %u | %u | %u]", w, hw[w].pad[10], hw[w].pad[11], hw[w].pad[12], hw[w].pad[13], hw[w].pad[14]);
+      fprintf(stderr, "\n  longest phases of its passes (SQ clock >> 10): publication word | granules | log ticket + drain | steps + requests | tokens:");
+      for (uint32_t w = 0; w < ps->tree_wgs; ++w) fprintf(stderr, "  [%u: %u | %u | %u | %u | %u]", w, hw[w].pad[18], hw[w].pad[19], hw[w].pad[20], hw[w].pad[21], hw[w].pad[22]);
+      fprintf(stderr, "\n  its longest segments (SQ clock >> 10): token load | control words | between looks:");
+      for (uint32_t w = 0; w < ps->tree_wgs; ++w) fprintf(stderr, "  [%u: %u | %u | %u]", w, hw[w].pad[15], hw[w].pad[16], hw[w].pad[17]);
+      fprintf(stderr, "\n");
+    }
+  }
+  // reported once: k_pipe_settle has put every slot whose request went unanswered back into the move step's kSlotQueued form, so
+  // the engine is whole - the next call (either driver) carries on from here
+  AZMI_HIP_TRY(hipMemsetAsync(&pa.ctl->err, 0, sizeof(uint32_t), st));
+  AZMI_HIP_TRY(hipMemsetAsync(pa.ctl->dbg, 0, sizeof(pa.ctl->dbg), st));
+  AZMI_HIP_TRY(hipStreamSynchronize(st));
+  return azmi_host_fail(AZMI_ERR_STATE, "pipeline error mask 0x%x (1 a spin hit the epoch's time cap, 2 a ring entry never arrived, 4 a result tag "
+                        "did not match, 8 insert log full, 16 cache lock, 32 slots, 64 the net side hit the time cap); census: %u of %u tree and %u of %u net workgroups started; "
+                        "last epoch: head %u tail %u sims %llu ended %u dead %u stop %u tree_done %u tiles %llu boards %llu; latest tree / net workgroup start %u / %u us; "
+                        "first time-out saw: slot %u seq %u / %u; net side: stop %u tree done %u of %u tail %u window at %u after %u0 us; "
+                        "wavefronts that stood still > 2 ms (not one instruction between two looks at the clock) so far: %llu, the longest for %.1f ms",
+                        hc.err, he.tree_arrived, ps->tree_wgs, he.net_arrived, ps->net_launch, hc.head, hc.tail, he.sims, he.ended, he.dead, he.stop,
+                        he.tree_done, hc.tiles, hc.tile_boards, he.tree_late / 100u, he.net_late / 100u,
+                        hc.dbg[1], hc.dbg[2], hc.dbg[3], hc.dbg[8], hc.dbg[9], hc.dbg[10], hc.dbg[11], hc.dbg[12], hc.dbg[13],
+                        static_cast<unsigned long long>(hc.freezes), static_cast<double>(hc.freeze_max) * 1e-5);
+}
+}  // namespace
+
+static int run_pipeline_impl(azmi_pm* pm, azmi_net* const* nets, uint32_t num_nets, uint32_t epochs, uint64_t sims_per_epoch, void* stream, uint64_t* out_stats) {
+  if (!pm) return azmi_host_fail(AZMI_ERR_INVALID, "null argument");
+  const PipeKnobs k = pipe_read_knobs();
+  std::lock_guard<std::recursive_mutex> lock_(pm->mu);
+  std::lock_guard<std::mutex> turn_(pipeline_turn_of(pm->device));
+  const PipePlan plan = pipe_plan(pm, nets, num_nets);
+  if (plan.kind == 0)
+    return azmi_host_fail(AZMI_ERR_STATE, "azmi_run_pipeline: the pipeline drives the Connect4 engine (no PLAYOUT seats, at most two model groups, at most %u "
+                          "concurrent games) with a Connect4-family matrix-core net of one precision tier behind every model group that evaluates with a net "
+                          "(or no net at all when every seat uses EvalType::RANDOM) - azmi_pipeline_supported; use azmi_run_rounds for everything else", kPipeRing / 2u);
+  if (sims_per_epoch == 0) return azmi_host_fail(AZMI_ERR_INVALID, "azmi_run_pipeline: sims_per_epoch must be > 0");
+  if (pm->stopped.load(std::memory_order_relaxed)) {     // PlayManager::stop(): the workers leave their loop (play_manager.cc:272)
+    if (out_stats) for (int i = 0; i < 16; ++i) out_stats[i] = 0;
+    return AZMI_OK;
+  }
+  if (k.net_conveyor && !plan.tree_only) return pipe_no_conveyor();      // (before any GPU work: the engine is as it was)
+  AZMI_HIP_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->pick(stream);
+  int rc = pipe_prepare_call(pm, plan, k, epochs, sims_per_epoch, st);
+  if (rc != AZMI_OK) return rc;
   const auto host_t0 = std::chrono::steady_clock::now();       // what the host spends enqueueing the epochs (it runs ahead of the GPU)
   for (uint32_t e = 0; e < epochs; ++e) {
-    AZMI_HIP_TRY(hipMemsetAsync(pa.ep, 0, sizeof(PipeEpoch), st));
-    if (ps->cv_on) { rc = cv_zero_headers(ps, st); if (rc != AZMI_OK) return rc; }
-    k_pipe_seed<<<settle_blocks, 256, 0, st>>>(pm->ep, pm->ar, pa);
-    AZMI_HIP_TRY(hipGetLastError());
-    if (!tree_only) {
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_go, st));
-      AZMI_HIP_TRY(hipStreamWaitEvent(ps->net_stream, ps->ev_go, 0));
-      if (ps->cv_on) AZMI_HIP_TRY(hipStreamWaitEvent(ps->svc_stream, ps->ev_go, 0));
-    }
-    if (ps->cv_on) {      // the conv workgroups take their CUs first (k_cv_wait_started), the tree workgroups pack into the rest
-      AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 0], ps->net_stream));
-      rc = cv_launch(ps, view, pa, 0u);
-      if (rc != AZMI_OK) return rc;
-      AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 1], ps->net_stream));
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_net, ps->net_stream));
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_svc, ps->svc_stream));
-      k_cv_wait_started<<<1, 1, 0, st>>>(pa.ep, ps->cv_lines * ps->cv_nwg);
-      AZMI_HIP_TRY(hipGetLastError());
-    }
-    // the tree kernel goes first: its workgroups take their places per shader engine, the net kernel is sized for what is left
-    // (CU split: on its own stream, masked to the tree side's CUs; the caller's stream waits for it)
-    hipStream_t ts = ps->tree_stream && !tree_only ? ps->tree_stream : st;
-    if (ts != st) AZMI_HIP_TRY(hipStreamWaitEvent(ts, ps->ev_go, 0));
-    AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 2], ts));
-    pipe_launch_tree(pm, ps, pa, ts, prof);
-    AZMI_HIP_TRY(hipGetLastError());
-    AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 3], ts));
-    if (ts != st) { AZMI_HIP_TRY(hipEventRecord(ps->ev_tree, ts)); AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_tree, 0)); }
-    if (pm->ep.cache_on) {      // behind the tree kernel, beside the net side's last tiles
-      k_pipe_cache_insert<<<2048, 256, 0, st>>>(pm->ar, pa, 0u);
-      AZMI_HIP_TRY(hipGetLastError());
-    }
-    if (!tree_only && !ps->cv_on) {
-      AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 0], ps->net_stream));
-      rc = pipe_launch_net(ps, view, net_mode, ps->net_launch, ps->net_stream, pa);
-      if (rc != AZMI_OK) return rc;
-      AZMI_HIP_TRY(hipEventRecord(ps->tev[4 * e + 1], ps->net_stream));
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_net, ps->net_stream));
-      AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_net, 0));
-    }
-    if (ps->cv_on) {
-      AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_net, 0));
-      AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_svc, 0));
-    }
-    k_pipe_settle<<<settle_blocks, 256, 0, st>>>(pm->ep, pm->ar, pa);
-    AZMI_HIP_TRY(hipGetLastError());
-    rc = azmi_host_launch_move_step(pm, st);
+    rc = pipe_enqueue_epoch(pm, plan, k, e, st);
     if (rc != AZMI_OK) return rc;
-    rc = azmi_host_launch_assign(pm, st, 1u);
-    if (rc != AZMI_OK) return rc;
-    if (pm->ep.cache_on) {
-      k_pipe_cache_insert<<<256, 256, 0, st>>>(pm->ar, pa, 1u);
-      AZMI_HIP_TRY(hipGetLastError());
-    }
-    if (getenv("AZMI_PIPE_DEBUG")) {      // stop at the first epoch that raised an error, with that epoch's own counters
+    if (k.debug) {      // AZMI_PIPE_DEBUG: stop at the first epoch that raised an error, with that epoch's own counters
       PipeCtl dc; PipeEpoch de;
-      AZMI_HIP_TRY(hipMemcpyAsync(&dc, pa.ctl, sizeof(dc), hipMemcpyDeviceToHost, st));
-      AZMI_HIP_TRY(hipMemcpyAsync(&de, pa.ep, sizeof(de), hipMemcpyDeviceToHost, st));
+      AZMI_HIP_TRY(hipMemcpyAsync(&dc, pm->pipe->pa.ctl, sizeof(dc), hipMemcpyDeviceToHost, st));
+      AZMI_HIP_TRY(hipMemcpyAsync(&de, pm->pipe->pa.ep, sizeof(de), hipMemcpyDeviceToHost, st));
       AZMI_HIP_TRY(hipStreamSynchronize(st));
       if (dc.err) {
         fprintf(stderr, "pipeline debug: epoch %u of this call: err 0x%x head %u tail %u sims %llu ended %u dead %u stop %u tree_done %u/%u arrived, net arrived %u, ins %u, late %u/%u\n",
@@ -2124,84 +2001,7 @@ static int run_pipeline_impl(azmi_pm* pm, azmi_net* const* nets, uint32_t num_ne
     }
   }
   const uint64_t host_enqueue_us = static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - host_t0).count());
-  // the run is synchronous: a pipeline error (a spin that hit its time cap, a tag that did not match) must not go unseen
-  PipeCtl hc;
-  PipeEpoch he;
-  AZMI_HIP_TRY(hipMemcpyAsync(&hc, pa.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-  AZMI_HIP_TRY(hipMemcpyAsync(&he, pa.ep, sizeof(he), hipMemcpyDeviceToHost, st));
-  AZMI_HIP_TRY(hipStreamSynchronize(st));
-  if (hc.lost_total != ps->lost_seen) {
-    fprintf(stderr, "azmi_run_pipeline: %u request(s) were given up by the net side and sent again (a net workgroup fell more than half a ring behind)\n", hc.lost_total - ps->lost_seen);
-    ps->lost_seen = hc.lost_total;
-  }
-  if (!tree_only && !hc.err && !ps->cv_on) pipe_balance(ps, hc);       // (takes effect with the next call's first epoch)
-  if (out_stats) {
-    out_stats[0] = hc.tiles; out_stats[1] = hc.tile_boards; out_stats[2] = he.sims; out_stats[3] = he.tree_arrived;
-    out_stats[4] = he.net_arrived; out_stats[5] = he.ins_count; out_stats[6] = ps->cv_on ? ps->cv_lines : ps->net_launch; out_stats[7] = ps->tree_wgs;
-    out_stats[8] = he.tree_late / 100u; out_stats[9] = he.net_late / 100u;
-    double net_us = 0.0, tree_us = 0.0;
-    for (uint32_t e = 0; e < epochs; ++e) {
-      float ms = 0.0f;
-      if (!tree_only && hipEventElapsedTime(&ms, ps->tev[4 * e + 0], ps->tev[4 * e + 1]) == hipSuccess) net_us += 1e3 * ms;
-      if (hipEventElapsedTime(&ms, ps->tev[4 * e + 2], ps->tev[4 * e + 3]) == hipSuccess) tree_us += 1e3 * ms;
-    }
-    out_stats[10] = static_cast<uint64_t>(net_us); out_stats[11] = static_cast<uint64_t>(tree_us); out_stats[12] = epochs; out_stats[13] = host_enqueue_us; out_stats[14] = static_cast<uint64_t>(ps->calib_rounds & 0xFFu) | (static_cast<uint64_t>(std::min<unsigned long long>(hc.freezes, 0xFFFFFFull)) << 8) | (static_cast<uint64_t>(hc.lost_total) << 32); out_stats[15] = hc.l0_hits;
-    if (getenv("AZMI_PIPE_PROF")) {
-      fprintf(stderr, "pipe prof:");
-      for (int i = 0; i < 16; ++i) fprintf(stderr, " %llu", hc.prof[i]);
-      fprintf(stderr, "\n");
-    }
-    if (getenv("AZMI_PIPE_PROF") || getenv("AZMI_PIPE_HIST")) {
-      fprintf(stderr, "pipe tile hist (tiles of 1 .. 6 boards since creation):");
-      for (int i = 0; i < 6; ++i) fprintf(stderr, " %llu", hc.tile_hist[i]);
-      fprintf(stderr, "\n");
-    }
-  }
-  if (hc.err) {
-    fprintf(stderr, "pipeline dbg:");
-    for (int i = 0; i < 18; ++i) fprintf(stderr, " %u", hc.dbg[i]);
-    fprintf(stderr, "\n");
-    if (plan.kind == 2) {      // the generic tree kernel: where each of its wavefronts was last (phase, 10 us units since its start)
-      std::vector<PipeWg> hw(ps->tree_wgs);
-      if (hipMemcpy(hw.data(), pa.wg, hw.size() * sizeof(PipeWg), hipMemcpyDeviceToHost) == hipSuccess) {
-        fprintf(stderr, "pipeline generic tree kernel, workgroup: rhead rtail | phase@10us of its four wavefronts | their entry times, us after wavefront 0's:");
-        for (uint32_t w = 0; w < ps->tree_wgs; ++w)
-          fprintf(stderr, "  [%u: %u %u | %u@%u %u@%u %u@%u %u@%u | %d %d %d]", w, hw[w].rhead, hw[w].rtail, hw[w].pad[2] & 255u, hw[w].pad[2] >> 8, hw[w].pad[3] & 255u, hw[w].pad[3] >> 8,
-                  hw[w].pad[4] & 255u, hw[w].pad[4] >> 8, hw[w].pad[5] & 255u, hw[w].pad[5] >> 8,
-                  static_cast<int32_t>(hw[w].pad[7] - hw[w].pad[6]) / 100, static_cast<int32_t>(hw[w].pad[8] - hw[w].pad[6]) / 100, static_cast<int32_t>(hw[w].pad[9] - hw[w].pad[6]) / 100);
-        fprintf(stderr, "\n  wavefront 0's longest interval between two looks: wall clock x10us | SQ clock >> 10 | 0 poll loop, 1 a pass | after polls | polls in all:");
-        for (uint32_t w = 0; w < ps->tree_wgs; ++w) fprintf(stderr, "  [%u: %u | %u | %u | %u | %u]", w, hw[w].pad[10], hw[w].pad[11], hw[w].pad[12], hw[w].pad[13], hw[w].pad[14]);
-        fprintf(stderr, "\n  longest phases of its passes (SQ clock >> 10): publication word | granules | log ticket + drain | steps + requests | tokens:");
-        for (uint32_t w = 0; w < ps->tree_wgs; ++w) fprintf(stderr, "  [%u: %u | %u | %u | %u | %u]", w, hw[w].pad[18], hw[w].pad[19], hw[w].pad[20], hw[w].pad[21], hw[w].pad[22]);
-        fprintf(stderr, "\n  its longest segments (SQ clock >> 10): token load | control words | between looks:");
-        for (uint32_t w = 0; w < ps->tree_wgs; ++w) fprintf(stderr, "  [%u: %u | %u | %u]", w, hw[w].pad[15], hw[w].pad[16], hw[w].pad[17]);
-        fprintf(stderr, "\n");
-      }
-    }
-  }
-  if (hc.err) {
-    // reported once: k_pipe_settle has put every slot whose request went unanswered back into the move step's kSlotQueued form, so
-    // the engine is whole - the next call (either driver) carries on from here
-    AZMI_HIP_TRY(hipMemsetAsync(&pa.ctl->err, 0, sizeof(uint32_t), st));
-    AZMI_HIP_TRY(hipMemsetAsync(pa.ctl->dbg, 0, sizeof(pa.ctl->dbg), st));
-    AZMI_HIP_TRY(hipStreamSynchronize(st));
-  }
-  if (hc.err)
-    return azmi_host_fail(AZMI_ERR_STATE, "pipeline error mask 0x%x (1 a spin hit the epoch's time cap, 2 a ring entry never arrived, 4 a result tag "
-                          "did not match, 8 insert log full, 16 cache lock, 32 slots, 64 the net side hit the time cap); census: %u of %u tree and %u of %u net workgroups started; "
-                          "last epoch: head %u tail %u sims %llu ended %u dead %u stop %u tree_done %u tiles %llu boards %llu; latest tree / net workgroup start %u / %u us; "
-                          "first time-out saw: slot %u seq %u / %u; net side: stop %u tree done %u of %u tail %u window at %u after %u0 us; "
-                          "wavefronts that stood still > 2 ms (not one instruction between two looks at the clock) so far: %llu, the longest for %.1f ms",
-                          hc.err, he.tree_arrived, ps->tree_wgs, he.net_arrived, ps->net_launch, hc.head, hc.tail, he.sims, he.ended, he.dead, he.stop,
-                          he.tree_done, hc.tiles, hc.tile_boards, he.tree_late / 100u, he.net_late / 100u,
-                          hc.dbg[1], hc.dbg[2], hc.dbg[3], hc.dbg[8], hc.dbg[9], hc.dbg[10], hc.dbg[11], hc.dbg[12], hc.dbg[13],
-                          static_cast<unsigned long long>(hc.freezes), static_cast<double>(hc.freeze_max) * 1e-5);
-  if (hc.err && getenv("AZMI_PIPE_DEBUG")) {
-    fprintf(stderr, "pipeline dbg:");
-    for (int i = 0; i < 18; ++i) fprintf(stderr, " %u", hc.dbg[i]);
-    fprintf(stderr, "\n");
-  }
-  return AZMI_OK;
+  return pipe_finish_call(pm, plan, k, epochs, host_enqueue_us, st, out_stats);
 }
 
 // probes the S3-FIFO missed and the in-epoch answer table answered (azmi_pm_cache_stats moves them from misses to hits)
@@ -2270,6 +2070,7 @@ __global__ void k_pipe_head_reset(PipeArrays pa) { pa.ctl->head = pa.ctl->tail; 
 // three-board).  Timing only: the slots' result granules are overwritten.
 extern "C" int azmi_debug_pipe_net_bench(azmi_pm* pm, azmi_net* net, uint32_t n, uint32_t reps, uint32_t net_wgs, int mode, float* ms_out) {
   if (!pm || !net || !ms_out) return azmi_host_fail(AZMI_ERR_INVALID, "null argument");
+  if (mode == 3) return pipe_no_conveyor();
   std::lock_guard<std::recursive_mutex> lock_(pm->mu);
   azmi_net* nets_[2] = {net, net};
   const PipePlan plan_ = pipe_plan(pm, nets_, 2);
@@ -2287,28 +2088,12 @@ extern "C" int azmi_debug_pipe_net_bench(azmi_pm* pm, azmi_net* net, uint32_t n,
   AZMI_HIP_TRY(hipEventCreate(&e0)); AZMI_HIP_TRY(hipEventCreate(&e1));
   float total = 0.0f;
   const uint32_t wgs = net_wgs ? net_wgs : ps->net_wgs;
-  if (mode == 3) {      // the conveyor: net_wgs = lines (0: as many as the chip holds)
-    if (view.x3 || view.nd.depth < 2 || view.nd.depth % 2) return azmi_host_fail(AZMI_ERR_STATE, "the conveyor runs the bf16 tier with an even number of residual blocks");
-    { const int rc = cv_setup(pm, ps, view); if (rc != AZMI_OK) return rc; }
-    if (net_wgs) ps->cv_lines = std::min(net_wgs, ps->cv_lines_alloc);
-    else { hipDeviceProp_t prop; AZMI_HIP_TRY(hipGetDeviceProperties(&prop, pm->device)); ps->cv_lines = std::min(ps->cv_lines_alloc, cv_default_lines(static_cast<uint32_t>(prop.multiProcessorCount), ps->cv_nwg, 0u)); }
-  }
   for (uint32_t r = 0; r < reps + 1; ++r) {
     AZMI_HIP_TRY(hipMemsetAsync(pa.ep, 0, sizeof(PipeEpoch), st));
-    if (mode == 3) { const int rc = cv_zero_headers(ps, st); if (rc != AZMI_OK) return rc; }
     k_pipe_fill<<<(n + 255) / 256, 256, 0, st>>>(pa, n, pm->ep.S, 1234 + r);
     k_pipe_fill_done<<<1, 1, 0, st>>>(pa, n);
     AZMI_HIP_TRY(hipEventRecord(e0, st));
-    if (mode == 3) {
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_go, st));
-      AZMI_HIP_TRY(hipStreamWaitEvent(ps->net_stream, ps->ev_go, 0));
-      AZMI_HIP_TRY(hipStreamWaitEvent(ps->svc_stream, ps->ev_go, 0));
-      { const int rc = cv_launch(ps, view, pa, 0u); if (rc != AZMI_OK) return rc; }
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_net, ps->net_stream));
-      AZMI_HIP_TRY(hipEventRecord(ps->ev_svc, ps->svc_stream));
-      AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_net, 0));
-      AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_svc, 0));
-    } else { const int rc = pipe_launch_net(ps, view, mode, wgs, st, pa); if (rc != AZMI_OK) return rc; }
+    { const int rc = pipe_launch_net(ps, view, mode, wgs, st, pa); if (rc != AZMI_OK) return rc; }
     AZMI_HIP_TRY(hipEventRecord(e1, st));
     k_pipe_head_reset<<<1, 1, 0, st>>>(pa);                   // (head = tail for the next drain; the READY tokens of the synthetic answers are dropped)
     AZMI_HIP_TRY(hipStreamSynchronize(st));
@@ -2317,20 +2102,6 @@ extern "C" int azmi_debug_pipe_net_bench(azmi_pm* pm, azmi_net* net, uint32_t n,
     if (r > 0) total += ms;
   }
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  if (mode == 3 && getenv("AZMI_CV_STAT")) {
-    unsigned long long h[32];
-    AZMI_HIP_TRY(hipMemcpy(h, ps->cv_stat, sizeof(h), hipMemcpyDeviceToHost));
-    AZMI_HIP_TRY(hipMemset(ps->cv_stat, 0, sizeof(h)));
-    fprintf(stderr, "conveyor stat (%u lines, %u drains): conv n-tiles %llu (drained %llu), stem groups %llu boards %llu, head groups %llu | per wave, us: "
-            "conv wait-in %.0f %.0f %.0f %.0f wait-out %.0f %.0f %.0f %.0f life %.0f | stem claim %.0f room %.0f life %.0f | head wait %.0f life %.0f\n",
-            ps->cv_lines, reps + 1, h[0], h[1], h[2], h[3], h[4],
-            h[5] * 0.01 / (ps->cv_lines * ps->cv_nwg), h[6] * 0.01 / (ps->cv_lines * ps->cv_nwg), h[7] * 0.01 / (ps->cv_lines * ps->cv_nwg), h[8] * 0.01 / (ps->cv_lines * ps->cv_nwg),
-            h[9] * 0.01 / (ps->cv_lines * ps->cv_nwg), h[10] * 0.01 / (ps->cv_lines * ps->cv_nwg), h[11] * 0.01 / (ps->cv_lines * ps->cv_nwg), h[12] * 0.01 / (ps->cv_lines * ps->cv_nwg),
-            h[16] * 0.01 / (ps->cv_lines * ps->cv_nwg), h[13] * 0.01 / ps->cv_lines, h[14] * 0.01 / ps->cv_lines, h[20] * 0.01 / ps->cv_lines,
-            h[15] * 0.01 / (ps->cv_lines * ps->cv_heads), h[21] * 0.01 / (ps->cv_lines * ps->cv_heads));
-    if (h[26]) fprintf(stderr, "  back-to-back n-tiles, ns each by role: %.0f %.0f %.0f %.0f (of %llu %llu %llu %llu)\n", 10.0 * h[22] / std::max(1ull, h[26]), 10.0 * h[23] / std::max(1ull, h[27]),
-                       10.0 * h[24] / std::max(1ull, h[28]), 10.0 * h[25] / std::max(1ull, h[29]), h[26], h[27], h[28], h[29]);
-  }
   // the synthetic answers carry sequence numbers a real request of the same slot could draw later: wipe the granules
   AZMI_HIP_TRY(hipMemsetAsync(pa.res, 0, sizeof(unsigned long long) * static_cast<size_t>(pm->ep.S) * kResStride, st));
   AZMI_HIP_TRY(hipStreamSynchronize(st));
@@ -2340,65 +2111,6 @@ extern "C" int azmi_debug_pipe_net_bench(azmi_pm* pm, azmi_net* net, uint32_t n,
   if (hc.err) {
     (void)hipMemset(&pa.ctl->err, 0, sizeof(uint32_t));
     return azmi_host_fail(AZMI_ERR_STATE, "pipeline error mask 0x%x in the net drain", hc.err);
-  }
-  return AZMI_OK;
-}
-
-// The net side's ANSWERS for `n` synthetic positions (n <= the engine's slots; position i -> slot i): the request ring is filled from
-// `seed` (k_pipe_fill), the net side drains it once - conveyor != 0: the conveyor with `lines` lines (0: the default), else the tile
-// kernel (tile selection 0) -, out[i * 10 + k] = entry k of slot i's result granules (pi[0..7) then v[0..3)), out_seq[i] = the sequence
-// number they carry (i + 1 when the slot was answered).  tests/test_gpu_conveyor.py compares the two paths bit for bit.
-extern "C" int azmi_debug_pipe_net_answers(azmi_pm* pm, azmi_net* net, uint32_t n, uint64_t seed, int conveyor, uint32_t lines, float* out, uint32_t* out_seq) {
-  if (!pm || !net || !out || !out_seq) return azmi_host_fail(AZMI_ERR_INVALID, "null argument");
-  std::lock_guard<std::recursive_mutex> lock_(pm->mu);
-  azmi_net* nets_[2] = {net, net};
-  const PipePlan plan_ = pipe_plan(pm, nets_, 2);
-  if (plan_.kind == 0 || plan_.tree_only) return azmi_host_fail(AZMI_ERR_STATE, "not a pipeline engine");
-  const azmi_net_c4_view view = plan_.view[0];
-  if (n > pm->ep.S || n > kPipeRing) return azmi_host_fail(AZMI_ERR_INVALID, "at most %u positions", pm->ep.S);
-  AZMI_HIP_TRY(hipSetDevice(pm->device));
-  if (!pm->pipe) { const int rc = pipe_create(pm, azmi_net_dev::c4::TileBig::LDS_BYTES); if (rc != AZMI_OK) return rc; }
-  PipeState* ps = pm->pipe;
-  PipeArrays pa = ps->pa;
-  { const int rc = pipe_size_net(pm, ps, view); if (rc != AZMI_OK) return rc; }
-  pa.cap_ticks = 25000000ull;
-  pa.l0 = nullptr;
-  hipStream_t st = pm->stream;
-  { const int rc = pipe_pair_streams(ps, st); if (rc != AZMI_OK) return rc; }
-  if (conveyor) {
-    if (view.x3 || view.nd.depth < 2 || view.nd.depth % 2) return azmi_host_fail(AZMI_ERR_STATE, "the conveyor runs the bf16 tier with an even number of residual blocks");
-    { const int rc = cv_setup(pm, ps, view); if (rc != AZMI_OK) return rc; }
-    if (lines) ps->cv_lines = std::min(lines, ps->cv_lines_alloc);
-  }
-  AZMI_HIP_TRY(hipMemsetAsync(pa.res, 0, sizeof(unsigned long long) * static_cast<size_t>(pm->ep.S) * kResStride, st));
-  AZMI_HIP_TRY(hipMemsetAsync(pa.ep, 0, sizeof(PipeEpoch), st));
-  if (conveyor) { const int rc = cv_zero_headers(ps, st); if (rc != AZMI_OK) return rc; }
-  k_pipe_fill<<<(n + 255) / 256, 256, 0, st>>>(pa, n, pm->ep.S, seed);
-  k_pipe_fill_done<<<1, 1, 0, st>>>(pa, n);
-  if (conveyor) {
-    AZMI_HIP_TRY(hipEventRecord(ps->ev_go, st));
-    AZMI_HIP_TRY(hipStreamWaitEvent(ps->net_stream, ps->ev_go, 0));
-    AZMI_HIP_TRY(hipStreamWaitEvent(ps->svc_stream, ps->ev_go, 0));
-    { const int rc = cv_launch(ps, view, pa, 0u); if (rc != AZMI_OK) return rc; }
-    AZMI_HIP_TRY(hipEventRecord(ps->ev_net, ps->net_stream));
-    AZMI_HIP_TRY(hipEventRecord(ps->ev_svc, ps->svc_stream));
-    AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_net, 0));
-    AZMI_HIP_TRY(hipStreamWaitEvent(st, ps->ev_svc, 0));
-  } else { const int rc = pipe_launch_net(ps, view, 0, ps->net_wgs, st, pa); if (rc != AZMI_OK) return rc; }
-  k_pipe_head_reset<<<1, 1, 0, st>>>(pa);
-  std::vector<unsigned long long> hres(static_cast<size_t>(n) * kResStride);
-  AZMI_HIP_TRY(hipMemcpyAsync(hres.data(), pa.res, hres.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  AZMI_HIP_TRY(hipMemsetAsync(pa.res, 0, sizeof(unsigned long long) * static_cast<size_t>(pm->ep.S) * kResStride, st));
-  PipeCtl hc;
-  AZMI_HIP_TRY(hipMemcpyAsync(&hc, pa.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-  AZMI_HIP_TRY(hipStreamSynchronize(st));
-  for (uint32_t i = 0; i < n; ++i) {
-    out_seq[i] = static_cast<uint32_t>(hres[static_cast<size_t>(i) * kResStride] >> 32);
-    for (uint32_t k = 0; k < 10; ++k) { const uint32_t bits = static_cast<uint32_t>(hres[static_cast<size_t>(i) * kResStride + k]); memcpy(out + static_cast<size_t>(i) * 10 + k, &bits, 4); }
-  }
-  if (hc.err) {
-    AZMI_HIP_TRY(hipMemset(&pa.ctl->err, 0, sizeof(uint32_t)));
-    return azmi_host_fail(AZMI_ERR_STATE, "pipeline error mask 0x%x in the net drain (dbg %u %u %u %u %u %u)", hc.err, hc.dbg[8], hc.dbg[9], hc.dbg[10], hc.dbg[11], hc.dbg[12], hc.dbg[13]);
   }
   return AZMI_OK;
 }
