@@ -32,6 +32,8 @@ lib.azmi_net_destroy.restype = None
 lib.azmi_net_destroy.argtypes = [C.c_void_p]
 lib.azmi_net_forward.restype = C.c_int
 lib.azmi_net_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+lib.azmi_net_forward_rows.restype = C.c_int
+lib.azmi_net_forward_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
 lib.azmi_net_last_error.restype = C.c_char_p
 
 
@@ -107,6 +109,13 @@ def fold_spatial(net, x3=False):
                            "channels, one extra conv per head); use precision='fp32' for other shapes")
     pc = spec.policy_shape[0]
     Hd, L, P1 = spec.v_fc_hidden, spec.v_fc_layers, spec.num_players + 1
+    # the bounds of azmi_net_create (csrc/leafnet.hip) that the paddings below rely on, with its messages
+    if pc > 32 or not 0 <= spec.num_moves - pc * H * W <= 32:
+        raise RuntimeError("spatial head: policy channels <= 32, 0..32 global actions")
+    if spec.num_moves > pc * H * W and (spec.pi_fc_hidden < 64 or spec.pi_fc_hidden > 1024 or spec.pi_fc_hidden % 64):
+        raise RuntimeError("spatial head with global actions: pi_hidden must be a multiple of 64 in [64, 1024]")
+    if Hd > 512 or Hd % 128 or Hd < 128 or L < 1 or P1 > 16 or P1 < 2:
+        raise RuntimeError("value head sizes out of range")
     sd = {k: v.detach().double().cpu() for k, v in net.state_dict().items()}
     stream, prm = bytearray(), bytearray()
     # x3 (precision "bf16x3", csrc/leafnet_sp.h Geo<.., SPLIT>): every 8 KB chunk three times - high parts, high parts, low parts
@@ -160,7 +169,8 @@ def fold_fp32(net):
     """fp32 path (csrc/leafnet_f32.hip): torch layouts, BatchNorms folded in double, no bf16 anywhere."""
     spec = net.spec
     Cin, H, W = spec.in_shape
-    assert spec.kernel_size == 3 and spec.head_pool
+    if not (spec.kernel_size == 3 and spec.head_pool):
+        raise RuntimeError("fp32 leaf net: 3x3 convolutions and pooled value / global-action heads only")
     sd = {k: v.detach().double().cpu() for k, v in net.state_dict().items()}
     blob = bytearray()
 
@@ -232,7 +242,9 @@ def fold(net, precision="bf16"):
             and 9 * Cin <= 64 and (H, W) == (6, 7)):
         raise RuntimeError("the bf16 MFMA flat-head kernel covers the Connect4 net family (6x7, 64 trunk / 32 head channels, "
                            "flat policy head); use precision='fp32' for other shapes")
-    sd = {k: v.detach().double().cpu() for k, v in net.state_dict().items()}
+    if not (16 <= spec.v_fc_hidden <= 256 and 1 <= spec.num_players <= 3 and 1 <= spec.num_moves <= 16) and spec.v_fc_hidden % 16 == 0:
+        raise RuntimeError("head sizes out of range (v_hidden: a multiple of 16, at most 256)")      # azmi_net_create's bound and message
+    sd ={k: v.detach().double().cpu() for k, v in net.state_dict().items()}
     blob = bytearray()
     # stem: conv1 * bn1
     a, b = bn_affine(net.bn1)
@@ -300,6 +312,25 @@ class HipLeafNet:
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
         rc = lib.azmi_net_forward(self._h, canonical.data_ptr(), v_out.data_ptr(), pi_out.data_ptr(), n, C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(lib.azmi_net_last_error().decode())
+
+    def forward_rows(self, canonical, v_out, pi_out, rows, row_count, max_rows=None, stream=None):
+        """azmi_net_forward_rows: evaluate the slots rows[0 .. row_count[0]) of `canonical` into the same slots of v_out / pi_out
+        and touch no other slot.  `rows` (int32 / uint32, at least max_rows entries, every one a valid slot) and `row_count`
+        (one element) are DEVICE tensors read when the kernels run; max_rows (default len(rows)) bounds the count and
+        sizes the launch."""
+        if max_rows is None:
+            max_rows = rows.numel()
+        assert canonical.dtype == torch.float32 and canonical.is_contiguous() and v_out.is_contiguous() and pi_out.is_contiguous()
+        assert v_out.dtype == torch.float32 and pi_out.dtype == torch.float32
+        assert rows.is_cuda and row_count.is_cuda and rows.is_contiguous() and rows.element_size() == 4 and row_count.element_size() == 4
+        assert not rows.dtype.is_floating_point and not row_count.dtype.is_floating_point
+        assert 0 <= max_rows <= rows.numel() and row_count.numel() >= 1
+        if stream is None:
+            stream = torch.cuda.current_stream().cuda_stream
+        rc = lib.azmi_net_forward_rows(self._h, canonical.data_ptr(), v_out.data_ptr(), pi_out.data_ptr(), rows.data_ptr(),
+                                       row_count.data_ptr(), int(max_rows), C.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(lib.azmi_net_last_error().decode())
 

@@ -126,8 +126,8 @@ struct Net {
   azmi_net_desc d{};
   int device = 0;
   float* blob = nullptr;
-  float* buf[3] = {nullptr, nullptr, nullptr};   // [rows][64][HW] ping-pong activations
-  float* small[2] = {nullptr, nullptr};          // [rows][max(Hd, M, HC)] head vectors
+  float* buf[3] = {nullptr, nullptr, nullptr};   // [rows][max(CH, HC, PC)][HW] ping-pong activations
+  float* small[2] = {nullptr, nullptr};          // [rows][max(Hd, Hp, M, HC, P+1)] head vectors
   uint32_t rows = 0;
 };
 
@@ -177,8 +177,10 @@ int reserve(void* impl, uint32_t batch, const char** err) {
   for (float*& p : n->small) { if (p) (void)hipFree(p); p = nullptr; }
   n->rows = 0;
   const size_t HW = static_cast<size_t>(n->d.height) * n->d.width;
-  const size_t CH = std::max<size_t>(n->d.channels, n->d.head_channels);
-  const size_t wide = std::max<size_t>(std::max<size_t>(std::max<size_t>(n->d.v_hidden, n->d.pi_hidden), n->d.num_moves), n->d.head_channels);
+  // the widest [rows][c][HW] activation: trunk, heads, or the spatial policy block [policy_channels][HW] (it may be the widest)
+  const size_t CH = std::max<size_t>(std::max<size_t>(n->d.channels, n->d.head_channels), std::max(n->d.policy_channels, 0));
+  const size_t wide = std::max<size_t>(std::max<size_t>(std::max<size_t>(std::max<size_t>(n->d.v_hidden, n->d.pi_hidden), n->d.num_moves), n->d.head_channels),
+                                       n->d.num_players + 1);
   for (float*& p : n->buf)
     if (hipMalloc(reinterpret_cast<void**>(&p), static_cast<size_t>(batch) * CH * HW * sizeof(float)) != hipSuccess)
       return fail(err, AZMI_ERR_OOM, "hipMalloc(fp32 activations) failed");
@@ -191,6 +193,8 @@ int reserve(void* impl, uint32_t batch, const char** err) {
 
 int create(const azmi_net_desc* d, const void* blob, size_t bytes, int device, void** impl, const char** err) {
   if (d->channels < 1 || d->kernel_size != 3) return fail(err, AZMI_ERR_INVALID, "fp32 leaf net: 3x3 convolutions only");
+  if (d->in_channels < 1 || d->height < 1 || d->width < 1 || d->depth < 0 || d->v_hidden < 1 || d->num_moves < 1 || d->num_players < 0)
+    return fail(err, AZMI_ERR_INVALID, "fp32 leaf net: sizes out of range");
   if (d->head_channels < 1 || d->v_fc_layers < 1 || d->v_head_convs < 0 || d->pi_head_convs < 0)
     return fail(err, AZMI_ERR_INVALID, "fp32 leaf net: head sizes out of range");
   if (d->policy_channels > 0 && d->policy_channels * d->height * d->width > d->num_moves)
