@@ -563,11 +563,36 @@ class MCTSBatch:
     call (frozen_eval.py:545-660, mcts_analysis.py:923-1049, play.py:292-343).  Tree i is bit for bit the stand-alone
     `MCTS(..., seed=seeds[i])` driven call by call from states[i] with the same evaluator values.  The constructor takes the
     MCTS constructor's search arguments; `max_simulations` (required) sizes every tree's arena.  No move is played on a batch:
-    call reset() with the new positions.  Read-outs return one row per tree."""
+    call reset() with the new positions.  Read-outs return one row per tree.
+
+    `leaves_per_step=K` (1 <= K <= 64, default 1) holds K leaves of every tree in flight per step (WU-UCT), for a few
+    positions searched deeply: the net then sees up to n * K rows per call instead of n.  With K > 1 one step of tree i is
+
+        for k in 0..K-1:                      # exactly K descents: a step is K simulations of every live tree
+            leaf = find_leaf_batched(root)    # sees the in-flight marks of descents 0..k-1
+            terminal leaf, RANDOM evaluator or cache hit: process_result_batched(k, ...) at once
+            otherwise: the leaf's planes become one row of the step's batch
+        evaluate all rows in one call
+        for the pending k, ascending: process_result_batched(k, v, pi, root_noise)
+        reset_batch()
+
+    and tree i is bit for bit the stand-alone `MCTS(seed=seeds[i])` driven by those calls.  This is play.py's _run_one_batch
+    with the attempt count fixed at K: the reference loops "until K misses or 2K attempts", which gives the trees of one
+    batch different simulation counts per step, and a lock-step batch cannot budget that against `max_simulations`.  Rows of
+    a step are ordered by tree, then by descent (find_leaves() returns `tree_index` with repeats); two in-flight leaves on
+    the same position both miss the cache and are both evaluated; search(visits) runs visits // K steps and one of
+    visits % K descents; `max_simulations` and stats()["simulations"] count descents, stats()["steps"] counts steps.  After
+    every completed step no in-flight mark is left.  Gumbel search needs K == 1 (the reference's batched descent is plain
+    PUCT, mcts.cc:752-784)."""
 
     def __init__(self, game, n, cpuct, epsilon=0.0, root_policy_temp=1.0, fpu_reduction=0.0, root_fpu_zero=False,
                  shaped_dirichlet=False, gumbel_enabled=False, gumbel_m=16, gumbel_c_visit=50.0, gumbel_c_scale=1.0,
-                 gumbel_full=False, *, max_simulations, seeds=None, device=0):
+                 gumbel_full=False, *, max_simulations, seeds=None, device=0, leaves_per_step=1):
+        if isinstance(leaves_per_step, bool) or not isinstance(leaves_per_step, (int, np.integer)) or not 1 <= leaves_per_step <= 64:
+            raise RuntimeError(f"leaves_per_step must be an integer in [1, 64], got {leaves_per_step!r}")
+        if leaves_per_step > 1 and gumbel_enabled:
+            raise RuntimeError(f"leaves_per_step = {leaves_per_step} with gumbel_enabled: the batched descent (find_leaf_batched) "
+                               "is plain PUCT; use leaves_per_step = 1 for a Gumbel search")
         game = game if isinstance(game, type) else type(game)
         P, M, chw = game._info()
         cfg = _capi.MctsConfigC(cpuct, P, M, epsilon, root_policy_temp, fpu_reduction, int(game.GAME_ID == StarGambitUnifiedGS.GAME_ID),
@@ -580,6 +605,13 @@ class MCTSBatch:
         self._vec = max(M, 64)
         self._seeds = None if seeds is None else self._seed_array(seeds)
         self._rows = None          # rows of the pending find_leaves() batch
+        self._k = int(leaves_per_step)
+        if self._k > 1:
+            check(lib.azmi_search_set_leaves_per_step(self._h, self._k))
+
+    @property
+    def leaves_per_step(self):
+        return self._k
 
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:
@@ -623,7 +655,8 @@ class MCTSBatch:
                                     offs.ctypes.data, sd.ctypes.data))
 
     def search(self, visits, net=None, cache=None, root_noise=False):
-        """`visits` simulations of every tree, enqueued without host synchronisation (the read-outs and synchronize() wait).
+        """`visits` simulations of every tree, enqueued without host synchronisation (the read-outs and synchronize() wait);
+        with leaves_per_step = K: visits // K steps of K descents and one of visits % K.
         net: a HipLeafNet (None = EvalType.RANDOM, dumb_eval); cache: a ShardedS3FIFOCache shared by all trees."""
         if net is not None and (net.desc.num_moves != self._M or (net.desc.in_channels, net.desc.height, net.desc.width) != self._chw):
             raise RuntimeError("search: the net's shape does not match the game")
@@ -637,8 +670,9 @@ class MCTSBatch:
 
     # ---- step API: any evaluator --------------------------------------------------------------------
     def find_leaves(self, numpy=None):
-        """One simulation's descent of every tree -> (canonical [n_rows, C, H, W], tree_index [n_rows]): the leaves that need
-        an evaluation, rows in ascending tree order (terminal leaves are backed up at once and take no row).  Device tensors
+        """One simulation's descent of every tree (leaves_per_step = K: K descents, or as many as max_simulations leaves)
+        -> (canonical [n_rows, C, H, W], tree_index [n_rows]): the leaves that need an evaluation, rows in ascending tree
+        order, then descent order (terminal leaves are backed up at once and take no row).  Device tensors
         (views of the object's buffers, valid until the next find_leaves) when torch is importable, numpy arrays otherwise or
         with numpy=True."""
         pc, pt, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
@@ -672,8 +706,8 @@ class MCTSBatch:
             raise RuntimeError("process_results: no leaf batch is pending; call find_leaves first")
         rows = self._rows
         if tuple(v.shape) != (rows, self._P + 1) or tuple(pi.shape) != (rows, self._M):
-            raise RuntimeError(f"process_results: v must be [{rows}, {self._P + 1}] and pi [{rows}, {self._M}], "
-                               f"got {tuple(v.shape)} and {tuple(pi.shape)}")
+            raise RuntimeError(f"process_results: the step has {rows} rows: v must be [{rows}, {self._P + 1}] and pi "
+                               f"[{rows}, {self._M}], got {tuple(v.shape)} and {tuple(pi.shape)}")
         if isinstance(v, np.ndarray) or isinstance(pi, np.ndarray):
             vv = np.ascontiguousarray(v, dtype=np.float32); pp = np.ascontiguousarray(pi, dtype=np.float32)
             check(lib.azmi_search_process_results_host(self._h, vv.ctypes.data, pp.ctypes.data, int(bool(root_noise))))

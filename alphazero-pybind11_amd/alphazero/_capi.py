@@ -202,6 +202,7 @@ SYMBOLS = {
     "azmi_search_query": (C.c_int, [_VP, C.c_uint32, C.c_float, C.c_uint32, _VP, _VP]),
     "azmi_search_sync": (C.c_int, [_VP]),
     "azmi_search_stats": (C.c_int, [_VP, _VP]),
+    "azmi_search_set_leaves_per_step": (C.c_int, [_VP, C.c_uint32]),
     "azmi_game_replay_ex": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32]),
     "azmi_game_replay_from": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "azmi_playout_eval": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP]),

@@ -2,10 +2,13 @@
 // them advanced by one simulation per (find-leaves, process-results) launch pair, the leaf net and the position cache on the
 // device.  Host side of csrc/search_batch_kernels.h.  The engine behind it is a PlayManager engine with N slots built from the
 // MCTS constructor's arguments (azmi_host_mcts_params, as azmi_mcts_create does for its one slot); no game is ever played on it.
+// azmi_search_set_leaves_per_step(K > 1) switches every step to K descents per tree with K leaves in flight (WU-UCT): the *_wu
+// kernels and launch helpers below; K == 1 runs the original ones.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/azmi.h"
@@ -35,6 +38,14 @@ struct azmi_search {
   float* d_qf = nullptr;          // [N, vec_f] / [N, vec_u] read-out buffers
   uint32_t* d_qu = nullptr;
   uint64_t launches = 0, net_calls = 0, steps = 0;
+  // several leaves in flight per tree and step (azmi_search_set_leaves_per_step): allocated only when K > 1
+  uint32_t k_leaves = 1;
+  uint32_t step_k = 0;            // descents of the pending find_leaves step
+  SbWuArrays wu{};
+  float* d_batch_wu = nullptr;    // [K * N, ...] the step API's buffers of a K > 1 step (d_batch, d_vrows, d_pirows hold N rows)
+  float* d_vrows_wu = nullptr;
+  float* d_pirows_wu = nullptr;
+  std::vector<void*> wu_allocs;
 };
 
 namespace {
@@ -86,6 +97,47 @@ void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArr
                 (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)));
     s->launches += 1;
   }
+}
+
+// ---- K > 1: the same steps over K descents of every tree; the launch counts do not depend on N or K ---------------------------
+EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine arrays with the step-sized [K * N] row buffers in place
+  ar.canon = s->wu.canon; ar.v = s->wu.v; ar.pi = s->wu.pi; ar.cache_keys = s->wu.keys;
+  return ar;
+}
+
+void launch_find_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t eval_random, uint32_t root_noise, hipStream_t st) {
+  const uint32_t n = s->n;
+  SB_DISPATCH(s->pm->game, (k_sb_find_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise)),
+              (k_sb_big_find_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise)));
+  k_sb_compact_wu<<<1, 1024, 0, st>>>(s->sb, s->wu, n, kk);
+  s->launches += 2;
+}
+
+void launch_process_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, const float* v_rows,
+                       const float* pi_rows, hipStream_t st) {
+  const uint32_t n = s->n;
+  SB_DISPATCH(s->pm->game, (k_sb_process_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows)),
+              (k_sb_big_process_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows)));
+  s->launches += 1;
+}
+
+// as launch_cache_insert, over the kk * N entries of the step: ceil(N * kk / kApplyMax) launches
+void launch_cache_insert_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, hipStream_t st) {
+  const EngineArrays aw = wu_rows(s, ar);
+  const uint32_t total = s->n * kk;
+  for (uint32_t off = 0; off < total; off += kApplyMax) {
+    const uint32_t m = std::min<uint32_t>(kApplyMax, total - off);
+    SB_DISPATCH(s->pm->game, (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, aw, aw.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)),
+                (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, aw, aw.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)));
+    s->launches += 1;
+  }
+}
+
+void wu_free(azmi_search* s) {
+  for (void* q : s->wu_allocs) (void)hipFree(q);
+  s->wu_allocs.clear();
+  s->wu = SbWuArrays{};
+  s->d_batch_wu = nullptr; s->d_vrows_wu = nullptr; s->d_pirows_wu = nullptr;
 }
 
 // synchronises `st` and turns a stopped tree / a raised overflow bit into an error that names the tree
@@ -171,8 +223,58 @@ int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, 
 
 void azmi_search_destroy(azmi_search* s) {
   if (!s) return;
+  (void)hipSetDevice(s->pm->device);
+  wu_free(s);        // (hipFree waits for the device)
   azmi_pm_destroy(s->pm);
   delete s;
+}
+
+int azmi_search_set_leaves_per_step(azmi_search* s, uint32_t k) {
+  if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (k < 1 || k > 64) return SB_FAIL(AZMI_ERR_INVALID, "leaves_per_step must be in [1, 64], got %u", k);
+  if (k > 1 && s->gumbel)
+    return SB_FAIL(AZMI_ERR_INVALID, "leaves_per_step = %u with gumbel_enabled: the batched descent (find_leaf_batched) is plain PUCT; "
+                   "use leaves_per_step = 1 for a Gumbel search", k);
+  if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "set_leaves_per_step: a find_leaves step is pending; call process_results first");
+  if (s->sims_done != 0) return SB_FAIL(AZMI_ERR_STATE, "set_leaves_per_step: the trees have been searched; call reset first");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  SB_TRY(hipStreamSynchronize(pm->last));
+  wu_free(s);
+  s->k_leaves = 1;
+  if (k == 1) return AZMI_OK;
+  const size_t N = s->n, E = N * k, P = pm->gi.P, M = pm->gi.M;
+  const size_t nif_cnt = N * P * pm->ep.cap;
+  const unsigned long long need = 4ull * nif_cnt + E * (4ull * pm->ep.max_depth + 8 + 1 + 12 + 8) +
+                                  8ull * E * (static_cast<size_t>(s->chw) + (P + 1) + M);
+  size_t free_b = 0, total_b = 0;
+  SB_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (need > free_b)
+    return SB_FAIL(AZMI_ERR_OOM, "leaves_per_step = %u on %u trees needs %llu bytes of device memory for the in-flight records and the "
+                   "step's row buffers, %llu are free", k, s->n, need, static_cast<unsigned long long>(free_b));
+  hipError_t e = hipSuccess;
+  auto A = [&](auto*& ptr, size_t cnt) {
+    if (e != hipSuccess) return;
+    void* q = nullptr;
+    const size_t sz = std::max<size_t>(cnt, 1) * sizeof(*ptr);
+    e = hipMalloc(&q, sz);
+    if (e != hipSuccess) return;
+    s->wu_allocs.push_back(q);
+    e = hipMemset(q, 0, sz);
+    ptr = static_cast<std::remove_reference_t<decltype(ptr)>>(q);
+  };
+  SbWuArrays& w = s->wu;
+  A(w.wu.nif, nif_cnt); A(w.wu.ifl_path, E * pm->ep.max_depth); A(w.wu.ifl_plen, E); A(w.wu.ifl_cur, E);
+  A(w.pend, E); A(w.row_of, E); A(w.rows, E); A(w.tree_of, E);
+  A(w.canon, E * s->chw); A(w.v, E * (P + 1)); A(w.pi, E * M); A(w.keys, E);
+  A(s->d_batch_wu, E * s->chw); A(s->d_vrows_wu, E * (P + 1)); A(s->d_pirows_wu, E * M);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (e != hipSuccess) {
+    wu_free(s);
+    return SB_FAIL(AZMI_ERR_OOM, "leaves_per_step = %u: %llu bytes of device memory: %s", k, need, hipGetErrorString(e));
+  }
+  s->k_leaves = k;
+  return AZMI_OK;
 }
 
 int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride, const int32_t* moves, const uint32_t* move_offsets,
@@ -210,6 +312,8 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
   SB_TRY2(up(reinterpret_cast<void**>(&d_offs), move_offsets, (static_cast<size_t>(n) + 1) * 4));
   SB_TRY2(up(reinterpret_cast<void**>(&d_seeds), seeds, static_cast<size_t>(n) * 8));
   SB_TRY2(hipMemsetAsync(pm->ar.ctl, 0, sizeof(Control), st));       // a stopped search does not outlive its positions
+  if (s->k_leaves > 1)     // the in-flight mark of every root (node 0 of its tree); every other node gets its mark cleared when it is created
+    SB_TRY2(hipMemset2DAsync(s->wu.wu.nif, static_cast<size_t>(pm->gi.P) * pm->ep.cap * 4, 0, 4, n, st));
   SB_DISPATCH(pm->game, (k_sb_seed<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds)),
               (k_sb_big_seed<GM><<<n, 64, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds)));
   s->launches += 1;
@@ -231,16 +335,25 @@ int azmi_search_find_leaves(azmi_search* s, void* stream, float** dev_canonical,
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
-  launch_find(s, pm->ep, pm->ar, 0u, st);
-  k_sb_gather<<<s->n, 256, 0, st>>>(s->sb, s->n, pm->ar.canon, s->chw, s->d_batch);
+  const bool wu = s->k_leaves > 1;
+  const uint32_t kk = std::min<uint32_t>(s->k_leaves, s->max_sims - s->sims_done);     // fewer than K left: the remainder only
+  if (wu) {
+    launch_find_wu(s, pm->ep, pm->ar, kk, 0u, 0u, st);
+    SbArrays rows_of_step = s->sb;       // k_sb_gather over the step's kk * N entries
+    rows_of_step.row_of = s->wu.row_of;
+    k_sb_gather<<<s->n * kk, 256, 0, st>>>(rows_of_step, s->n * kk, s->wu.canon, s->chw, s->d_batch_wu);
+  } else {
+    launch_find(s, pm->ep, pm->ar, 0u, st);
+    k_sb_gather<<<s->n, 256, 0, st>>>(s->sb, s->n, pm->ar.canon, s->chw, s->d_batch);
+  }
   s->launches += 1;
   SB_TRY(hipGetLastError());
   uint32_t rows = 0;
   SB_TRY(hipMemcpyAsync(&rows, s->sb.n_rows, 4, hipMemcpyDeviceToHost, st));
   rc = check_device(s, st); if (rc) return rc;
-  s->step_pending = true; s->step_rows = rows;
-  if (dev_canonical) *dev_canonical = s->d_batch;
-  if (dev_tree_index) *dev_tree_index = s->sb.rows;
+  s->step_pending = true; s->step_rows = rows; s->step_k = kk;
+  if (dev_canonical) *dev_canonical = wu ? s->d_batch_wu : s->d_batch;
+  if (dev_tree_index) *dev_tree_index = wu ? s->wu.tree_of : s->sb.rows;
   *n_rows = rows;
   return AZMI_OK;
 }
@@ -250,8 +363,11 @@ int azmi_search_leaves_to_host(azmi_search* s, float* canonical, uint32_t* tree_
   if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "no leaf batch: call find_leaves first");
   SB_TRY(hipSetDevice(s->pm->device));
   hipStream_t st = s->pm->last;
-  if (canonical && s->step_rows) SB_TRY(hipMemcpyAsync(canonical, s->d_batch, static_cast<size_t>(s->step_rows) * s->chw * 4, hipMemcpyDeviceToHost, st));
-  if (tree_index && s->step_rows) SB_TRY(hipMemcpyAsync(tree_index, s->sb.rows, static_cast<size_t>(s->step_rows) * 4, hipMemcpyDeviceToHost, st));
+  const bool wu = s->k_leaves > 1;
+  if (canonical && s->step_rows)
+    SB_TRY(hipMemcpyAsync(canonical, wu ? s->d_batch_wu : s->d_batch, static_cast<size_t>(s->step_rows) * s->chw * 4, hipMemcpyDeviceToHost, st));
+  if (tree_index && s->step_rows)
+    SB_TRY(hipMemcpyAsync(tree_index, wu ? s->wu.tree_of : s->sb.rows, static_cast<size_t>(s->step_rows) * 4, hipMemcpyDeviceToHost, st));
   SB_TRY(hipStreamSynchronize(st));
   return AZMI_OK;
 }
@@ -264,10 +380,13 @@ int azmi_search_process_results(azmi_search* s, const float* dev_v, const float*
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
   // (with no rows the pointers are not read: every pending tree is a terminal leaf already backed up)
-  launch_process(s, pm->ep, pm->ar, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
+  if (s->k_leaves > 1)
+    launch_process_wu(s, pm->ep, pm->ar, s->step_k, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
+  else
+    launch_process(s, pm->ep, pm->ar, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
   SB_TRY(hipGetLastError());
   s->step_pending = false;
-  s->sims_done += 1; s->steps += 1;
+  s->sims_done += s->step_k; s->steps += 1;
   return AZMI_OK;
 }
 
@@ -278,11 +397,13 @@ int azmi_search_process_results_host(azmi_search* s, const float* v, const float
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->last;
+  float* d_v = s->k_leaves > 1 ? s->d_vrows_wu : s->d_vrows;
+  float* d_pi = s->k_leaves > 1 ? s->d_pirows_wu : s->d_pirows;
   if (s->step_rows) {
-    SB_TRY(hipMemcpyAsync(s->d_vrows, v, static_cast<size_t>(s->step_rows) * (pm->gi.P + 1) * 4, hipMemcpyHostToDevice, st));
-    SB_TRY(hipMemcpyAsync(s->d_pirows, pi, static_cast<size_t>(s->step_rows) * pm->gi.M * 4, hipMemcpyHostToDevice, st));
+    SB_TRY(hipMemcpyAsync(d_v, v, static_cast<size_t>(s->step_rows) * (pm->gi.P + 1) * 4, hipMemcpyHostToDevice, st));
+    SB_TRY(hipMemcpyAsync(d_pi, pi, static_cast<size_t>(s->step_rows) * pm->gi.M * 4, hipMemcpyHostToDevice, st));
   }
-  rc = azmi_search_process_results(s, s->d_vrows, s->d_pirows, root_noise_enabled, st);
+  rc = azmi_search_process_results(s, d_v, d_pi, root_noise_enabled, st);
   if (rc) return rc;
   SB_TRY(hipStreamSynchronize(st));     // the host arrays may be reused by the caller
   return AZMI_OK;
@@ -309,6 +430,25 @@ int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t v
   hipStream_t st = pm->pick(stream);
   if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
   const uint32_t rn = root_noise_enabled ? 1u : 0u;
+  if (s->k_leaves > 1) {
+    // visits / K steps of K descents and one of the remainder, enqueued back to back like the K == 1 steps below
+    const EngineArrays aw = wu_rows(s, ar);
+    for (uint32_t left = visits; left;) {
+      const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
+      launch_find_wu(s, ep, ar, kk, net ? 0u : 1u, rn, st);
+      if (net) {
+        rc = azmi_net_forward_rows(net, aw.canon, aw.v, aw.pi, s->wu.rows, s->sb.n_rows, s->n * kk, st);
+        if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
+        s->net_calls += 1;
+        if (ep.cache_on) launch_cache_insert_wu(s, ep, ar, kk, st);
+      }
+      launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
+      left -= kk; s->steps += 1;
+    }
+    SB_TRY(hipGetLastError());
+    s->sims_done += visits;
+    return AZMI_OK;
+  }
   // `visits` step pairs, enqueued back to back: the row count of a step never leaves the device
   for (uint32_t i = 0; i < visits; ++i) {
     launch_find(s, ep, ar, net ? 0u : 1u, st);

@@ -251,6 +251,251 @@ __global__ __launch_bounds__(64) void k_sb_big_process(EngineParams ep, EngineAr
   c.store(kSlotWaitEval);
 }
 
+// ======================= several leaves in flight per tree and step (WU-UCT, leaves_per_step = K > 1) ==========================
+// One step of tree i = K calls of MCTS::find_leaf_batched (mcts.cc:752-784), each seeing the in-flight marks of the ones before
+// it, a back-up at once for every leaf that needs no evaluator (terminal, RANDOM, cache hit), one evaluator call for the rest,
+// then MCTS::process_result_batched (mcts.cc:786-851) for the pending ones in ascending order: play.py:_run_one_batch with the
+// attempt count fixed at K.  Descent k of tree i owns entry k * N + i ("[K][N]-major") of every step-sized array, so that an
+// EngineArrays copy whose canon / v / pi / cache_keys pointers are moved by k * N rows makes emit_leaf, cache_lookup,
+// process_result and k_cache_insert, which address rows by slot, work on that entry.  The VISIBLE row order is ascending tree,
+// then descent: k_sb_compact_wu numbers the pending entries in that order.
+struct SbWuArrays {
+  WuArrays wu;         // nif [N * P * cap]; in-flight records [K * N]: ifl_path[max_depth], ifl_plen, ifl_cur
+  uint8_t* pend;       // [K * N] SbPend of descent k of tree i (kPendRow or kPendNone: everything else is backed up by the find kernel)
+  uint32_t* row_of;    // [K * N] compacted row of the entry (kNoRow = none)
+  uint32_t* rows;      // [K * N] entry of compacted row r: the net's row list
+  uint32_t* tree_of;   // [K * N] tree of compacted row r (ascending, with repeats)
+  float* canon;        // [K * N, C, H, W]
+  float* v;            // [K * N, P + 1]
+  float* pi;           // [K * N, M]
+  uint64_t* keys;      // [K * N] cache keys of the evaluated entries (0 = none)
+};
+
+// `al` is the kernel's own copy of the engine arrays that the slot context reads through: entry (k, slot) becomes "the slot's row"
+__device__ __forceinline__ void sb_wu_point(EngineArrays& al, const SbWuArrays& w, size_t row0, uint32_t chw, uint32_t nv, uint32_t np) {
+  al.canon = w.canon + row0 * chw; al.v = w.v + row0 * nv; al.pi = w.pi + row0 * np; al.cache_keys = w.keys + row0;
+}
+
+// `kk` <= K descents of every live tree (the last step of a search whose visit count is no multiple of K runs the remainder)
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_find_wu(EngineParams ep, EngineArrays ar, SbArrays sb, SbWuArrays w, uint32_t n, uint32_t kk,
+                                                    uint32_t eval_random, uint32_t root_noise) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) {
+    if (lane == 0) for (uint32_t k = 0; k < kk; ++k) { w.pend[k * n + slot] = kPendNone; w.keys[k * n + slot] = 0; }
+    return;
+  }
+  EngineArrays al = ar;
+  SlotCtx<GM> c(ep, al, slot, lane);
+  c.load();
+  uint32_t* nif = w.wu.nif + c.tree_base(0);
+  const uint32_t* path = ar.path + static_cast<size_t>(slot) * ep.max_depth;
+  for (uint32_t k = 0; k < kk; ++k) {
+    const uint32_t e = k * n + slot;
+    sb_wu_point(al, w, static_cast<size_t>(k) * n, GM::CANON, GM::P + 1, GM::M);
+    typename GM::State leaf;
+    uint32_t term = 0;
+    uint8_t pend = kPendNone;
+    uint64_t ins_key = 0;
+    bool now = false, from_net = true;      // back up at once / with the (v, pi) rows of the entry
+    if (!c.find_leaf_wu(0, leaf, term, nif)) {
+      // the tree stops: nothing of this step is backed up (reset() clears the root's mark, new nodes get theirs cleared)
+      if (lane == 0) { sb.status[slot] = -2; for (uint32_t j = 0; j < kk; ++j) { w.pend[j * n + slot] = kPendNone; w.keys[j * n + slot] = 0; } }
+      break;
+    }
+    if (term != 0) {
+      now = true;
+      if (lane == 0) sb.n_term[slot] += 1;
+    } else if (eval_random) {
+      now = true; from_net = false;
+    } else {
+      const uint64_t key = GM::key(leaf);
+      float hit_pi = 0.0f, hit_v = 0.0f;
+      if (ep.cache_on && c.cache_lookup(key, 0, hit_pi, hit_v)) now = true;
+      else {
+        c.emit_leaf(leaf, key);
+        if (lane == 0) ar.c_evals[slot] += 1;
+        ins_key = cache_key(key);
+        pend = kPendRow;
+      }
+    }
+    if (now) {      // process_result_batched(k, ...) right behind its find_leaf_batched: the record would be read back unchanged
+      if (lane == 0) { --nif[c.cur]; for (uint32_t i = 0; i < c.plen; ++i) --nif[path[i]]; }
+      c.sync_lanes();
+      c.process_result(0, from_net, term == 0 && root_noise != 0);
+    } else {
+      uint32_t* rec = w.wu.ifl_path + static_cast<size_t>(e) * ep.max_depth;
+      for (uint32_t i = lane; i < c.plen; i += G) rec[i] = path[i];
+      if (lane == 0) { w.wu.ifl_plen[e] = c.plen; w.wu.ifl_cur[e] = c.cur; }
+    }
+    if (lane == 0) { w.pend[e] = pend; w.keys[e] = ins_key; }
+  }
+  c.store(kSlotWaitEval);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_find_wu(EngineParams ep, EngineArrays ar, SbArrays sb, SbWuArrays w, uint32_t n, uint32_t kk,
+                                                       uint32_t eval_random, uint32_t root_noise) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) {
+    if (lane == 0) for (uint32_t k = 0; k < kk; ++k) { w.pend[k * n + slot] = kPendNone; w.keys[k * n + slot] = 0; }
+    return;
+  }
+  EngineArrays al = ar;
+  BigSlot<GM> c(ep, al, sm, slot, lane);
+  c.load();
+  uint32_t* nif = w.wu.nif + c.tree_base(0);
+  const uint32_t* path = ar.path + static_cast<size_t>(slot) * ep.max_depth;
+  for (uint32_t k = 0; k < kk; ++k) {
+    const uint32_t e = k * n + slot;
+    sb_wu_point(al, w, static_cast<size_t>(k) * n, GM::CANON, GM::P + 1, GM::M);
+    typename GM::State leaf;
+    uint32_t term = 0;
+    uint8_t pend = kPendNone;
+    uint64_t ins_key = 0;
+    bool now = false, from_net = true;
+    if (!c.find_leaf_wu(0, leaf, term, nif)) {
+      if (lane == 0) { sb.status[slot] = -2; for (uint32_t j = 0; j < kk; ++j) { w.pend[j * n + slot] = kPendNone; w.keys[j * n + slot] = 0; } }
+      break;
+    }
+    if (term != 0) {
+      now = true;
+      if (lane == 0) sb.n_term[slot] += 1;
+    } else if (eval_random) {
+      now = true; from_net = false;
+    } else {
+      const uint64_t key = c.emit_leaf(leaf);
+      if (ep.cache_on && c.cache_lookup(key, 0)) now = true;
+      else {
+        if (lane == 0) ar.c_evals[slot] += 1;
+        ins_key = cache_key(key);
+        pend = kPendRow;
+      }
+    }
+    if (now) {
+      if (lane == 0) { --nif[c.cur]; for (uint32_t i = 0; i < c.plen; ++i) --nif[path[i]]; }
+      c.sync();
+      c.process_result(0, from_net, term == 0 && root_noise != 0);
+    } else {
+      uint32_t* rec = w.wu.ifl_path + static_cast<size_t>(e) * ep.max_depth;
+      for (uint32_t i = lane; i < c.plen; i += 64) rec[i] = path[i];
+      if (lane == 0) { w.wu.ifl_plen[e] = c.plen; w.wu.ifl_cur[e] = c.cur; }
+    }
+    if (lane == 0) { w.pend[e] = pend; w.keys[e] = ins_key; }
+  }
+  c.sync();
+  c.store(kSlotWaitEval);
+}
+
+// the kPendRow entries of the step in ascending (tree, descent) order; the row count stays on the device
+__global__ __launch_bounds__(1024) void k_sb_compact_wu(SbArrays sb, SbWuArrays w, uint32_t n, uint32_t kk) {
+  __shared__ uint32_t s_sum[1024];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t total = n * kk;
+  const uint32_t per = (total + 1023u) / 1024u;
+  const uint32_t lo = min(total, tid * per), hi = min(total, lo + per);
+  uint32_t cnt = 0;
+  for (uint32_t j = lo; j < hi; ++j) cnt += w.pend[(j % kk) * n + j / kk] == kPendRow ? 1u : 0u;
+  s_sum[tid] = cnt;
+  __syncthreads();
+  for (uint32_t off = 1; off < 1024u; off <<= 1) {     // inclusive scan
+    const uint32_t add = tid >= off ? s_sum[tid - off] : 0u;
+    __syncthreads();
+    s_sum[tid] += add;
+    __syncthreads();
+  }
+  uint32_t row = s_sum[tid] - cnt;
+  for (uint32_t j = lo; j < hi; ++j) {
+    const uint32_t tree = j / kk, e = (j % kk) * n + tree;
+    if (w.pend[e] == kPendRow) { w.row_of[e] = row; w.rows[row] = e; w.tree_of[row] = tree; ++row; }
+    else w.row_of[e] = kNoRow;
+  }
+  if (tid == 1023u) *sb.n_rows = s_sum[1023];
+}
+
+// process_result_batched for the pending descents of every tree, ascending.  v_rows / pi_rows: the evaluator's answers by
+// COMPACTED row (step API), or NULL when the net wrote them to the entries' own rows.
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_process_wu(EngineParams ep, EngineArrays ar, SbWuArrays w, uint32_t n, uint32_t kk, uint32_t root_noise,
+                                                       const float* v_rows, const float* pi_rows) {
+  constexpr int G = GM::GROUP;
+  constexpr uint32_t P = GM::P, M = GM::M;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n) return;
+  uint32_t k = 0;
+  while (k < kk && w.pend[k * n + slot] != kPendRow) ++k;
+  if (k == kk) return;
+  EngineArrays al = ar;
+  SlotCtx<GM> c(ep, al, slot, lane);
+  c.load();
+  uint32_t* nif = w.wu.nif + c.tree_base(0);
+  uint32_t* path = ar.path + static_cast<size_t>(slot) * ep.max_depth;
+  for (; k < kk; ++k) {
+    const uint32_t e = k * n + slot;
+    if (w.pend[e] != kPendRow) continue;
+    sb_wu_point(al, w, static_cast<size_t>(k) * n, GM::CANON, P + 1, M);
+    if (v_rows) {
+      const uint32_t r = w.row_of[e];
+      if (lane <= P) al.v[static_cast<size_t>(slot) * (P + 1) + lane] = v_rows[static_cast<size_t>(r) * (P + 1) + lane];
+      if (lane < M) al.pi[static_cast<size_t>(slot) * M + lane] = pi_rows[static_cast<size_t>(r) * M + lane];
+    }
+    c.cur = w.wu.ifl_cur[e]; c.plen = w.wu.ifl_plen[e];
+    if (lane == 0) {
+      const uint32_t* rec = w.wu.ifl_path + static_cast<size_t>(e) * ep.max_depth;
+      --nif[c.cur];
+      for (uint32_t i = 0; i < c.plen; ++i) { path[i] = rec[i]; --nif[rec[i]]; }
+      w.pend[e] = kPendNone;
+    }
+    c.sync_lanes();
+    c.process_result(0, true, root_noise != 0);
+  }
+  c.store(kSlotWaitEval);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_process_wu(EngineParams ep, EngineArrays ar, SbWuArrays w, uint32_t n, uint32_t kk,
+                                                          uint32_t root_noise, const float* v_rows, const float* pi_rows) {
+  __shared__ BigScratch<GM> sm;
+  constexpr uint32_t P = GM::P, M = GM::M;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n) return;
+  uint32_t k = 0;
+  while (k < kk && w.pend[k * n + slot] != kPendRow) ++k;
+  if (k == kk) return;
+  EngineArrays al = ar;
+  BigSlot<GM> c(ep, al, sm, slot, lane);
+  c.load();
+  uint32_t* nif = w.wu.nif + c.tree_base(0);
+  uint32_t* path = ar.path + static_cast<size_t>(slot) * ep.max_depth;
+  for (; k < kk; ++k) {
+    const uint32_t e = k * n + slot;
+    if (w.pend[e] != kPendRow) continue;
+    sb_wu_point(al, w, static_cast<size_t>(k) * n, GM::CANON, P + 1, M);
+    if (v_rows) {
+      const uint32_t r = w.row_of[e];
+      if (lane <= P) al.v[static_cast<size_t>(slot) * (P + 1) + lane] = v_rows[static_cast<size_t>(r) * (P + 1) + lane];
+      for (uint32_t m = lane; m < M; m += 64) al.pi[static_cast<size_t>(slot) * M + m] = pi_rows[static_cast<size_t>(r) * M + m];
+    }
+    c.cur = w.wu.ifl_cur[e]; c.plen = w.wu.ifl_plen[e];
+    if (lane == 0) {
+      const uint32_t* rec = w.wu.ifl_path + static_cast<size_t>(e) * ep.max_depth;
+      --nif[c.cur];
+      for (uint32_t i = 0; i < c.plen; ++i) { path[i] = rec[i]; --nif[rec[i]]; }
+      w.pend[e] = kPendNone;
+    }
+    c.sync();
+    c.process_result(0, true, root_noise != 0);
+  }
+  c.sync();
+  c.store(kSlotWaitEval);
+}
+
 // ---- read-out: one launch for all trees; tree i writes out_f + i * stride_f / out_u + i * stride_u ----------------------------
 template <class GM>
 __global__ __launch_bounds__(256) void k_sb_query(EngineParams ep, EngineArrays ar, uint32_t n, uint32_t kind, float temp, uint32_t arg,

@@ -375,7 +375,20 @@ int azmi_mcts_query(azmi_mcts* m, uint32_t kind, float temp, uint32_t arg, const
  *            [n_trees, max(M, 64) + 64], row i laid out as azmi_mcts_query lays out its one row (either may be NULL)
  *   sync     waits for everything enqueued and reports a device-side error
  *   stats    out[6] = kernel launches enqueued by the object since creation (the net's own launches not included), net calls,
- *            steps, simulations / leaves given to the evaluator / terminal leaves since the last reset (summed over the trees) */
+ *            steps, simulations / leaves given to the evaluator / terminal leaves since the last reset (summed over the trees)
+ *   set_leaves_per_step   k in [1, 64] leaves of EVERY tree in flight per step (WU-UCT; 1, the default, is everything above
+ *            unchanged).  With k > 1 a step of tree i is k calls of azmi_mcts_find_leaf_batched, each seeing the in-flight marks
+ *            of the ones before it; a leaf that needs no evaluator (terminal, dumb_eval, cache hit) gets its
+ *            azmi_mcts_process_result_batched at once, the others become rows of ONE evaluator call and are backed up in
+ *            ascending order behind it, then reset_batch: play.py:_run_one_batch with the attempt count fixed at k (the
+ *            reference goes on "until k misses or 2k attempts", which a lock-step batch cannot budget).  Tree i stays bit for
+ *            bit the stand-alone azmi_mcts driven by those calls.  Rows are ordered by tree, then by descent: *dev_tree_index
+ *            repeats a tree, and [*n_rows] may reach n_trees * k.  run(visits) is visits / k steps and one of visits % k
+ *            descents; max_simulations and `simulations` count descents, `steps` counts steps; a find_leaves with fewer than k
+ *            descents left runs those.  Two in-flight leaves on one position both miss the cache and are both evaluated.
+ *            Legal before the first reset and after a reset, before anything is searched; (re)allocates the in-flight records
+ *            and step-sized row buffers and fails with the byte count when they do not fit.  gumbel_enabled with k > 1 is
+ *            AZMI_ERR_INVALID: the batched descent is plain PUCT (mcts.cc:752-784) */
 typedef struct azmi_search azmi_search;
 int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, int device, azmi_search** out);
 void azmi_search_destroy(azmi_search* s);
@@ -390,6 +403,7 @@ int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t v
 int azmi_search_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u);
 int azmi_search_sync(azmi_search* s);
 int azmi_search_stats(azmi_search* s, uint64_t out[6]);
+int azmi_search_set_leaves_per_step(azmi_search* s, uint32_t k);
 
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
  *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------

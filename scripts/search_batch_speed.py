@@ -7,7 +7,9 @@
 for Connect4 (N positions x VISITS, the 6b64c bf16 net) and Tawlbwrdd (the configs/tawlbwrdd.yaml net).  Warm-up first, then
 the two versions alternate in one process; every time is taken around a device synchronise; median and spread are printed.
   python scripts/search_batch_speed.py [--game connect4|tawlbwrdd|both] [--n N] [--visits V] [--reps R] [--loop-reps L]
-One JSON line per game on stdout."""
+                                       [--leaves-per-step K]
+One JSON line per game on stdout.  --leaves-per-step K > 1 times (a) with K leaves of every tree in flight per step (WU-UCT: a
+different search, so (b) is not run beside it); every line carries the steps, the time per step and the rows per net call."""
 import argparse
 import json
 import os
@@ -47,6 +49,7 @@ def run_batch(az, mb, states, seeds, visits, net):
     mb.synchronize()
     dt = time.perf_counter() - t0
     l1 = mb.stats()
+    run_batch.last = dict(steps=l1["steps"] - l0["steps"], evaluator_leaves=l1["evaluator_leaves"])
     return dt, l1["launches"] - l0["launches"], l1["net_calls"] - l0["net_calls"], mb.counts()
 
 
@@ -81,7 +84,7 @@ def run_loop(az, Game, states, seeds, visits, net, cpuct):
     return dt, calls, np.stack([m.counts() for m in trees])
 
 
-def measure(az, name, n, visits, reps, loop_reps):
+def measure(az, name, n, visits, reps, loop_reps, leaves_per_step=1):
     from alphazero import torch_net
     Game, spec, plies = {"connect4": (az.Connect4GS, torch_net.connect4_spec(), 12),
                          "tawlbwrdd": (az.TawlbwrddGS, torch_net.tawlbwrdd_spec(), 6)}[name]
@@ -89,7 +92,9 @@ def measure(az, name, n, visits, reps, loop_reps):
     rng = np.random.default_rng(1)
     states = positions(az, Game, n, rng, plies)
     seeds = [1 + i for i in range(n)]
-    mb = az.MCTSBatch(Game, n, 1.25, max_simulations=visits, seeds=seeds)
+    mb = az.MCTSBatch(Game, n, 1.25, max_simulations=visits, seeds=seeds, leaves_per_step=leaves_per_step)
+    if leaves_per_step > 1:
+        loop_reps = 0
     run_batch(az, mb, states, seeds, visits, net)                  # warm-up (code objects, the net's scratch)
     a, b, launches, net_calls, loop_calls, same = [], [], 0, 0, 0, True
     order = ["a", "b"] * loop_reps + ["a"] * max(0, reps - loop_reps)
@@ -103,7 +108,10 @@ def measure(az, name, n, visits, reps, loop_reps):
             same = same and bool(np.array_equal(counts_a, counts_b))
     rec = dict(game=name, positions=n, visits=visits,
                batch_s=dict(median=statistics.median(a), min=min(a), max=max(a), runs=len(a)),
-               batch_launches=launches, batch_net_calls=net_calls)
+               batch_launches=launches, batch_net_calls=net_calls, leaves_per_step=leaves_per_step, steps=run_batch.last["steps"],
+               step_us=dict(median=1e6 * statistics.median(a) / run_batch.last["steps"], min=1e6 * min(a) / run_batch.last["steps"],
+                            max=1e6 * max(a) / run_batch.last["steps"]),
+               rows_per_net_call=run_batch.last["evaluator_leaves"] / max(1, net_calls))
     if b:
         rec.update(loop_s=dict(median=statistics.median(b), min=min(b), max=max(b), runs=len(b)), loop_device_calls=loop_calls,
                    ratio=statistics.median(b) / statistics.median(a), same_counts=same)
@@ -117,10 +125,11 @@ def main():
     ap.add_argument("--visits", type=int, default=120)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop-reps", type=int, default=2, help="runs of the stand-alone-object loop (minutes each at full size; 0 = skip)")
+    ap.add_argument("--leaves-per-step", type=int, default=1, help="K leaves of every tree in flight per step (1 = the plain search)")
     args = ap.parse_args()
     import alphazero as az
     for name in (["connect4", "tawlbwrdd"] if args.game == "both" else [args.game]):
-        measure(az, name, args.n or (1024 if name == "connect4" else 256), args.visits, args.reps, args.loop_reps)
+        measure(az, name, args.n or (1024 if name == "connect4" else 256), args.visits, args.reps, args.loop_reps, args.leaves_per_step)
 
 
 if __name__ == "__main__":
