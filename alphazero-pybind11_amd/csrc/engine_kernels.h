@@ -147,19 +147,39 @@ struct SlotCtx {
   __device__ __forceinline__ static uint32_t dpp_u(uint32_t v) {
     return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, true));
   }
+  // Lane SRC of the 8-lane group to all eight lanes with two DPP moves and a select: quad_perm [s,s,s,s] fills SRC's own quad
+  // (and hands the other quad its lane s, which is not wanted), row_half_mirror (lane i <-> 7 - i) carries the filled quad
+  // over to the other one.  No LDS round trip, unlike bcast; the source lane is a compile-time constant.
+  template <int SRC, class T>
+  __device__ __forceinline__ T bcast_lane(T v) const {
+    static_assert(G == 8 && SRC >= 0 && SRC < 8 && sizeof(T) == 4, "8-lane groups, 32-bit values");
+    const int q = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), (SRC & 3) * 0x55, 0xF, 0xF, true);
+    const int m = __builtin_amdgcn_update_dpp(0, q, 0x141, 0xF, 0xF, true);
+    const bool upper = (lane & 4u) != 0u;
+    return __builtin_bit_cast(T, (upper == (SRC >= 4)) ? q : m);
+  }
+  // ---- boolean reductions over the group: the group's byte of the wavefront's ballot.  (Every lane of a group is active
+  // wherever group code runs - control flow is uniform inside a group -, so the byte is whole; other groups' bytes may not be.)
+  __device__ __forceinline__ uint32_t group_ballot(bool pred) const {
+    return static_cast<uint32_t>(__ballot(pred) >> (__lane_id() & 56u)) & 0xFFu;
+  }
+  __device__ __forceinline__ bool group_all(bool pred) const { static_assert(G == 8, "8-lane groups"); return group_ballot(pred) == 0xFFu; }
+  __device__ __forceinline__ bool group_any(bool pred) const { static_assert(G == 8, "8-lane groups"); return group_ballot(pred) != 0u; }
   // x_0 + x_1 + ... + x_7 in lane order over the 8-lane group; lanes past the data must hold +0.0f.  Lane j takes lane
-  // j-1's running sum (row_shr:1) at step j, so the additions happen in exactly the sequential order.
-  __device__ __forceinline__ float seqsum8(float x) const {
+  // j-1's running sum (row_shr:1) at step j, so the additions happen in exactly the sequential order.  The sum ends in
+  // lane 7: seqsum8_last leaves it there (every other lane holds a partial sum), seqsum8 hands it to all eight lanes.
+  __device__ __forceinline__ float seqsum8_last(float x) const {
     static_assert(G == 8, "8-lane groups");
     const uint32_t li = lane & 7u;
     float run = x;
 #pragma unroll
     for (uint32_t j = 1; j < 8; ++j) {
       const float t = dpp_f<0x111>(run);          // row_shr:1
-      if (li == j) run = t + x;
+      run = (li == j) ? t + x : run;
     }
-    return bcast(run, 7);
+    return run;
   }
+  __device__ __forceinline__ float seqsum8(float x) const { return bcast_lane<7>(seqsum8_last(x)); }
   __device__ __forceinline__ float seqsum(float x, uint32_t n) const {  // x_0 + x_1 + ... in lane order
     float s = 0.0f;
     for (uint32_t i = 0; i < n; ++i) s += bcast(x, i);
@@ -463,26 +483,36 @@ struct SlotCtx {
   // (`if_l` = Node::n_in_flight of the child, `n_parent` includes the parent's: only the WU-UCT batched API has them non-zero)
   __device__ __forceinline__ uint32_t select_child(uint32_t k, uint32_t n_l, float q_l, float p_l, float v_parent,
                                    uint32_t n_parent, float fpu_reduction, uint32_t if_l = 0) const {
+    return select_among(k, n_l, q_l, p_l, v_parent, select_parent(n_parent), ep.cpuct, fpu_reduction, if_l);
+  }
+  // The parent's share of the select: it does not depend on the child records, so a descent that has just asked for them
+  // computes it while they are on their way and hands it to select_among.
+  __device__ __forceinline__ static float select_parent(uint32_t n_parent) { return sqrtf(static_cast<float>(n_parent)); }
+  __device__ __forceinline__ uint32_t select_among(uint32_t k, uint32_t n_l, float q_l, float p_l, float v_parent,
+                                   float sqrt_n, float cpuct, float fpu_reduction, uint32_t if_l = 0) const {
     // seen_policy: the priors of the visited children added in child order; an unvisited child contributes +0.0f, which
     // leaves the running sum unchanged, so the masked in-order sum is the reference's
     const float seen = seqsum8((lane < k && n_l > 0) ? p_l : 0.0f);
     const float fpu_value = v_parent - fpu_reduction * sqrtf(seen);
-    const float sqrt_n = sqrtf(static_cast<float>(n_parent));
-    float u = (n_l == 0 ? fpu_value : q_l) + ep.cpuct * p_l * sqrt_n / static_cast<float>(n_l + if_l + 1);
+    float u = (n_l == 0 ? fpu_value : q_l) + cpuct * p_l * sqrt_n / static_cast<float>(n_l + if_l + 1);
     // a strict `>` scan never replaces the incumbent with a NaN and never leaves a NaN at
     // index 0: map NaN to +inf at lane 0 and -inf elsewhere, then reduce (score, index) keys: largest score, smallest
     // index among equals — an order-free reduction, done with DPP moves (xor 1, xor 2 inside quads, then the half-row
     // mirror to meet the other quad)
-    if (u != u) u = (lane == 0) ? __builtin_inff() : -__builtin_inff();
-    if (lane >= k) u = -__builtin_inff();
+    // (every step below is a select, not a branch: compares and v_cndmask, no exec-mask region on the descent's chain)
+    u = (u != u) ? ((lane == 0) ? __builtin_inff() : -__builtin_inff()) : u;
+    u = (lane >= k) ? -__builtin_inff() : u;
     uint32_t idx = lane < k ? lane : 0xFFFFu;
     {
       float ou = dpp_f<0xB1>(u); uint32_t oi = dpp_u<0xB1>(idx);          // quad_perm [1,0,3,2]
-      if (ou > u || (ou == u && oi < idx)) { u = ou; idx = oi; }
+      bool take = (ou > u) | ((ou == u) & (oi < idx));
+      u = take ? ou : u; idx = take ? oi : idx;
       ou = dpp_f<0x4E>(u); oi = dpp_u<0x4E>(idx);                           // quad_perm [2,3,0,1]
-      if (ou > u || (ou == u && oi < idx)) { u = ou; idx = oi; }
+      take = (ou > u) | ((ou == u) & (oi < idx));
+      u = take ? ou : u; idx = take ? oi : idx;
       ou = dpp_f<0x141>(u); oi = dpp_u<0x141>(idx);                         // row_half_mirror: lane i <-> 7 - i
-      if (ou > u || (ou == u && oi < idx)) { u = ou; idx = oi; }
+      take = (ou > u) | ((ou == u) & (oi < idx));
+      u = take ? ou : u; idx = take ? oi : idx;
     }
     return idx;
   }
@@ -1442,6 +1472,10 @@ __global__ __launch_bounds__(256, 2) void k_sim(EngineParams ep, EngineArrays ar
   uint32_t inline_sims = 0, insert_key_set = 0, sims_done = 0;
   bool rec_ok = true;
   c.trace(101);
+  // (read once: the descent's level loop would otherwise fetch them from the kernel's arguments, a scalar load and its wait
+  // in the middle of every level's divide chain)
+  float cpuct = ep.cpuct, fpu_red = ep.fpu_reduction;
+  asm volatile("" : "+s"(cpuct), "+s"(fpu_red));
   for (;;) {
     if (AZMI_SEL(c.t_depth, cp) + 1 >= goal || c.cur == root || !rec_ok) {   // (never true in the first pass: checked above)
       if (ep.cache_on && lane == 0) ar.cache_keys[slot] = 0;
@@ -1458,8 +1492,7 @@ __global__ __launch_bounds__(256, 2) void k_sim(EngineParams ep, EngineArrays ar
       } else {
         float p = 0.0f;
         if (from_net) {
-#pragma unroll
-          for (int i = 0; i <= P; ++i) val[i] = c.bcast(reg_v, i);
+          val[0] = c.template bcast_lane<0>(reg_v); val[1] = c.template bcast_lane<1>(reg_v); val[2] = c.template bcast_lane<2>(reg_v);
           p = c.bcast(reg_pi, static_cast<int>(lf_mv));
           if (lane >= lf_k) p = 0.0f;
         } else {                  // dumb_eval: uniform over legal moves, u8 sum wraps (game_state.h:160-173)
@@ -1503,32 +1536,43 @@ __global__ __launch_bounds__(256, 2) void k_sim(EngineParams ep, EngineArrays ar
     while (n > 0 && meta_term(meta) == 0) {
       if (plen >= ep.max_depth) { c.raise(8u); if (ep.cache_on && lane == 0) ar.cache_keys[slot] = 0; c.store(kSlotDone); return; }
       if (lane == 0) path[plen] = cur;
-      const uint32_t k = meta_nch(meta), c0 = meta_ch0(meta);
+      uint32_t k = meta_nch(meta); const uint32_t c0 = meta_ch0(meta);
       if (k == 0) { c.raise(8u); if (ep.cache_on && lane == 0) ar.cache_keys[slot] = 0; c.store(kSlotDone); return; }
-      uint32_t n_l = 0; float q_l = 0.0f, p_l = 0.0f, d_l = 0.0f, v_l = 0.0f; uint64_t m_l = 0;
-      if (cur == fl_node) {                 // the children of the leaf evaluated a moment ago: all in registers
-        if (lane < k) { p_l = fl_pr; m_l = meta_pack(0, 0, fl_mv, 0, 0); }
-      } else {
-        if (lane < k) {
-          const NodeRec* cr = ar.nodes + tb + c0 + lane;
-          n_l = cr->n; q_l = cr->q; p_l = cr->pr; d_l = cr->d; v_l = cr->v; m_l = cr->meta;
-        }
+      // the node the last backup updated at this level: asked for here, with the child records, and used twice below (the patch
+      // and the prefix test) - one permute and no round trip of its own behind the winner's
+      const uint32_t t_node = c.bcast(fw_node, static_cast<int>(plen & 7u));
+      // Every lane asks for a child record (the lanes past the children for the last child's, and a group whose children are all
+      // in registers - the leaf evaluated a moment ago - for records it will not use): the loads stand in no exec-mask region, so
+      // nothing has to wait for them where they are issued, and the parent's share of the select runs while they are on their way.
+      const bool in_regs = cur == fl_node;
+      const NodeRec* const cr = ar.nodes + tb + c0 + (lane < k ? lane : k - 1u);
+      uint32_t n_l = cr->n; float q_l = cr->q, p_l = cr->pr, d_l = cr->d, v_l = cr->v; uint64_t m_l = cr->meta;
+      float sqrt_n = SlotCtx<GM>::select_parent(n);
+      // (the selects below read k as this statement leaves it, so they - and the wait for the records in front of them - stay
+      // behind the square root instead of being scheduled ahead of it)
+      asm volatile("" : "+v"(sqrt_n), "+v"(k));
+      {
+        const bool have = lane < k, mem = have && !in_regs;
+        n_l = mem ? n_l : 0u; q_l = mem ? q_l : 0.0f; d_l = mem ? d_l : 0.0f; v_l = mem ? v_l : 0.0f;
+        p_l = mem ? p_l : have ? fl_pr : 0.0f;
+        m_l = mem ? m_l : have ? meta_pack(0, 0, fl_mv, 0, 0) : 0ull;
+      }
+      if (!in_regs) {
         if (prefix && plen < fw_plen && plen < 8u) {   // one child of this node was updated by the last backup
-          const uint32_t t_node = c.bcast(fw_node, static_cast<int>(plen));
           const uint32_t t_n = c.bcast(fw_n, static_cast<int>(plen));
           const float t_q = c.bcast(fw_q, static_cast<int>(plen)), t_d = c.bcast(fw_d, static_cast<int>(plen)), t_v = c.bcast(fw_v, static_cast<int>(plen));
           if (c0 + lane == t_node) { n_l = t_n; q_l = t_q; d_l = t_d; v_l = t_v; if (t_node == fl_node) m_l = fl_meta; }
         }
       }
-      const float fpu = (cur == root) ? fpu_root : ep.fpu_reduction;
-      const uint32_t best = c.select_child(k, n_l, q_l, p_l, v_cur, n, fpu);
+      const float fpu = (cur == root) ? fpu_root : fpu_red;
+      const uint32_t best = c.select_among(k, n_l, q_l, p_l, v_cur, sqrt_n, cpuct, fpu);
       const uint32_t nxt = c0 + best;
       const uint32_t s_n = c.bcast(n_l, static_cast<int>(best));
       const float s_q = c.bcast(q_l, static_cast<int>(best)), s_d = c.bcast(d_l, static_cast<int>(best)), s_v = c.bcast(v_l, static_cast<int>(best));
       const uint64_t s_m = c.bcast(m_l, static_cast<int>(best));
       if (plen < 8u) {
         if (lane == plen) { lv_node = nxt; lv_n = s_n; lv_q = s_q; lv_d = s_d; lv_v = s_v; lv_pp = meta_player(meta); }
-        prefix = prefix && plen < fw_plen && nxt == c.bcast(fw_node, static_cast<int>(plen));
+        prefix = prefix && plen < fw_plen && nxt == t_node;
       } else {
         prefix = false;
       }

@@ -420,11 +420,8 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
           }
           const bool ok = (lane >= static_cast<uint32_t>(GM::M) || static_cast<uint32_t>(g0 >> 32) == seq) &&
                           (lane > static_cast<uint32_t>(P) || static_cast<uint32_t>(g1 >> 32) == seq);
-          // (all eight lanes of the group agree through a group-wide AND of ok)
-          uint32_t okg = ok ? 1u : 0u;
-          okg &= c.bcast(okg, 0) & c.bcast(okg, 1) & c.bcast(okg, 2) & c.bcast(okg, 3) & c.bcast(okg, 4) & c.bcast(okg, 5) & c.bcast(okg, 6);
-          okg = c.bcast(okg, 0);
-          if (okg) break;
+          // (all eight lanes of the group agree: the group's byte of the wavefront's ballot, no LDS traffic)
+          if (c.group_all(ok)) break;
           if (wall_clock64() - t_start > pa.cap_ticks) {
             if (lane == 0 && atomicAdd(&pc->dbg[0], 1u) == 0u) { pc->dbg[1] = slot; pc->dbg[2] = seq; pc->dbg[3] = c.flags; pc->dbg[4] = static_cast<uint32_t>(g1 >> 32); pc->dbg[5] = static_cast<uint32_t>(g0 >> 32); }
             if (lane == 0) atomicOr(&pc->err, static_cast<uint32_t>(kPipeErrTimeout));
@@ -473,6 +470,10 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
     bool listed = false;
     if (st == kGrpReady) {
       uint32_t inline_sims = 0;
+      // (read once per pass: the level loop would otherwise fetch them from the kernel's arguments, a scalar load and its wait - which
+      // is also a wait for every LDS permute in flight - in the middle of each level's divide chain)
+      float cpuct = ep.cpuct, fpu_red = ep.fpu_reduction;
+      asm volatile("" : "+s"(cpuct), "+s"(fpu_red));
       for (;;) {
         if (AZMI_SEL(c.t_depth, cp) + 1 >= goal || c.cur == root || (GUM && gum_defer)) {
           // the next backup completes the search (a move follows) or the evaluated leaf is the root (temperature, noise): the move step's
@@ -500,8 +501,7 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
           } else {
             float p = 0.0f;
             if (from_net) {
-#pragma unroll
-              for (int i = 0; i <= P; ++i) val[i] = c.bcast(reg_v, i);
+              val[0] = c.template bcast_lane<0>(reg_v); val[1] = c.template bcast_lane<1>(reg_v); val[2] = c.template bcast_lane<2>(reg_v);
               p = c.bcast(reg_pi, static_cast<int>(lf_mv));
               if (lane >= lf_k) p = 0.0f;
             } else {                  // dumb_eval: uniform over legal moves, u8 sum wraps (game_state.h:160-173)
@@ -545,31 +545,42 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
         while (n > 0 && meta_term(meta) == 0) {
           if (plen >= ep.max_depth) { failed = true; break; }
           if (lane == 0) path[plen] = cur;
-          const uint32_t k = meta_nch(meta), c0 = meta_ch0(meta);
+          uint32_t k = meta_nch(meta); const uint32_t c0 = meta_ch0(meta);
           if (k == 0) { failed = true; break; }
-          uint32_t n_l = 0; float q_l = 0.0f, p_l = 0.0f, d_l = 0.0f, v_l = 0.0f; uint64_t m_l = 0;
-          if (cur == fl_node) {                 // the children of the leaf evaluated a moment ago: all in registers
-            if (lane < k) { p_l = fl_pr; m_l = meta_pack(0, 0, fl_mv, 0, 0); }
-          } else {
-            if (lane < k) {
-              const NodeRec* cr = ar.nodes + tb + c0 + lane;
-              n_l = cr->n; q_l = cr->q; p_l = cr->pr; d_l = cr->d; v_l = cr->v; m_l = cr->meta;
-            }
+          // the node the last backup updated at this level: asked for here, with the child records, and used twice below (the patch
+          // and the prefix test) - one permute and no round trip of its own behind the winner's
+          const uint32_t t_node = c.bcast(fw_node, static_cast<int>(plen & 7u));
+          // Every lane asks for a child record (the lanes past the children for the last child's, and a group whose children are all
+          // in registers - the leaf evaluated a moment ago - for records it will not use): the loads stand in no exec-mask region, so
+          // nothing has to wait for them where they are issued, and the parent's share of the select runs while they are on their way.
+          const bool in_regs = cur == fl_node;
+          const NodeRec* const cr = ar.nodes + tb + c0 + (lane < k ? lane : k - 1u);
+          uint32_t n_l = cr->n; float q_l = cr->q, p_l = cr->pr, d_l = cr->d, v_l = cr->v; uint64_t m_l = cr->meta;
+          float sqrt_n = SlotCtx<GM>::select_parent(n);
+          // (the selects below read k as this statement leaves it, so they - and the wait for the records in front of them - stay
+          // behind the square root instead of being scheduled ahead of it)
+          asm volatile("" : "+v"(sqrt_n), "+v"(k));
+          {
+            const bool have = lane < k, mem = have && !in_regs;
+            n_l = mem ? n_l : 0u; q_l = mem ? q_l : 0.0f; d_l = mem ? d_l : 0.0f; v_l = mem ? v_l : 0.0f;
+            p_l = mem ? p_l : have ? fl_pr : 0.0f;
+            m_l = mem ? m_l : have ? meta_pack(0, 0, fl_mv, 0, 0) : 0ull;
+          }
+          if (!in_regs) {
             if (fw && prefix && plen < fw_plen && plen < 8u) {   // one child of this node was updated by the last backup
-              const uint32_t t_node = c.bcast(fw_node, static_cast<int>(plen));
               const uint32_t t_n = c.bcast(fw_n, static_cast<int>(plen));
               const float t_q = c.bcast(fw_q, static_cast<int>(plen)), t_d = c.bcast(fw_d, static_cast<int>(plen)), t_v = c.bcast(fw_v, static_cast<int>(plen));
               if (c0 + lane == t_node) { n_l = t_n; q_l = t_q; d_l = t_d; v_l = t_v; if (t_node == fl_node) m_l = fl_meta; }
             }
           }
-          const float fpu = (cur == root) ? fpu_root : ep.fpu_reduction;
+          const float fpu = (cur == root) ? fpu_root : fpu_red;
           uint32_t best;
           if constexpr (GUM) {
             if (gum_active != 0u && cur == root) best = c.gumbel_next_root_child(cp, k, n_l, q_l, p_l);
             else if (gum_active != 0u && gum_full != 0u) best = c.gumbel_interior_select(cp, k, n_l, q_l, p_l, v_cur);
-            else best = c.select_child(k, n_l, q_l, p_l, v_cur, n, fpu);
+            else best = c.select_among(k, n_l, q_l, p_l, v_cur, sqrt_n, cpuct, fpu);
           } else {
-            best = c.select_child(k, n_l, q_l, p_l, v_cur, n, fpu);
+            best = c.select_among(k, n_l, q_l, p_l, v_cur, sqrt_n, cpuct, fpu);
           }
           const uint32_t nxt = c0 + best;
           const uint32_t s_n = c.bcast(n_l, static_cast<int>(best));
@@ -577,7 +588,7 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
           const uint64_t s_m = c.bcast(m_l, static_cast<int>(best));
           if (plen < 8u) {
             if (lane == plen) { lv_node = nxt; lv_n = s_n; lv_q = s_q; lv_d = s_d; lv_v = s_v; lv_pp = meta_player(meta); }
-            prefix = prefix && plen < fw_plen && nxt == c.bcast(fw_node, static_cast<int>(plen));
+            prefix = prefix && plen < fw_plen && nxt == t_node;
           } else {
             prefix = false;
           }
@@ -621,11 +632,9 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
             },
             [&](int cslot, float& o_pi, float& o_v) -> bool {
               if (!pa.l0) return false;
-              uint32_t okg = ((lane >= static_cast<uint32_t>(GM::M) || static_cast<uint32_t>(l0a >> 32) == pipe_l0_tag(lkey, lane)) &&
-                              (lane > static_cast<uint32_t>(P) || static_cast<uint32_t>(l0b >> 32) == pipe_l0_tag(lkey, kResV + lane))) ? 1u : 0u;
-              okg &= c.bcast(okg, 0) & c.bcast(okg, 1) & c.bcast(okg, 2) & c.bcast(okg, 3) & c.bcast(okg, 4) & c.bcast(okg, 5) & c.bcast(okg, 6);
-              okg = c.bcast(okg, 0);
-              if (!okg) return false;
+              const bool okl = (lane >= static_cast<uint32_t>(GM::M) || static_cast<uint32_t>(l0a >> 32) == pipe_l0_tag(lkey, lane)) &&
+                               (lane > static_cast<uint32_t>(P) || static_cast<uint32_t>(l0b >> 32) == pipe_l0_tag(lkey, kResV + lane));
+              if (!c.group_all(okl)) return false;
               o_pi = lane < static_cast<uint32_t>(GM::M) ? __uint_as_float(static_cast<uint32_t>(l0a)) : 0.0f;
               o_v = lane <= static_cast<uint32_t>(P) ? __uint_as_float(static_cast<uint32_t>(l0b)) : 0.0f;
               if (cslot < 0) l0_hits += 1;          // (the shard counted a miss: the host moves these to the hits)
@@ -645,7 +654,7 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
             seq = seq + 1u == 0u ? 1u : seq + 1u;
             uint32_t pos = 0;
             if (lane == 0) pos = atomicAdd(TWO ? pipe_tail_of(pc, mg) : &pc->tail, 1u);
-            pos = c.bcast(pos, 0);
+            pos = c.template bcast_lane<0>(pos);
             const uint64_t payload = lane == 0 ? leaf.bb[0] : lane == 1 ? leaf.bb[1] : lane == 2 ? (static_cast<uint64_t>(slot) | (static_cast<uint64_t>(leaf.player) << 16))
                                                                                                   : static_cast<uint64_t>(seq);
             // (test hook, AZMI_PIPE_TEST_DROP = n: the request at ring position n goes out with a foreign lap tag - what an entry looks
@@ -900,11 +909,9 @@ __global__ __launch_bounds__(NT, 2) void k_pipe_tree_generic(PipeKernArgs ka) {
       for (;;) {
         if (lane < static_cast<uint32_t>(GM::M)) g0 = g_ld(res + lane);
         if (lane <= static_cast<uint32_t>(P)) g1 = g_ld(res + kResV + lane);
-        uint32_t okg = ((lane >= static_cast<uint32_t>(GM::M) || static_cast<uint32_t>(g0 >> 32) == tok_seq) &&
-                        (lane > static_cast<uint32_t>(P) || static_cast<uint32_t>(g1 >> 32) == tok_seq)) ? 1u : 0u;
-#pragma unroll
-        for (int i = 1; i < 8; i <<= 1) okg &= static_cast<uint32_t>(__shfl_xor(static_cast<int>(okg), i, 8));
-        if (okg) { answered = true; break; }
+        const bool okl = (lane >= static_cast<uint32_t>(GM::M) || static_cast<uint32_t>(g0 >> 32) == tok_seq) &&
+                         (lane > static_cast<uint32_t>(P) || static_cast<uint32_t>(g1 >> 32) == tok_seq);
+        if (((__ballot(okl) >> (grp * 8u)) & 0xFFull) == 0xFFull) { answered = true; break; }      // (the group's byte of the ballot: all eight agree)
         if (wall_clock64() - t_start > pa.cap_ticks) {
           if (lane == 0 && atomicAdd(&pc->dbg[0], 1u) == 0u) { pc->dbg[1] = my_slot; pc->dbg[2] = tok_seq; pc->dbg[3] = static_cast<uint32_t>(g0 >> 32); pc->dbg[4] = 0xBBBBu; pc->dbg[5] = static_cast<uint32_t>(g1 >> 32); pc->dbg[6] = g_ld(ar.req_seq + my_slot); }
           if (lane == 0) atomicOr(&pc->err, static_cast<uint32_t>(kPipeErrTimeout));
@@ -2035,6 +2042,68 @@ extern "C" int azmi_debug_pipe_log_dupes(azmi_pm* pm, uint64_t* out) {
   for (uint32_t i = 1; i < n; ++i)
     if (kv[i].first == kv[i - 1].first) { ++dup; if (kv[i].second - kv[i - 1].second < 4096u) ++near; }
   out[0] = n; out[1] = dup; out[2] = near;
+  return AZMI_OK;
+}
+
+// ---- diagnostics: the lane-group primitives of the descent, one wavefront (eight groups) per row ------------------------------------
+namespace azmi {
+__global__ __launch_bounds__(64) void k_debug_group_select(const uint32_t* k8, const uint32_t* n64, const float* q64, const float* p64, const float* vpar8,
+                                                           const uint32_t* npar8, const float* fpu8, const float* cpuct8, const unsigned long long* pred,
+                                                           float* sum64, uint32_t* best64, uint32_t* all64) {
+  const uint32_t wlane = threadIdx.x & 63u, row = blockIdx.x;
+  const size_t li = static_cast<size_t>(row) * 64u + wlane, gi = static_cast<size_t>(row) * 8u + (wlane >> 3);
+  EngineParams ep{};
+  EngineArrays ar{};
+  ep.cpuct = cpuct8[gi];
+  SlotCtx<Connect4> c(ep, ar, 0u, wlane & 7u);
+  const uint32_t k = k8[gi], n_l = n64[li];
+  const float q_l = q64[li], p_l = p64[li];
+  sum64[li] = c.seqsum8((c.lane < k && n_l > 0u) ? p_l : 0.0f);
+  best64[li] = c.select_child(k, n_l, q_l, p_l, vpar8[gi], npar8[gi], fpu8[gi]);
+  const bool mine = (pred[row] >> wlane) & 1ull;
+  all64[li] = (c.group_all(mine) ? 1u : 0u) | (c.group_any(mine) ? 2u : 0u);
+}
+}  // namespace azmi
+
+extern "C" int azmi_debug_group_select(int device, uint32_t rows, const uint32_t* k8, const uint32_t* n64, const float* q64, const float* p64,
+                                       const float* v_parent8, const uint32_t* n_parent8, const float* fpu8, const float* cpuct8, const uint64_t* pred,
+                                       float* sum64, uint32_t* best64, uint32_t* all64) {
+  using namespace azmi;
+  if (!k8 || !n64 || !q64 || !p64 || !v_parent8 || !n_parent8 || !fpu8 || !cpuct8 || !pred || !sum64 || !best64 || !all64)
+    return azmi_host_fail(AZMI_ERR_INVALID, "azmi_debug_group_select: null buffer");
+  if (rows == 0u || rows > 65536u) return azmi_host_fail(AZMI_ERR_INVALID, "azmi_debug_group_select: rows must be 1 .. 65536");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return azmi_host_fail(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  AZMI_HIP_TRY(hipSetDevice(device));
+  // one allocation: eight per-group / per-lane inputs, the predicate words, three per-lane outputs (4-byte words; the predicates 8)
+  const size_t n8 = static_cast<size_t>(rows) * 8u, n64w = static_cast<size_t>(rows) * 64u;
+  const size_t words = 5u * n8 + 3u * n64w + 2u * rows + 3u * n64w;
+  uint32_t* d = nullptr;
+  AZMI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), words * 4u));
+  unsigned long long* const d_pred = reinterpret_cast<unsigned long long*>(d);      // (first: 8-byte aligned)
+  uint32_t* const d_k = d + 2u * rows; uint32_t* const d_npar = d_k + n8;
+  float* const d_vpar = reinterpret_cast<float*>(d_npar + n8); float* const d_fpu = d_vpar + n8; float* const d_cpuct = d_fpu + n8;
+  uint32_t* const d_n = reinterpret_cast<uint32_t*>(d_cpuct + n8);
+  float* const d_q = reinterpret_cast<float*>(d_n + n64w); float* const d_p = d_q + n64w;
+  float* const d_sum = d_p + n64w; uint32_t* const d_best = reinterpret_cast<uint32_t*>(d_sum + n64w); uint32_t* const d_all = d_best + n64w;
+  hipError_t e = hipMemcpy(d_pred, pred, rows * 8u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_k, k8, n8 * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_npar, n_parent8, n8 * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_vpar, v_parent8, n8 * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_fpu, fpu8, n8 * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_cpuct, cpuct8, n8 * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_n, n64, n64w * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_q, q64, n64w * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_p, p64, n64w * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    k_debug_group_select<<<rows, 64>>>(d_k, d_n, d_q, d_p, d_vpar, d_npar, d_fpu, d_cpuct, d_pred, d_sum, d_best, d_all);
+    e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(sum64, d_sum, n64w * 4u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(best64, d_best, n64w * 4u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(all64, d_all, n64w * 4u, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return azmi_host_fail(AZMI_ERR_NO_DEVICE, "azmi_debug_group_select: %s", hipGetErrorString(e));
   return AZMI_OK;
 }
 

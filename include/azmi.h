@@ -539,6 +539,14 @@ int azmi_debug_pipe_net_bench(azmi_pm* pm, azmi_net* net, uint32_t n, uint32_t r
  * those whose key is in the log more than once (evaluations an insert at answer time - PlayManager::update_inferences,
  * play_manager.cc:631-640 - or a table of requests in flight would have saved), out[2] = of those, twins within 4096 log entries */
 int azmi_debug_pipe_log_dupes(azmi_pm* pm, uint64_t* out);
+/* diagnostics: the descent's lane-group primitives on their own, one wavefront (eight 8-lane groups) per row.  Inputs per group
+ * (rows x 8): k, v_parent, n_parent, fpu, cpuct; per lane (rows x 64, lane j of group g at 8 g + j): n_l, q_l, p_l; pred[row]: a 64-bit
+ * lane predicate.  Outputs per lane (rows x 64): sum64 = the in-order sum of the priors of the visited children as that lane holds
+ * it, best64 = select_child's winner, all64 = bit 0: every lane of the group has its predicate bit set, bit 1: some lane has.
+ * tests/test_gpu_group_primitives.py */
+int azmi_debug_group_select(int device, uint32_t rows, const uint32_t* k8, const uint32_t* n64, const float* q64, const float* p64,
+                            const float* v_parent8, const uint32_t* n_parent8, const float* fpu8, const float* cpuct8, const uint64_t* pred,
+                            float* sum64, uint32_t* best64, uint32_t* all64);
 /* 1 when azmi_run_pipeline can drive this engine with this net (net may be NULL for an engine whose seats all use
  * EvalType::RANDOM: the tree kernel alone), 0 otherwise (then azmi_run_rounds is the driver) */
 int azmi_pipeline_supported(azmi_pm* pm, azmi_net* net);
