@@ -1,5 +1,12 @@
-// Host-side state of one PlayManager engine, shared by the translation units of libazmi.so that launch kernels on it
-// (engine.hip: the round loop and the C ABI; pipeline.hip: the asynchronous tree / net pipeline).
+// Host-side state of one PlayManager engine and the host helpers shared by the translation units of libazmi.so that launch
+// kernels on it:
+//   engine.hip        the lock-step round loop, azmi_pm_* / azmi_run_rounds* and the error text.  It is also the one device
+//                     module of the engine, MCTS-object and replay kernels (the code of a kernel depends on the kernels it
+//                     shares a module with) and launches them for the two files below; defines k_assign
+//   mcts_object.hip   the stand-alone MCTS object (azmi_mcts_*) on a one-slot engine; host code only
+//   replay.hip        rules replay, playout evaluation, StarGambit images and the RNG probe; host code only
+//   pipeline.hip      the asynchronous tree / net pipeline
+//   search_batch.hip  the batched position search (azmi_search_*)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,10 +30,47 @@ int azmi_host_fail(int code, const char* fmt, ...);
                             hipGetErrorString(e_));                                       \
   } while (0)
 
-// shared with search_batch.hip (defined in engine.hip): the PlayParams of the engine behind MCTS(...) constructor arguments with
-// room for `sims` simulations per tree, and the host-side check of a batch of serialized start positions
+// calls that stage temporary device buffers (DevTemps below) report every HIP error as AZMI_ERR_NO_DEVICE
+#define AZMI_HIP_TRY_NODEV(expr)                                                          \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) return azmi_host_fail(AZMI_ERR_NO_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// the PlayParams of the engine behind MCTS(...) constructor arguments with room for `sims` simulations per tree
+// (mcts_object.hip; shared with search_batch.hip)
 extern "C" int azmi_host_mcts_params(int game, const azmi_mcts_config* cfg, uint32_t sims, azmi_play_params* out_p);
+// the host-side check of a batch of serialized start positions (replay.hip)
 extern "C" int azmi_host_check_init_rows(int game, const uint8_t* init, uint32_t init_stride, uint32_t n, uint32_t* extra_reps);
+
+// Temporary device buffers of one host call, freed when the call returns.  A buffer is never smaller than min_bytes.
+struct DevTemps {
+  explicit DevTemps(size_t min_bytes = 4) : min_bytes_(min_bytes) {}
+  DevTemps(const DevTemps&) = delete;
+  DevTemps& operator=(const DevTemps&) = delete;
+  ~DevTemps() { for (void* q : bufs_) (void)hipFree(q); }
+  template <class T>
+  hipError_t alloc(T*& p, size_t count) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, std::max(count * sizeof(T), min_bytes_));
+    if (e == hipSuccess) { bufs_.push_back(q); p = static_cast<T*>(q); }
+    return e;
+  }
+  // alloc + copy of `count` elements from the host: blocking, or queued on `st`
+  template <class T>
+  hipError_t upload(T*& p, const T* host, size_t count) {
+    const hipError_t e = alloc(p, count);
+    return e != hipSuccess || count == 0 ? e : hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice);
+  }
+  template <class T>
+  hipError_t upload_async(T*& p, const T* host, size_t count, hipStream_t st) {
+    const hipError_t e = alloc(p, count);
+    return e != hipSuccess || count == 0 ? e : hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, st);
+  }
+ private:
+  size_t min_bytes_;
+  std::vector<void*> bufs_;
+};
 
 namespace azmi {
 struct GameInfo {
@@ -100,3 +144,28 @@ struct azmi_pm {
   }
 };
 
+// ---- defined in engine.hip for mcts_object.hip and replay.hip ------------------------------------------------------------------------
+// the static description of a game id (false: unknown id), and the engine's Control block read back on `st` - after a settling
+// k_assign when `settle` - with a raised overflow mask turned into AZMI_ERR_OVERFLOW
+bool azmi_host_game_info(int game, azmi::GameInfo* gi);
+int azmi_host_read_ctl(azmi_pm* pm, hipStream_t st, azmi::Control* out, bool settle);
+// One launch each, arguments as the kernels take them.  Replay family: on the null stream, grids sized by n.
+void azmi_host_launch_replay(int game, const uint8_t* d_init, uint32_t init_stride, const int32_t* d_moves, uint32_t n, uint32_t len, uint64_t* d_rep,
+                             uint32_t stride, uint8_t* d_valid, float* d_scores, float* d_canon, uint32_t* d_player, uint32_t* d_turn, uint64_t* d_key,
+                             int32_t* d_status, uint32_t flags);
+void azmi_host_launch_playout(int game, const uint8_t* d_init, uint32_t init_stride, const int32_t* d_moves, uint32_t n, uint32_t len, uint64_t* d_rep,
+                              uint32_t stride, const uint64_t* d_seeds, float* d_v, float* d_pi, int32_t* d_status);
+void azmi_host_launch_sg_image(const uint8_t* d_init, uint32_t init_stride, const int32_t* d_moves, uint32_t n, uint32_t len, uint64_t* d_rep, uint32_t stride,
+                               uint8_t* d_out, uint32_t out_stride, uint32_t* d_len, int32_t* d_status, uint32_t flags);
+void azmi_host_launch_rng_probe(int kind, uint64_t seed, float param, uint32_t n, uint32_t reps, uint32_t* out_u, float* out_f);
+// MCTS object: one wavefront on the engine's slot 0, on `st`
+namespace azmi { struct WuArrays; }
+void azmi_host_launch_mcts_find_leaf(azmi_pm* pm, hipStream_t st, uint32_t* nif, const uint8_t* di, uint32_t init_bytes, const int32_t* d_moves, uint32_t len,
+                                     int32_t* d_out_moves, uint32_t* d_len, int32_t* d_status);
+void azmi_host_launch_mcts_process_result(azmi_pm* pm, hipStream_t st, uint32_t rn, float* d_f);
+void azmi_host_launch_mcts_find_leaf_batched(azmi_pm* pm, hipStream_t st, const azmi::WuArrays& wu, uint32_t idx, const uint8_t* di, uint32_t init_bytes,
+                                             const int32_t* d_moves, uint32_t len, int32_t* d_out_moves, uint32_t* d_len, int32_t* d_status);
+void azmi_host_launch_mcts_process_result_batched(azmi_pm* pm, hipStream_t st, const azmi::WuArrays& wu, uint32_t leaf_index, uint32_t rn, float* d_f);
+void azmi_host_launch_mcts_update_root(azmi_pm* pm, hipStream_t st, uint32_t* nif, const uint8_t* di, uint32_t init_bytes, const int32_t* d_moves, uint32_t len,
+                                       uint32_t move, int32_t* d_status);
+void azmi_host_launch_mcts_query(azmi_pm* pm, hipStream_t st, uint32_t kind, float temp, uint32_t arg, float* d_f, uint32_t* d_u);

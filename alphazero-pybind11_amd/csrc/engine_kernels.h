@@ -1670,9 +1670,7 @@ __device__ __forceinline__ void assign_body(const EngineParams& ep, const Engine
   }
 }
 
-#ifndef AZMI_KERNELS_NO_ASSIGN   // (a plain, non-template kernel: one translation unit of the library defines it)
-__global__ void k_assign(EngineParams ep, EngineArrays ar, uint32_t count_round) { assign_body(ep, ar, count_round); }
-#endif
+// (k_assign, the plain kernel around assign_body, is defined in engine.hip: one translation unit of the library owns it)
 
 // Start of a round with the position cache on: the leaves the net evaluated in the previous round go into
 // the cache (PlayManager::update_inferences -> insert_many, play_manager.cc:631-640; one wave per leaf, batch

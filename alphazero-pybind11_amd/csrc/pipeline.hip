@@ -21,7 +21,6 @@
 
 #include "../../include/azmi.h"
 #include "engine_host.h"
-#define AZMI_KERNELS_NO_ASSIGN
 #include "engine_kernels.h"
 #include "leafnet_c4.h"
 #include "pipe_types.h"

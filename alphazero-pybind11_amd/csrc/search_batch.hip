@@ -14,7 +14,6 @@
 #include "../../include/azmi.h"
 #include "cache_host.h"
 #include "engine_host.h"
-#define AZMI_KERNELS_NO_ASSIGN      // k_assign, the one plain kernel of engine_kernels.h, belongs to engine.hip
 #include "search_batch_kernels.h"
 
 using namespace azmi;
@@ -53,20 +52,22 @@ namespace {
 constexpr uint32_t kSmallThreads = 256;
 inline uint32_t small_blocks(uint32_t n) { return (n * static_cast<uint32_t>(Connect4::GROUP) + kSmallThreads - 1) / kSmallThreads; }
 
-// SMALL / BIG: statements that use the game type GM (lane-group engine / one wavefront per tree)
-#define SB_DISPATCH(game, SMALL, BIG)                                            \
-  switch (game) {                                                                \
-    case AZMI_GAME_CONNECT4: { using GM = Connect4; SMALL; break; }              \
-    case AZMI_GAME_TAWLBWRDD: { using GM = Tawlbwrdd; BIG; break; }              \
-    case AZMI_GAME_BRANDUBH: { using GM = Brandubh; BIG; break; }                \
-    case AZMI_GAME_OPENTAFL: { using GM = OpenTafl; BIG; break; }                \
-    default: { using GM = StarGambit; BIG; break; }                              \
+// small(Connect4{}) / big(GM{}) as for_game, with this file's own last arm: any other id runs as StarGambit (ids are validated at create)
+template <class Small, class Big>
+void sb_for_game(int game, Small&& small, Big&& big) {
+  switch (game) {
+    case AZMI_GAME_CONNECT4: small(Connect4{}); break;
+    case AZMI_GAME_TAWLBWRDD: big(Tawlbwrdd{}); break;
+    case AZMI_GAME_BRANDUBH: big(Brandubh{}); break;
+    case AZMI_GAME_OPENTAFL: big(OpenTafl{}); break;
+    default: big(StarGambit{}); break;
   }
+}
 
 void launch_find(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t eval_random, hipStream_t st) {
   const uint32_t n = s->n;
-  SB_DISPATCH(s->pm->game, (k_sb_find<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, eval_random)),
-              (k_sb_big_find<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, eval_random)));
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_find<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, eval_random); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_find<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, eval_random); });
   k_sb_compact<<<1, 1024, 0, st>>>(s->sb, n);
   s->launches += 2;
 }
@@ -74,8 +75,8 @@ void launch_find(azmi_search* s, const EngineParams& ep, const EngineArrays& ar,
 void launch_process(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, const float* v_rows, const float* pi_rows,
                     hipStream_t st) {
   const uint32_t n = s->n;
-  SB_DISPATCH(s->pm->game, (k_sb_process<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows)),
-              (k_sb_big_process<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows)));
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_process<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_process<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows); });
   s->launches += 1;
 }
 
@@ -83,8 +84,8 @@ void launch_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, hipSt
   const uint32_t n = s->n;
   const EngineParams& ep = s->pm->ep;
   const EngineArrays& ar = s->pm->ar;
-  SB_DISPATCH(s->pm->game, (k_sb_query<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u)),
-              (k_sb_big_query<GM><<<n, 64, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u)));
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_query<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_query<GM><<<n, 64, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u); });
   s->launches += 1;
 }
 
@@ -93,8 +94,8 @@ void launch_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, hipSt
 void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, hipStream_t st) {
   for (uint32_t off = 0; off < s->n; off += kApplyMax) {
     const uint32_t m = std::min<uint32_t>(kApplyMax, s->n - off);
-    SB_DISPATCH(s->pm->game, (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)),
-                (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)));
+    auto insert = [&](auto tag) { using GM = decltype(tag); k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u); };
+    sb_for_game(s->pm->game, insert, insert);
     s->launches += 1;
   }
 }
@@ -107,8 +108,8 @@ EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine 
 
 void launch_find_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t eval_random, uint32_t root_noise, hipStream_t st) {
   const uint32_t n = s->n;
-  SB_DISPATCH(s->pm->game, (k_sb_find_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise)),
-              (k_sb_big_find_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise)));
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_find_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_find_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise); });
   k_sb_compact_wu<<<1, 1024, 0, st>>>(s->sb, s->wu, n, kk);
   s->launches += 2;
 }
@@ -116,8 +117,8 @@ void launch_find_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& 
 void launch_process_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, const float* v_rows,
                        const float* pi_rows, hipStream_t st) {
   const uint32_t n = s->n;
-  SB_DISPATCH(s->pm->game, (k_sb_process_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows)),
-              (k_sb_big_process_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows)));
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_process_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_process_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows); });
   s->launches += 1;
 }
 
@@ -127,8 +128,8 @@ void launch_cache_insert_wu(azmi_search* s, const EngineParams& ep, const Engine
   const uint32_t total = s->n * kk;
   for (uint32_t off = 0; off < total; off += kApplyMax) {
     const uint32_t m = std::min<uint32_t>(kApplyMax, total - off);
-    SB_DISPATCH(s->pm->game, (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, aw, aw.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)),
-                (k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, aw, aw.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u)));
+    auto insert = [&](auto tag) { using GM = decltype(tag); k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, aw, aw.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u); };
+    sb_for_game(s->pm->game, insert, insert);
     s->launches += 1;
   }
 }
@@ -297,31 +298,29 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->stream;
   s->ready = false; s->step_pending = false; s->sims_done = 0;
-  std::vector<void*> tmp;
-  auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); };
-  auto up = [&](void** d, const void* h, size_t bytes) {
-    hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) return e;
-    tmp.push_back(*d);
-    return bytes ? hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-#define SB_TRY2(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { (void)hipStreamSynchronize(st); cleanup(); return SB_FAIL(AZMI_ERR_NO_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } } while (0)
+  DevTemps tmp(16);
   uint8_t* d_init = nullptr; int32_t* d_moves = nullptr; uint32_t* d_offs = nullptr; uint64_t* d_seeds = nullptr;
-  if (init) SB_TRY2(up(reinterpret_cast<void**>(&d_init), init, static_cast<size_t>(n) * init_stride));
-  SB_TRY2(up(reinterpret_cast<void**>(&d_moves), moves, static_cast<size_t>(total) * 4));
-  SB_TRY2(up(reinterpret_cast<void**>(&d_offs), move_offsets, (static_cast<size_t>(n) + 1) * 4));
-  SB_TRY2(up(reinterpret_cast<void**>(&d_seeds), seeds, static_cast<size_t>(n) * 8));
-  SB_TRY2(hipMemsetAsync(pm->ar.ctl, 0, sizeof(Control), st));       // a stopped search does not outlive its positions
-  if (s->k_leaves > 1)     // the in-flight mark of every root (node 0 of its tree); every other node gets its mark cleared when it is created
-    SB_TRY2(hipMemset2DAsync(s->wu.wu.nif, static_cast<size_t>(pm->gi.P) * pm->ep.cap * 4, 0, 4, n, st));
-  SB_DISPATCH(pm->game, (k_sb_seed<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds)),
-              (k_sb_big_seed<GM><<<n, 64, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds)));
-  s->launches += 1;
-  SB_TRY2(hipGetLastError());
+  auto stage = [&]() -> hipError_t {      // uploads, resets and the seed launch, queued on st; the first error ends it
+    hipError_t e = init ? tmp.upload_async(d_init, init, static_cast<size_t>(n) * init_stride, st) : hipSuccess;
+    if (e == hipSuccess) e = tmp.upload_async(d_moves, moves, total, st);
+    if (e == hipSuccess) e = tmp.upload_async(d_offs, move_offsets, static_cast<size_t>(n) + 1, st);
+    if (e == hipSuccess) e = tmp.upload_async(d_seeds, seeds, n, st);
+    if (e == hipSuccess) e = hipMemsetAsync(pm->ar.ctl, 0, sizeof(Control), st);       // a stopped search does not outlive its positions
+    if (e == hipSuccess && s->k_leaves > 1)     // the in-flight mark of every root (node 0 of its tree); every other node gets its mark cleared when it is created
+      e = hipMemset2DAsync(s->wu.wu.nif, static_cast<size_t>(pm->gi.P) * pm->ep.cap * 4, 0, 4, n, st);
+    if (e != hipSuccess) return e;
+    sb_for_game(pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_seed<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds); },
+                [&](auto tag) { using GM = decltype(tag); k_sb_big_seed<GM><<<n, 64, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds); });
+    s->launches += 1;
+    return hipGetLastError();
+  };
+  const hipError_t e = stage();
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);     // what was queued may still read the buffers tmp is about to free
+    return SB_FAIL(AZMI_ERR_NO_DEVICE, "azmi_search_reset: %s", hipGetErrorString(e));
+  }
   pm->last = st;
-  const int rc = check_device(s, st);
-  cleanup();
-#undef SB_TRY2
+  const int rc = check_device(s, st);   // synchronises st: tmp is freed after it
   if (rc != AZMI_OK) return rc;
   s->ready = true;
   return AZMI_OK;
