@@ -379,6 +379,7 @@ class GameState:
 
 class Connect4GS(GameState):  # py_wrapper.cc:562-586
     GAME_ID = 0
+    MAX_TURNS = 42             # board cells
 
     def __init__(self, board=None, player=0, turn=0):
         super().__init__()
@@ -562,8 +563,18 @@ class MCTSBatch:
     reference's evaluation tools, which hold a list of MCTS objects, step them in lock step and batch the leaves into one net
     call (frozen_eval.py:545-660, mcts_analysis.py:923-1049, play.py:292-343).  Tree i is bit for bit the stand-alone
     `MCTS(..., seed=seeds[i])` driven call by call from states[i] with the same evaluator values.  The constructor takes the
-    MCTS constructor's search arguments; `max_simulations` (required) sizes every tree's arena.  No move is played on a batch:
-    call reset() with the new positions.  Read-outs return one row per tree.
+    MCTS constructor's search arguments; `max_simulations` (required) sizes every tree's arena.  Read-outs return one row per tree.
+
+    Moves are played on the device with tree reuse, the way the tools walk a game (play.py:274-346, mcts_analysis.py:995-1051):
+    pick_moves(temp) is m.pick_move(m.probs(temp)) of every tree from its own stream (gumbel_final_action() for a Gumbel
+    search), update_roots() is m.update_root(gs, move) + gs.play_move(move) on every tree, add_root_noise() /
+    apply_root_policy_temp() are the object's, and play(visits, ..., max_moves=m) enqueues m x (search, pick, update_roots,
+    root prior) without a host round trip - whole games in one call.  Tree i stays bit for bit the stand-alone MCTS driven by
+    the same calls.  A tree whose game is over is finished(): it is skipped by every later step (its read-outs stay legal),
+    takes no further move, and its result is final_scores()[i]; move_logs() / states() give the moves played since reset()
+    and the current root states.  The budget: a Connect4 arena never reclaims, so `max_simulations` counts every descent
+    since reset(), moves included (a game needs visits x moves); the wide games compact their arenas behind update_roots(),
+    so it counts the descents since the last update_roots() that moved every tree.
 
     `leaves_per_step=K` (1 <= K <= 64, default 1) holds K leaves of every tree in flight per step (WU-UCT), for a few
     positions searched deeply: the net then sees up to n * K rows per call instead of n.  With K > 1 one step of tree i is
@@ -605,6 +616,7 @@ class MCTSBatch:
         self._vec = max(M, 64)
         self._seeds = None if seeds is None else self._seed_array(seeds)
         self._rows = None          # rows of the pending find_leaves() batch
+        self._start = None         # the states of the last reset()
         self._k = int(leaves_per_step)
         if self._k > 1:
             check(lib.azmi_search_set_leaves_per_step(self._h, self._k))
@@ -651,8 +663,10 @@ class MCTSBatch:
             for i, b in enumerate(images):
                 init[i, : len(b)] = np.frombuffer(b, np.uint8)
         self._rows = None
+        self._start = None
         check(lib.azmi_search_reset(self._h, None if init is None else init.ctypes.data, stride, moves.ctypes.data if moves.size else None,
                                     offs.ctypes.data, sd.ctypes.data))
+        self._start = [g.copy() for g in states]
 
     def search(self, visits, net=None, cache=None, root_noise=False):
         """`visits` simulations of every tree, enqueued without host synchronisation (the read-outs and synchronize() wait);
@@ -667,6 +681,76 @@ class MCTSBatch:
 
     def synchronize(self):
         check(lib.azmi_search_sync(self._h))
+
+    # ---- moves: tree reuse on the device ----------------------------------------------------------------
+    def pick_moves(self, temp):
+        """pick_move(probs(temp)) of every tree from its own stream (a Gumbel search: gumbel_final_action(), no draw)
+        -> int32 [n], -1 for a finished tree.  The moves also stay on the device for update_roots()."""
+        out = np.full(self._n, -1, np.int32)
+        check(lib.azmi_search_pick_moves(self._h, float(temp), out.ctypes.data, C.c_void_p(-1)))
+        return out
+
+    def update_roots(self, moves=None):
+        """update_root + play_move on every tree: moves[i] (< 0: tree i stays), default the moves of the last pick_moves()
+        (a pick is played once: without a new pick_moves() nothing moves).
+        A move that is not one of a tree's root raises RuntimeError naming the tree; that tree is left where it was, the other
+        trees' moves of the call are applied."""
+        mv = None
+        if moves is not None:
+            mv = np.ascontiguousarray(moves, dtype=np.int32)
+            if mv.shape != (self._n,):
+                raise RuntimeError(f"update_roots: one move per tree ({self._n}), got {mv.shape}")
+        check(lib.azmi_search_update_roots(self._h, None if mv is None else mv.ctypes.data, C.c_void_p(-1)))
+
+    def add_root_noise(self): check(lib.azmi_search_root_prior(self._h, 0, 1, C.c_void_p(-1)))
+    def apply_root_policy_temp(self): check(lib.azmi_search_root_prior(self._h, 1, 0, C.c_void_p(-1)))
+
+    def play(self, visits, net=None, cache=None, temp=1.0, max_moves=1, root_noise=False):
+        """max_moves x (search(visits, net, cache, root_noise); pick_moves(temp); update_roots(); on the reused root
+        apply_root_policy_temp() when the root temperature is not 1 and add_root_noise() when root_noise), enqueued without
+        host synchronisation.  Finished trees are skipped, so `max_moves` of a game's length plays whole games."""
+        if net is not None and (net.desc.num_moves != self._M or (net.desc.in_channels, net.desc.height, net.desc.width) != self._chw):
+            raise RuntimeError("play: the net's shape does not match the game")
+        if cache is not None:
+            cache._ensure_engine_layout()
+        check(lib.azmi_search_play(self._h, None if net is None else net._h, None if cache is None else cache._h, int(visits), float(temp),
+                                   int(max_moves), int(bool(root_noise)), C.c_void_p(-1)))
+
+    def _game_state(self, log=False, final=False):
+        cap = self._game.MAX_TURNS + 8
+        status = np.zeros(self._n, np.int32); length = np.zeros(self._n, np.uint32)
+        lg = np.zeros((self._n, cap), np.int32) if log else None
+        fs = np.zeros((self._n, self._P + 1), np.float32) if final else None
+        check(lib.azmi_search_game_state(self._h, status.ctypes.data, length.ctypes.data, None if lg is None else lg.ctypes.data,
+                                         None if fs is None else fs.ctypes.data))
+        return status, length, lg, fs
+
+    def finished(self):
+        """bool [n]: the tree's game is over (a move played on the batch reached a terminal state)."""
+        return self._game_state()[0] > 0
+
+    def move_logs(self):
+        """The moves played on every tree since reset(): a list of int32 arrays."""
+        _, length, lg, _ = self._game_state(log=True)
+        return [lg[i, : int(length[i])].copy() for i in range(self._n)]
+
+    def final_scores(self):
+        """[n, P+1]: GameState.scores() of every finished tree (rows of live trees are zero)."""
+        status, _, _, fs = self._game_state(final=True)
+        fs[status <= 0] = 0
+        return fs
+
+    def states(self):
+        """The current root GameState of every tree: its reset() state + its move log."""
+        if self._start is None:
+            raise RuntimeError("states: the trees have no positions; call reset first")
+        out = []
+        for g, lg in zip(self._start, self.move_logs()):
+            g = g.copy()
+            g._moves.extend(int(m) for m in lg)      # (children of a root: legal by construction)
+            g._snap = None
+            out.append(g)
+        return out
 
     # ---- step API: any evaluator --------------------------------------------------------------------
     def find_leaves(self, numpy=None):
@@ -981,6 +1065,7 @@ class StarGambitUnifiedGS(GameState):
     PlayManager draws every game's variant from the slot's coin stream."""
 
     GAME_ID = 4
+    MAX_TURNS = 4096           # the engine's bound on the ACTIONS of a game (csrc/dev_stargambit.h)
     _REPLAY_FLAGS = 1          # play_move does not validate, like the reference's (star_gambit_gs.cc:1093-1238)
     _VARIANT_NAMES = ("Skirmish", "Showdown", "Clash", "Battle")
 

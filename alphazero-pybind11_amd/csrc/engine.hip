@@ -1297,6 +1297,12 @@ void azmi_host_launch_mcts_update_root(azmi_pm* pm, hipStream_t st, uint32_t* ni
       if (pm->ep.half_nodes) k_compact<GM><<<std::min<uint32_t>(trees, kCompactBlocks), 256, 0, st>>>(pm->ep, pm->ar, trees, nif);
     });
 }
+// the batched search's compaction behind an update-root launch: the flagged ones of `trees` = N * P trees (search_batch.hip)
+void azmi_host_launch_compact(azmi_pm* pm, hipStream_t st, uint32_t trees, uint32_t* nif) {
+  if (!pm->ep.half_nodes) return;
+  for_game(pm->game, [&](auto) {},
+    [&](auto tag) { using GM = decltype(tag); k_compact<GM><<<std::min<uint32_t>(trees, kCompactBlocks), 256, 0, st>>>(pm->ep, pm->ar, trees, nif); });
+}
 void azmi_host_launch_mcts_query(azmi_pm* pm, hipStream_t st, uint32_t kind, float temp, uint32_t arg, float* d_f, uint32_t* d_u) {
   for_game(pm->game,
     [&](auto tag) { using GM = decltype(tag); k_mcts_query<GM><<<1, 64, 0, st>>>(pm->ep, pm->ar, kind, temp, arg, d_f, d_u); },

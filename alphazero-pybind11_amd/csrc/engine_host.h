@@ -169,3 +169,5 @@ void azmi_host_launch_mcts_process_result_batched(azmi_pm* pm, hipStream_t st, c
 void azmi_host_launch_mcts_update_root(azmi_pm* pm, hipStream_t st, uint32_t* nif, const uint8_t* di, uint32_t init_bytes, const int32_t* d_moves, uint32_t len,
                                        uint32_t move, int32_t* d_status);
 void azmi_host_launch_mcts_query(azmi_pm* pm, hipStream_t st, uint32_t kind, float temp, uint32_t arg, float* d_f, uint32_t* d_u);
+// k_compact over the first `trees` trees of the engine on `st` (nif: the in-flight marks that move with the nodes, or NULL); no-op for Connect4
+void azmi_host_launch_compact(azmi_pm* pm, hipStream_t st, uint32_t trees, uint32_t* nif);

@@ -1,7 +1,9 @@
 // Batched position search (azmi_search_*, include/azmi.h): N search trees on N different positions in ONE engine arena, all of
 // them advanced by one simulation per (find-leaves, process-results) launch pair, the leaf net and the position cache on the
 // device.  Host side of csrc/search_batch_kernels.h.  The engine behind it is a PlayManager engine with N slots built from the
-// MCTS constructor's arguments (azmi_host_mcts_params, as azmi_mcts_create does for its one slot); no game is ever played on it.
+// MCTS constructor's arguments (azmi_host_mcts_params, as azmi_mcts_create does for its one slot); the engine's own game loop never
+// runs on it.  Moves ARE played on the trees: azmi_search_pick_moves / update_roots / root_prior / play below advance every tree's
+// root on the device (update_root with tree reuse) and cross moves without the host.
 // azmi_search_set_leaves_per_step(K > 1) switches every step to K descents per tree with K leaves in flight (WU-UCT): the *_wu
 // kernels and launch helpers below; K == 1 runs the original ones.
 #include <hip/hip_runtime.h>
@@ -23,7 +25,12 @@ using namespace azmi;
 
 struct azmi_search {
   azmi_pm* pm = nullptr;
-  uint32_t n = 0, max_sims = 0, sims_done = 0;
+  uint32_t n = 0, max_sims = 0;
+  uint32_t sims_done = 0;      // descents that count against max_sims: since reset (Connect4), since the last update_roots (wide games)
+  bool flat_arena = false;     // Connect4: the arena never reclaims.  Wide games: two halves, compacted behind update_roots
+  float root_temp = 1.0f;
+  SbPlayArrays pl{};
+  int32_t* d_moves_in = nullptr;  // [N] a caller's moves for update_roots
   uint32_t chw = 0, vec_f = 0, vec_u = 0;
   bool ready = false;          // reset() has given every tree a position
   bool step_pending = false;   // find_leaves() without its process_results()
@@ -141,18 +148,57 @@ void wu_free(azmi_search* s) {
   s->d_batch_wu = nullptr; s->d_vrows_wu = nullptr; s->d_pirows_wu = nullptr;
 }
 
-// synchronises `st` and turns a stopped tree / a raised overflow bit into an error that names the tree
+// why `more` descents do not fit (0: they do).  Connect4's flat arena never reclaims, so max_simulations counts every descent
+// since reset(), the searches between moves included; the wide games compact behind update_roots (the PlayManager engine's rule),
+// so it counts the descents since the last one.
+int check_budget(const azmi_search* s, const char* what, uint64_t more) {
+  if (more <= s->max_sims - s->sims_done) return AZMI_OK;
+  if (s->flat_arena)
+    return SB_FAIL(AZMI_ERR_OVERFLOW, "%s: %llu more simulations, %u of max_simulations = %u are already used: a Connect4 arena never "
+                   "reclaims, so the budget counts every descent since reset(), moves included (a game needs visits x moves)", what,
+                   static_cast<unsigned long long>(more), s->sims_done, s->max_sims);
+  return SB_FAIL(AZMI_ERR_OVERFLOW, "%s: %llu more simulations, %u of max_simulations = %u are already used: the budget counts the "
+                 "descents since the last update_roots (its compaction reclaims the discarded siblings)", what,
+                 static_cast<unsigned long long>(more), s->sims_done, s->max_sims);
+}
+
+// synchronises `st` and turns a stopped tree / a raised overflow bit into an error that names the tree.  A finished tree
+// (status > 0) is no error.  The two errors of a move (a move the root does not have, a root without visits) left their tree as
+// it was: the tree is named, its status and the engine's "unknown move" bit are cleared, and the object stays usable.
 int check_device(azmi_search* s, hipStream_t st) {
   Control c;
   std::vector<int32_t> status(s->n);
   SB_TRY(hipMemcpyAsync(&c, s->pm->ar.ctl, sizeof(c), hipMemcpyDeviceToHost, st));
   SB_TRY(hipMemcpyAsync(status.data(), s->sb.status, static_cast<size_t>(s->n) * 4, hipMemcpyDeviceToHost, st));
   SB_TRY(hipStreamSynchronize(st));
-  for (uint32_t i = 0; i < s->n; ++i)
-    if (status[i] != 0)
-      return SB_FAIL(status[i] == -1 ? AZMI_ERR_INVALID : AZMI_ERR_OVERFLOW, "tree %u: %s (device overflow mask 0x%x)", i,
-                     status[i] == -1 ? "illegal move in the game record or malformed start position" : "find_leaf failed (tree arena or path capacity)",
-                     c.overflow);
+  // the errors of a move are cleared wherever they sit, so that one of them never outlives its report behind another tree's stop
+  uint32_t first = s->n, first_move = s->n;
+  for (uint32_t i = 0; i < s->n; ++i) {
+    if (status[i] >= 0) continue;
+    if (status[i] == kSbBadMove || status[i] == kSbNoVisits) { if (first_move == s->n) first_move = i; }
+    else if (first == s->n) first = i;
+  }
+  const int32_t move_code = first_move < s->n ? status[first_move] : 0;
+  if (first_move < s->n) {
+    for (uint32_t i = 0; i < s->n; ++i) if (status[i] == kSbBadMove || status[i] == kSbNoVisits) status[i] = 0;
+    SB_TRY(hipMemcpy(s->sb.status, status.data(), static_cast<size_t>(s->n) * 4, hipMemcpyHostToDevice));
+    if (c.overflow & 32u) {      // as azmi_mcts_update_root does for its one tree
+      c.overflow &= ~32u; if (!c.overflow) c.stop = 0;
+      SB_TRY(hipMemcpy(s->pm->ar.ctl, &c, sizeof(c), hipMemcpyHostToDevice));
+    }
+  }
+  if (first < s->n) {
+    const int32_t code = status[first];
+    return SB_FAIL(code == kSbBadStart ? AZMI_ERR_INVALID : AZMI_ERR_OVERFLOW, "tree %u: %s (device overflow mask 0x%x)", first,
+                   code == kSbBadStart ? "illegal move in the game record or malformed start position"
+                   : code == kSbBadState ? "the root state did not take the move (rules or position-history capacity)"
+                                         : "find_leaf failed (tree arena or path capacity)",
+                   c.overflow);
+  }
+  if (move_code == kSbBadMove)
+    return SB_FAIL(AZMI_ERR_INVALID, "tree %u: ahh, what is this move (update_roots: not a move of the tree's root; that tree is left "
+                   "where it was, the other trees' moves of the call are applied)", first_move);
+  if (move_code == kSbNoVisits) return SB_FAIL(AZMI_ERR_STATE, "tree %u: pick_moves: the root has no visits; search first", first_move);
   if (c.overflow) return SB_FAIL(AZMI_ERR_OVERFLOW, "device search stopped: overflow mask 0x%x", c.overflow);
   return AZMI_OK;
 }
@@ -160,6 +206,119 @@ int check_device(azmi_search* s, hipStream_t st) {
 int begin_step(azmi_search* s, const char* what) {
   if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   if (!s->ready) return SB_FAIL(AZMI_ERR_STATE, "%s: the trees have no positions; call reset first", what);
+  return AZMI_OK;
+}
+
+// the engine parameters and arrays of a search() with this net and cache
+struct SearchArgs {
+  EngineParams ep;
+  EngineArrays ar;
+  azmi_net* net = nullptr;
+};
+int search_args(azmi_search* s, azmi_net* net, azmi_cache* cache, SearchArgs* out) {
+  azmi_pm* pm = s->pm;
+  out->ep = pm->ep; out->ar = pm->ar; out->net = net;
+  if (cache && net) {
+    if (cache->device != pm->device) return SB_FAIL(AZMI_ERR_INVALID, "cache lives on another device");
+    if (cache->c.np != pm->gi.M || cache->c.nv != pm->gi.P + 1) return SB_FAIL(AZMI_ERR_INVALID, "cache: num_policy / num_value do not match the game");
+    if (cache->c.cap != kWaveCap)
+      return SB_FAIL(AZMI_ERR_INVALID, "cache: the engine probes 64-entry shards; create the cache with shards = max_size / 64 "
+                     "(ShardedS3FIFOCache.for_engine)");
+    out->ep.cache_on = 1; out->ep.num_groups = 1;
+    out->ar.cache = cache->c; out->ar.cache_keys = s->d_keys;
+  }
+  return AZMI_OK;
+}
+
+// the steps of search(visits) on `st`, nothing read back: azmi_search_run, and every move of azmi_search_play
+int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
+  const EngineParams& ep = a.ep;
+  const EngineArrays& ar = a.ar;
+  azmi_net* net = a.net;
+  int rc = AZMI_OK;
+  if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
+  if (s->k_leaves > 1) {
+    // visits / K steps of K descents and one of the remainder, enqueued back to back like the K == 1 steps below
+    const EngineArrays aw = wu_rows(s, ar);
+    for (uint32_t left = visits; left;) {
+      const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
+      launch_find_wu(s, ep, ar, kk, net ? 0u : 1u, rn, st);
+      if (net) {
+        rc = azmi_net_forward_rows(net, aw.canon, aw.v, aw.pi, s->wu.rows, s->sb.n_rows, s->n * kk, st);
+        if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
+        s->net_calls += 1;
+        if (ep.cache_on) launch_cache_insert_wu(s, ep, ar, kk, st);
+      }
+      launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
+      left -= kk; s->steps += 1;
+    }
+    SB_TRY(hipGetLastError());
+    s->sims_done += visits;
+    return AZMI_OK;
+  }
+  // `visits` step pairs, enqueued back to back: the row count of a step never leaves the device
+  for (uint32_t i = 0; i < visits; ++i) {
+    launch_find(s, ep, ar, net ? 0u : 1u, st);
+    if (net) {
+      rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
+      if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
+      s->net_calls += 1;
+      if (ep.cache_on) launch_cache_insert(s, ep, ar, st);
+    }
+    launch_process(s, ep, ar, rn, nullptr, nullptr, st);
+  }
+  SB_TRY(hipGetLastError());
+  s->sims_done += visits; s->steps += visits;
+  return AZMI_OK;
+}
+
+// ---- a move: pick, update-root (+ compaction for the wide games), root prior; one launch each, whatever N is ------------------
+void launch_pick(azmi_search* s, float temp, hipStream_t st) {
+  const uint32_t n = s->n;
+  const EngineParams& ep = s->pm->ep;
+  const EngineArrays& ar = s->pm->ar;
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_pick<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->pl, n, temp, s->d_qf, s->vec_f, s->d_qu, s->vec_u); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_pick<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->pl, n, temp, s->d_qf, s->vec_f, s->d_qu, s->vec_u); });
+  s->launches += 1;
+}
+
+// `moves`: [N] on the device.  The wide games compact behind it (k_compact lives in engine.hip's device module)
+void launch_update_root(azmi_search* s, const int32_t* moves, hipStream_t st) {
+  const uint32_t n = s->n;
+  const EngineParams& ep = s->pm->ep;
+  const EngineArrays& ar = s->pm->ar;
+  uint32_t* nif = s->k_leaves > 1 ? s->wu.wu.nif : nullptr;
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_update_root<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->pl, n, moves, nif); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_update_root<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->pl, n, moves, nif); });
+  s->launches += 1;
+  if (ep.half_nodes) {
+    azmi_host_launch_compact(s->pm, st, n * s->pm->gi.P, nif);
+    s->launches += 1;
+  }
+}
+
+void launch_root_prior(azmi_search* s, uint32_t apply_temp, uint32_t noise, hipStream_t st) {
+  const uint32_t n = s->n;
+  const EngineParams& ep = s->pm->ep;
+  const EngineArrays& ar = s->pm->ar;
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_root_prior<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, apply_temp, noise, s->d_qf, s->vec_f, s->d_qu, s->vec_u); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_root_prior<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, apply_temp, noise, s->d_qf, s->vec_f, s->d_qu, s->vec_u); });
+  s->launches += 1;
+}
+
+// A NULL handle is what a caller holds whose create failed.  On a machine without a device that failure was the no-device one, and
+// the move entry points repeat it (AZMI_ERR_NO_DEVICE); with a device a NULL handle is an invalid argument (include/azmi.h says so).
+int begin_read(azmi_search* s, const char* what) {
+  if (!s) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SB_FAIL(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  }
+  return begin_step(s, what);
+}
+// the calls that change the trees: not while a find_leaves step is pending
+int begin_move(azmi_search* s, const char* what) {
+  int rc = begin_read(s, what); if (rc) return rc;
+  if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "%s: a find_leaves step is pending; call process_results first", what);
   return AZMI_OK;
 }
 
@@ -206,6 +365,8 @@ int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, 
   if (rc != AZMI_OK) { delete s; return rc; }
   azmi_pm* pm = s->pm;
   s->n = n_trees; s->max_sims = cfg->max_simulations; s->gumbel = cfg->gumbel_enabled != 0;
+  s->flat_arena = game == AZMI_GAME_CONNECT4; s->root_temp = cfg->root_policy_temp;
+  s->pl.log_cap = pm->gi.max_turns + 8;      // the MCTS object's moves_cap
   s->chw = pm->gi.C * pm->gi.H * pm->gi.W;
   s->vec_f = std::max<uint32_t>(pm->gi.M, 64u);
   s->vec_u = s->vec_f + 64u;
@@ -217,6 +378,8 @@ int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, 
   if (rc == AZMI_OK) rc = A(s->d_batch, N * s->chw);
   if (rc == AZMI_OK) rc = A(s->d_vrows, N * (pm->gi.P + 1)); if (rc == AZMI_OK) rc = A(s->d_pirows, N * pm->gi.M);
   if (rc == AZMI_OK) rc = A(s->d_qf, N * s->vec_f); if (rc == AZMI_OK) rc = A(s->d_qu, N * s->vec_u);
+  if (rc == AZMI_OK) rc = A(s->pl.move, N); if (rc == AZMI_OK) rc = A(s->pl.log, N * s->pl.log_cap); if (rc == AZMI_OK) rc = A(s->pl.log_len, N);
+  if (rc == AZMI_OK) rc = A(s->pl.final, N * (pm->gi.P + 1)); if (rc == AZMI_OK) rc = A(s->d_moves_in, N);
   if (rc != AZMI_OK) { azmi_pm_destroy(pm); delete s; return rc; }
   *out = s;
   return AZMI_OK;
@@ -306,6 +469,9 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
     if (e == hipSuccess) e = tmp.upload_async(d_offs, move_offsets, static_cast<size_t>(n) + 1, st);
     if (e == hipSuccess) e = tmp.upload_async(d_seeds, seeds, n, st);
     if (e == hipSuccess) e = hipMemsetAsync(pm->ar.ctl, 0, sizeof(Control), st);       // a stopped search does not outlive its positions
+    if (e == hipSuccess) e = hipMemsetAsync(s->pl.log_len, 0, static_cast<size_t>(n) * 4, st);      // nor do the moves played on the old ones
+    if (e == hipSuccess) e = hipMemsetAsync(s->pl.move, 0xFF, static_cast<size_t>(n) * 4, st);      // (-1: nothing picked yet)
+    if (e == hipSuccess && pm->ep.half_nodes) e = hipMemsetAsync(pm->ar.compact_flag, 0, static_cast<size_t>(n) * pm->gi.P * 4, st);
     if (e == hipSuccess && s->k_leaves > 1)     // the in-flight mark of every root (node 0 of its tree); every other node gets its mark cleared when it is created
       e = hipMemset2DAsync(s->wu.wu.nif, static_cast<size_t>(pm->gi.P) * pm->ep.cap * 4, 0, 4, n, st);
     if (e != hipSuccess) return e;
@@ -330,7 +496,7 @@ int azmi_search_find_leaves(azmi_search* s, void* stream, float** dev_canonical,
   int rc = begin_step(s, "find_leaves"); if (rc) return rc;
   if (!n_rows) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "find_leaves: the previous step's process_results has not been called");
-  if (s->sims_done + 1 > s->max_sims) return SB_FAIL(AZMI_ERR_OVERFLOW, "find_leaves: max_simulations = %u reached", s->max_sims);
+  rc = check_budget(s, "find_leaves", 1); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
@@ -411,56 +577,92 @@ int azmi_search_process_results_host(azmi_search* s, const float* v, const float
 int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream) {
   int rc = begin_step(s, "search"); if (rc) return rc;
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "search: a find_leaves step is pending; call process_results first");
-  if (visits > s->max_sims - s->sims_done)
-    return SB_FAIL(AZMI_ERR_OVERFLOW, "search of %u visits: %u of max_simulations = %u are already used", visits, s->sims_done, s->max_sims);
+  rc = check_budget(s, "search", visits); if (rc) return rc;
+  SearchArgs a;
+  rc = search_args(s, net, cache, &a); if (rc) return rc;
+  SB_TRY(hipSetDevice(s->pm->device));
+  return enqueue_search(s, a, visits, root_noise_enabled ? 1u : 0u, s->pm->pick(stream));
+}
+
+int azmi_search_pick_moves(azmi_search* s, float temp, int32_t* host_moves, void* stream) {
+  int rc = begin_move(s, "pick_moves"); if (rc) return rc;
   azmi_pm* pm = s->pm;
-  EngineParams ep = pm->ep;
-  EngineArrays ar = pm->ar;
-  if (cache && net) {
-    if (cache->device != pm->device) return SB_FAIL(AZMI_ERR_INVALID, "cache lives on another device");
-    if (cache->c.np != pm->gi.M || cache->c.nv != pm->gi.P + 1) return SB_FAIL(AZMI_ERR_INVALID, "cache: num_policy / num_value do not match the game");
-    if (cache->c.cap != kWaveCap)
-      return SB_FAIL(AZMI_ERR_INVALID, "cache: the engine probes 64-entry shards; create the cache with shards = max_size / 64 "
-                     "(ShardedS3FIFOCache.for_engine)");
-    ep.cache_on = 1; ep.num_groups = 1;
-    ar.cache = cache->c; ar.cache_keys = s->d_keys;
-  }
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
-  if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
-  const uint32_t rn = root_noise_enabled ? 1u : 0u;
-  if (s->k_leaves > 1) {
-    // visits / K steps of K descents and one of the remainder, enqueued back to back like the K == 1 steps below
-    const EngineArrays aw = wu_rows(s, ar);
-    for (uint32_t left = visits; left;) {
-      const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
-      launch_find_wu(s, ep, ar, kk, net ? 0u : 1u, rn, st);
-      if (net) {
-        rc = azmi_net_forward_rows(net, aw.canon, aw.v, aw.pi, s->wu.rows, s->sb.n_rows, s->n * kk, st);
-        if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
-        s->net_calls += 1;
-        if (ep.cache_on) launch_cache_insert_wu(s, ep, ar, kk, st);
-      }
-      launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
-      left -= kk; s->steps += 1;
+  launch_pick(s, temp, st);
+  SB_TRY(hipGetLastError());
+  if (!host_moves) return AZMI_OK;
+  SB_TRY(hipMemcpyAsync(host_moves, s->pl.move, static_cast<size_t>(s->n) * 4, hipMemcpyDeviceToHost, st));
+  return check_device(s, st);
+}
+
+int azmi_search_update_roots(azmi_search* s, const int32_t* host_moves, void* stream) {
+  int rc = begin_move(s, "update_roots"); if (rc) return rc;
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->pick(stream);
+  bool all = true;
+  if (host_moves) {
+    for (uint32_t i = 0; i < s->n; ++i) {
+      if (host_moves[i] >= static_cast<int32_t>(pm->gi.M)) return SB_FAIL(AZMI_ERR_INVALID, "tree %u: move %d out of range", i, host_moves[i]);
+      all = all && host_moves[i] >= 0;
     }
-    SB_TRY(hipGetLastError());
-    s->sims_done += visits;
-    return AZMI_OK;
+    SB_TRY(hipMemcpyAsync(s->d_moves_in, host_moves, static_cast<size_t>(s->n) * 4, hipMemcpyHostToDevice, st));
   }
-  // `visits` step pairs, enqueued back to back: the row count of a step never leaves the device
-  for (uint32_t i = 0; i < visits; ++i) {
-    launch_find(s, ep, ar, net ? 0u : 1u, st);
-    if (net) {
-      rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
-      if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
-      s->net_calls += 1;
-      if (ep.cache_on) launch_cache_insert(s, ep, ar, st);
-    }
-    launch_process(s, ep, ar, rn, nullptr, nullptr, st);
+  launch_update_root(s, host_moves ? s->d_moves_in : s->pl.move, st);
+  SB_TRY(hipGetLastError());
+  // a caller's moves may be unknown to a root: that is reported here, with the tree's index (the picked ones are children of their roots)
+  rc = host_moves ? check_device(s, st) : AZMI_OK;
+  // every live tree moved, none refused its move: compaction has made room for the next search
+  if (!s->flat_arena && all && rc == AZMI_OK) s->sims_done = 0;
+  return rc;
+}
+
+int azmi_search_root_prior(azmi_search* s, int apply_temp, int add_noise, void* stream) {
+  int rc = begin_move(s, "root_prior"); if (rc) return rc;
+  if (!apply_temp && !add_noise) return AZMI_OK;
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->pick(stream);
+  launch_root_prior(s, apply_temp ? 1u : 0u, add_noise ? 1u : 0u, st);
+  SB_TRY(hipGetLastError());
+  return AZMI_OK;
+}
+
+int azmi_search_play(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves, int root_noise,
+                     void* stream) {
+  int rc = begin_move(s, "play"); if (rc) return rc;
+  // the whole call's budget before anything is enqueued: Connect4 counts every move's search; a wide game's first search comes on
+  // top of the descents since the last update_roots, and every later one starts behind a compaction
+  rc = check_budget(s, "play", s->flat_arena ? static_cast<uint64_t>(visits) * max_moves : (max_moves ? visits : 0u)); if (rc) return rc;
+  SearchArgs a;
+  rc = search_args(s, net, cache, &a); if (rc) return rc;
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->pick(stream);
+  const uint32_t rn = root_noise ? 1u : 0u, rt = s->root_temp != 1.0f ? 1u : 0u;
+  for (uint32_t m = 0; m < max_moves; ++m) {
+    rc = enqueue_search(s, a, visits, rn, st); if (rc) return rc;
+    launch_pick(s, temp, st);
+    launch_update_root(s, s->pl.move, st);
+    if (!s->flat_arena) s->sims_done = 0;
+    if (rn || rt) launch_root_prior(s, rt, rn, st);
   }
   SB_TRY(hipGetLastError());
-  s->sims_done += visits; s->steps += visits;
+  return AZMI_OK;
+}
+
+int azmi_search_game_state(azmi_search* s, int32_t* status, uint32_t* log_len, int32_t* log, float* final_scores) {
+  int rc = begin_read(s, "game_state"); if (rc) return rc;      // a read-out: legal while a find_leaves step is pending
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->last;
+  const size_t N = s->n;
+  rc = check_device(s, st); if (rc) return rc;      // (synchronises)
+  if (status) SB_TRY(hipMemcpy(status, s->sb.status, N * 4, hipMemcpyDeviceToHost));
+  if (log_len) SB_TRY(hipMemcpy(log_len, s->pl.log_len, N * 4, hipMemcpyDeviceToHost));
+  if (log) SB_TRY(hipMemcpy(log, s->pl.log, N * s->pl.log_cap * 4, hipMemcpyDeviceToHost));
+  if (final_scores) SB_TRY(hipMemcpy(final_scores, s->pl.final, N * (pm->gi.P + 1) * 4, hipMemcpyDeviceToHost));
   return AZMI_OK;
 }
 

@@ -7,7 +7,10 @@
 // driven by the same per-tree functions: SlotCtx / BigSlot load, find_leaf, process_result, cache_lookup, emit_leaf, and the
 // read-outs of mcts_query_slot.  The kernels here only map the grid to slots and keep the per-tree bookkeeping of a step:
 //   pend[i]    what the tree's pending simulation waits for (SbPend)
-//   status[i]  0, or why the tree stopped (-1 bad start position, -2 find_leaf failed: arena / path capacity)
+//   status[i]  0, or why the tree stopped (-1 bad start position, -2 find_leaf failed: arena / path capacity, -3 update_root
+//              was given a move the root does not have, -4 a move was asked of a root without visits, -5 the root state did
+//              not take a move its tree has), or +1: the game is
+//              over (a move played on the batch reached a terminal state).  Every kernel skips a tree whose status != 0
 //   row_of[i]  row of the compacted leaf batch that holds tree i's leaf (kNoRow = none)
 //   rows[r]    tree index of compacted row r, ascending;  *n_rows = number of rows
 //   n_term[i]  simulations of tree i that ended in a terminal leaf
@@ -515,6 +518,197 @@ __global__ __launch_bounds__(64) void k_sb_big_query(EngineParams ep, EngineArra
   if (slot >= n) return;
   mcts_big_query_slot<GM>(ep, ar, sm, slot, threadIdx.x, kind, temp, arg, out_f + static_cast<size_t>(slot) * stride_f,
                           out_u + static_cast<size_t>(slot) * stride_u);
+}
+
+// ======================= moves played on the batch: pick, update_root, root prior ================================================
+// What the evaluation tools do between two searches of a game they walk (play.py:274-346, mcts_analysis.py:995-1051): pick a move
+// from the root's visit counts, MCTS::update_root (mcts.cc:151-173) on every tree, play the move on the root state, and search the
+// successor with the reused subtree.  The root state of tree i lives in slot i (written by the seed kernel), so the move is played
+// here, on the device.  Same grid-to-tree mapping as the find kernels.
+//   move[i]        the move chosen by the pick kernel (-1 = none: finished or stopped tree, nothing picked since reset, or the
+//                  pick was consumed by an update-root launch: an update_roots without a pick before it moves nothing)
+//   log[i][0..len) the moves played on tree i since reset (capacity log_cap = max_turns + 8), log_len[i] = len
+//   final[i][P+1]  GameState::scores() of a finished tree
+struct SbPlayArrays {
+  int32_t* move;       // [N]
+  int32_t* log;        // [N, log_cap]
+  uint32_t* log_len;   // [N]
+  float* final;        // [N, P + 1]
+  uint32_t log_cap;
+};
+enum SbStatus : int32_t { kSbFinished = 1, kSbBadStart = -1, kSbFindFailed = -2, kSbBadMove = -3, kSbNoVisits = -4, kSbBadState = -5 };
+
+// what the two update-root kernels share once the tree is re-rooted and `mv` is played: move log, finished rule
+template <class GM, class State>
+__device__ __forceinline__ void sb_after_move(const SbArrays& sb, const SbPlayArrays& pl, uint32_t slot, int32_t mv, const State& gs) {
+  const uint32_t len = pl.log_len[slot];
+  if (len < pl.log_cap) { pl.log[static_cast<size_t>(slot) * pl.log_cap + len] = mv; pl.log_len[slot] = len + 1; }
+  const uint32_t term = GM::terminal(gs);
+  if (term == 0) return;
+  bool scored = true;       // StarGambit: over with no winner recorded scores all zeros (replay_kernels.h)
+  if constexpr (is_stargambit<GM>::value) scored = GM::winner(gs) < 3;
+  for (uint32_t i = 0; i <= static_cast<uint32_t>(GM::P); ++i)
+    pl.final[static_cast<size_t>(slot) * (GM::P + 1) + i] = (scored && term - 1 == i) ? 1.0f : 0.0f;
+  sb.status[slot] = kSbFinished;
+}
+
+// pick_move(probs(temp)) from the tree's own stream (PUCT), gumbel_final_action() (Gumbel): the read-outs of mcts_query_slot,
+// kinds 1 + 10 / 7, through the tree's rows of the query buffers
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_pick(EngineParams ep, EngineArrays ar, SbArrays sb, SbPlayArrays pl, uint32_t n, float temp,
+                                                 float* out_f, uint32_t stride_f, uint32_t* out_u, uint32_t stride_u) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) { if (lane == 0) pl.move[slot] = -1; return; }
+  const uint32_t t = slot * GM::P;
+  if (ar.nodes[static_cast<size_t>(t) * ep.cap + ar.root[t]].n == 0) {      // pick_move of an all-zero vector: "this shouldn't be possible."
+    if (lane == 0) { pl.move[slot] = -1; sb.status[slot] = kSbNoVisits; }
+    return;
+  }
+  float* f = out_f + static_cast<size_t>(slot) * stride_f;
+  uint32_t* u = out_u + static_cast<size_t>(slot) * stride_u;
+  if (ep.gumbel_on) {
+    mcts_query_slot<GM>(ep, ar, slot, lane, kQGumbelFinal, 0.0f, 0u, f, u);
+  } else {
+    mcts_query_slot<GM>(ep, ar, slot, lane, kQProbs, temp, 0u, f, u);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // the slot state lane 0 stored is loaded again by every lane
+    mcts_query_slot<GM>(ep, ar, slot, lane, kQPickMove, 0.0f, 0u, f, u);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  if (lane == 0) pl.move[slot] = static_cast<int32_t>(u[0]);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_pick(EngineParams ep, EngineArrays ar, SbArrays sb, SbPlayArrays pl, uint32_t n, float temp,
+                                                    float* out_f, uint32_t stride_f, uint32_t* out_u, uint32_t stride_u) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) { if (lane == 0) pl.move[slot] = -1; return; }
+  const uint32_t t = slot * GM::P;
+  if (ar.N[static_cast<size_t>(t) * ep.cap + ar.root[t]] == 0) {
+    if (lane == 0) { pl.move[slot] = -1; sb.status[slot] = kSbNoVisits; }
+    return;
+  }
+  float* f = out_f + static_cast<size_t>(slot) * stride_f;
+  uint32_t* u = out_u + static_cast<size_t>(slot) * stride_u;
+  if (ep.gumbel_on) {
+    mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQGumbelFinal, 0.0f, 0u, f, u);
+  } else {
+    mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQProbs, temp, 0u, f, u);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQPickMove, 0.0f, 0u, f, u);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  if (lane == 0) pl.move[slot] = static_cast<int32_t>(u[0]);
+}
+
+// tree i advances by moves[i] (< 0: stays): update_root (which expands an unexpanded root first, as the reference does), the move
+// on the slot's root state, the marks of the nodes created here cleared (nif: only with K > 1), the move log, the finished rule.
+// A move the root does not have raises the engine's bit 32 and stops that tree alone (kSbBadMove); the host clears both.
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_update_root(EngineParams ep, EngineArrays ar, SbArrays sb, SbPlayArrays pl, uint32_t n,
+                                                        const int32_t* moves, uint32_t* nif) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) return;
+  const int32_t mv = moves[slot];
+  if (mv < 0) return;
+  SlotCtx<GM> c(ep, ar, slot, lane);
+  c.load();
+  const uint32_t bump0 = c.t_bump[0];
+  const bool ok = c.update_root(0, static_cast<uint32_t>(mv));
+  if (nif) for (uint32_t i = bump0 + lane; i < c.t_bump[0]; i += G) nif[c.tree_base(0) + i] = 0;
+  if (lane == 0) pl.move[slot] = -1;      // a pick is played once (every lane of the group has read its move above)
+  if (!ok) {
+    if (lane == 0) sb.status[slot] = kSbBadMove;
+    c.store(kSlotWaitEval);      // the root may have been expanded; the tree itself is where it was
+    return;
+  }
+  if (!GM::play(c.gs, static_cast<uint32_t>(mv))) {      // unreachable: a child of the root is a legal move.  Nothing is stored: the tree stops at its old root
+    if (lane == 0) sb.status[slot] = kSbBadState;
+    return;
+  }
+  c.cur = c.t_root[0]; c.plen = 0;
+  if (lane == 0) sb_after_move<GM>(sb, pl, slot, mv, c.gs);
+  c.store(kSlotWaitEval);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_update_root(EngineParams ep, EngineArrays ar, SbArrays sb, SbPlayArrays pl, uint32_t n,
+                                                           const int32_t* moves, uint32_t* nif) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) return;
+  const int32_t mv = moves[slot];
+  if (mv < 0) return;
+  BigSlot<GM> c(ep, ar, sm, slot, lane);
+  c.load();
+  const uint32_t bump0 = c.t_bump[0];
+  const bool ok = c.update_root(0, static_cast<uint32_t>(mv));
+  if (nif) for (uint32_t i = bump0 + lane; i < c.t_bump[0]; i += 64) nif[c.tree_base(0) + i] = 0;
+  if (lane == 0) pl.move[slot] = -1;      // a pick is played once (the wavefront has read its move above)
+  if (!ok) {
+    if (lane == 0) sb.status[slot] = kSbBadMove;
+    c.sync();
+    c.store(kSlotWaitEval);
+    return;
+  }
+  bool base_valid = true;
+  // unreachable behind a successful update_root for the Tafl family (false = a move the rules refuse, and a child of the root is
+  // legal); StarGambit: its position history is full.  Nothing is stored: the tree stops at its old root until the next reset
+  if (!c.step_state(c.gs, static_cast<uint32_t>(mv), c.game_list(), c.glen, base_valid, 0)) {
+    if (lane == 0) sb.status[slot] = kSbBadState;
+    return;
+  }
+  if constexpr (!is_stargambit<GM>::value) {   // the root's repetition list, as k_sb_big_seed writes it (whole list: a capture may have cleared it)
+    uint64_t* gl = ar.rep_list + static_cast<size_t>(slot) * (GM::MAX_TURNS + 2);
+    for (uint32_t i = lane; i < c.glen; i += 64) gl[i] = sm.glist[i];
+  }
+  if (lane == 0) {
+    if (ep.half_nodes) {      // ask k_compact to move the tree when its active half is filling up (k_mcts_big_update_root's rule)
+      const uint32_t b = c.t_bump[0];
+      if (b - ((b - 1) / ep.half_nodes) * ep.half_nodes > ep.compact_above) ar.compact_flag[slot * GM::P] = 1;
+    }
+    sb_after_move<GM>(sb, pl, slot, mv, c.gs);
+  }
+  c.cur = c.t_root[0]; c.plen = 0;      // no pending simulation for k_compact to re-point
+  c.sync();
+  c.store(kSlotWaitEval);
+}
+
+// MCTS::apply_root_policy_temp, then MCTS::add_root_noise, on the root of every live tree: what the reference does to a reused
+// root (play_manager.cc:523-555), through the read-out bodies of kinds 9 and 8
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_root_prior(EngineParams ep, EngineArrays ar, SbArrays sb, uint32_t n, uint32_t apply_temp, uint32_t noise,
+                                                       float* out_f, uint32_t stride_f, uint32_t* out_u, uint32_t stride_u) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n || sb.status[slot] != 0) return;
+  float* f = out_f + static_cast<size_t>(slot) * stride_f;
+  uint32_t* u = out_u + static_cast<size_t>(slot) * stride_u;
+  if (apply_temp) mcts_query_slot<GM>(ep, ar, slot, lane, kQApplyRootTemp, 0.0f, 0u, f, u);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // the priors and the slot state written above are read again below
+  if (noise) mcts_query_slot<GM>(ep, ar, slot, lane, kQAddRootNoise, 0.0f, 0u, f, u);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_root_prior(EngineParams ep, EngineArrays ar, SbArrays sb, uint32_t n, uint32_t apply_temp, uint32_t noise,
+                                                          float* out_f, uint32_t stride_f, uint32_t* out_u, uint32_t stride_u) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n || sb.status[slot] != 0) return;
+  float* f = out_f + static_cast<size_t>(slot) * stride_f;
+  uint32_t* u = out_u + static_cast<size_t>(slot) * stride_u;
+  if (apply_temp) mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQApplyRootTemp, 0.0f, 0u, f, u);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  if (noise) mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQAddRootNoise, 0.0f, 0u, f, u);
 }
 
 }  // namespace azmi

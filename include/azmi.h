@@ -348,7 +348,7 @@ int azmi_mcts_query(azmi_mcts* m, uint32_t kind, float temp, uint32_t arg, const
 
 /* ---- batched position search: `n_trees` independent MCTS trees, each on its own position, advanced together - what the
  * reference's evaluation tools do with a list of MCTS objects stepped in lock step, leaves batched into one net call and one
- * shared S3FIFOCache, no move played (frozen_eval.py:545-660, mcts_analysis.py:923-1049, play.py:292-343).  All five games.
+ * shared S3FIFOCache (frozen_eval.py:545-660, mcts_analysis.py:923-1049, play.py:292-343; moves: further down).  All five games.
  * Tree i is bit for bit the stand-alone azmi_mcts created with seed seeds[i] and driven call by call from the same position
  * with the same evaluator values.  Every tree runs exactly one simulation per step (a terminal leaf or a cache hit is one
  * too, mcts.cc:500-555), so a search of `visits` is `visits` step pairs.
@@ -404,6 +404,50 @@ int azmi_search_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, f
 int azmi_search_sync(azmi_search* s);
 int azmi_search_stats(azmi_search* s, uint64_t out[6]);
 int azmi_search_set_leaves_per_step(azmi_search* s, uint32_t k);
+/* ---- moves on a batched search: what the evaluation tools do between two searches of a game they walk (play.py:274-346,
+ * mcts_analysis.py:995-1051): pick a move, MCTS::update_root on every tree (mcts.cc:151-173), search the successor with the reused
+ * subtree.  The root state of every tree is advanced on the device; tree i stays bit for bit the stand-alone azmi_mcts driven by
+ * the same calls.  A tree whose game is over (a played move reached a terminal state) is FINISHED: every step skips it, its
+ * read-outs stay legal, it takes no further move.  A pending find_leaves step makes the four calls below that change the trees
+ * fail with AZMI_ERR_STATE; game_state is a read-out and stays legal.  A NULL handle is what a caller holds whose create
+ * failed: the five calls answer it with AZMI_ERR_NO_DEVICE on a machine without a HIP device (the reason create failed there) and
+ * with AZMI_ERR_INVALID on one with a device.
+ *   pick_moves    m.pick_move(m.probs(temp)) of every live tree, drawn from the tree's own stream (MCTS::probs mcts.cc:575-618,
+ *                 MCTS::pick_move mcts.cc:717-735); a Gumbel tree takes gumbel_final_action() (mcts.cc:375-401), no draw.  The
+ *                 moves stay on the device for update_roots(NULL); host_moves [n_trees] (may be NULL: nothing is read back,
+ *                 the call is asynchronous) receives them, -1 for a finished or stopped tree.  A root without visits takes no
+ *                 move: AZMI_ERR_STATE naming the tree at the next synchronising call; the tree is left as it was.
+ *   update_roots  MCTS::update_root(gs, move) (mcts.cc:151-173: an unexpanded root is expanded first; the Gumbel state is
+ *                 reset) + gs.play_move(move) on every live tree i with moves[i] >= 0, the move appended to the tree's log; a
+ *                 terminal successor finishes the tree.  host_moves NULL: the moves of the last pick_moves, asynchronous; a
+ *                 pick is played once (reset and update_roots leave "no move" behind, so without a new pick nothing moves).
+ *                 HOST array otherwise, and the call synchronises: a move the root does not have ("ahh, what is this move",
+ *                 mcts.cc:163) fails with AZMI_ERR_INVALID naming the tree; THAT tree is left where it was and stays live, the
+ *                 other trees' moves of the call are applied.  The wide games compact their arenas behind it (the PlayManager
+ *                 engine's k_compact: the live subtree moves to the idle half when the active one is filling up).
+ *   root_prior    MCTS::apply_root_policy_temp (mcts.cc:448-460) when apply_temp, then MCTS::add_root_noise (mcts.cc:403-446)
+ *                 when add_noise, on the root of every live tree: what PlayManager does to a reused root
+ *                 (play_manager.cc:523-555).  Asynchronous.
+ *   play          max_moves x { the steps of run(visits, root_noise), pick_moves(temp), update_roots(NULL), root_prior(root
+ *                 temperature != 1, root_noise) when either holds }: play.py:274-346's loop, enqueued on `stream` with nothing
+ *                 read back.  A move adds 2 launches to its search steps (3 for the wide games: the compaction; one more with
+ *                 the root prior), whatever n_trees is.
+ *   game_state    synchronises; HOST arrays, any may be NULL: status [n_trees] (0 live, 1 finished), log_len [n_trees], log
+ *                 [n_trees, cap] with cap = the game's max_turns + 8 (the moves played since reset; Connect4 42, Brandubh 150,
+ *                 Tawlbwrdd / OpenTafl 400, StarGambit 4096 turns), final_scores [n_trees, P+1] (GameState::scores() of a
+ *                 finished tree; rows of live trees are unspecified)
+ * The simulation budget.  max_simulations sizes the arena, and the two arena kinds differ.  Connect4's flat arena never reclaims:
+ * the budget counts every descent since reset(), the searches of all moves included (a game needs visits x moves).  The wide
+ * games' arenas have two halves and update_roots compacts them, reclaiming the discarded siblings (the PlayManager engine's
+ * rule): the budget counts the descents since the last update_roots that gave every tree a move and saw none refused.  run, find_leaves and play check it
+ * before they enqueue anything (AZMI_ERR_OVERFLOW; the message names the rule); `simulations` of stats counts everything since
+ * reset. */
+int azmi_search_pick_moves(azmi_search* s, float temp, int32_t* host_moves, void* stream);
+int azmi_search_update_roots(azmi_search* s, const int32_t* host_moves, void* stream);
+int azmi_search_root_prior(azmi_search* s, int apply_temp, int add_noise, void* stream);
+int azmi_search_play(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves, int root_noise,
+                     void* stream);
+int azmi_search_game_state(azmi_search* s, int32_t* status, uint32_t* log_len, int32_t* log, float* final_scores);
 
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
  *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------

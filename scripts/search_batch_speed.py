@@ -7,9 +7,15 @@
 for Connect4 (N positions x VISITS, the 6b64c bf16 net) and Tawlbwrdd (the configs/tawlbwrdd.yaml net).  Warm-up first, then
 the two versions alternate in one process; every time is taken around a device synchronise; median and spread are printed.
   python scripts/search_batch_speed.py [--game connect4|tawlbwrdd|both] [--n N] [--visits V] [--reps R] [--loop-reps L]
-                                       [--leaves-per-step K]
+                                       [--leaves-per-step K] [--play MOVES]
 One JSON line per game on stdout.  --leaves-per-step K > 1 times (a) with K leaves of every tree in flight per step (WU-UCT: a
-different search, so (b) is not run beside it); every line carries the steps, the time per step and the rows per net call."""
+different search, so (b) is not run beside it); every line carries the steps, the time per step and the rows per net call.
+
+--play MOVES times walking games instead of one search: (a) MCTSBatch.play(visits, net, max_moves=MOVES) - MOVES x (search, pick,
+update_roots) enqueued in one call - against (b) the same trees as stand-alone MCTS objects stepped from Python: one net.process
+per step, then pick_move(probs(1.0)) and update_root per object per move.  The equal-answers check compares the move logs of the
+two versions (defaults: 256 Connect4 positions x 64 visits x 8 moves with --play 8, 32 Tawlbwrdd positions x 64 visits x 4 moves
+with --play 4)."""
 import argparse
 import json
 import os
@@ -84,6 +90,90 @@ def run_loop(az, Game, states, seeds, visits, net, cpuct):
     return dt, calls, np.stack([m.counts() for m in trees])
 
 
+def run_play_batch(az, mb, states, seeds, visits, net, moves):
+    import torch
+    mb.reset(states, seeds=seeds)
+    torch.cuda.synchronize()
+    l0 = mb.stats()
+    t0 = time.perf_counter()
+    mb.play(visits, net=net, max_moves=moves)
+    mb.synchronize()
+    dt = time.perf_counter() - t0
+    l1 = mb.stats()
+    return dt, l1["launches"] - l0["launches"], l1["net_calls"] - l0["net_calls"], [l.tolist() for l in mb.move_logs()]
+
+
+def run_play_loop(az, Game, states, seeds, visits, net, cpuct, moves):
+    """The loop play() replaces: the trees as stand-alone objects, one net.process per step, update_root per object per move."""
+    import torch
+    P, M, chw = Game._info()
+    dev = torch.device("cuda", 0)
+    trees = [az.MCTS(cpuct, P, M, game=Game, seed=int(s), max_simulations=visits * moves) for s in seeds]
+    gss = [g.copy() for g in states]
+    logs = [[] for _ in trees]
+    dummy_v, dummy_pi = np.full(P + 1, 1.0 / (P + 1), np.float32), np.full(M, 1.0 / M, np.float32)
+    live = list(range(len(trees)))
+    torch.cuda.synchronize()
+    calls = 0
+    t0 = time.perf_counter()
+    for _ in range(moves):
+        for _ in range(visits):
+            leaves = {i: trees[i].find_leaf(gss[i]) for i in live}
+            need = [i for i in live if leaves[i].scores() is None]
+            calls += 2 * len(live)
+            if need:
+                batch = torch.from_numpy(np.stack([leaves[i].canonicalized() for i in need])).to(dev)
+                v, pi = net.process(batch)
+                v, pi = v.cpu().numpy(), pi.cpu().numpy()
+                calls += 1
+            row = {i: r for r, i in enumerate(need)}
+            for i in live:
+                if i in row:
+                    trees[i].process_result(gss[i], v[row[i]], pi[row[i]])
+                else:
+                    trees[i].process_result(gss[i], dummy_v, dummy_pi)
+                calls += 1
+        for i in live:
+            mv = trees[i].pick_move(trees[i].probs(1.0))
+            trees[i].update_root(gss[i], mv)
+            gss[i].play_move(mv)
+            logs[i].append(mv)
+            calls += 4                                            # probs, pick_move, update_root, the successor's replay (scores)
+        live = [i for i in live if gss[i].scores() is None]
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return dt, calls, logs
+
+
+def measure_play(az, name, n, visits, reps, loop_reps, moves):
+    from alphazero import torch_net
+    Game, spec, plies = {"connect4": (az.Connect4GS, torch_net.connect4_spec(), 12),
+                         "tawlbwrdd": (az.TawlbwrddGS, torch_net.tawlbwrdd_spec(), 6)}[name]
+    net = az.HipLeafNet(torch_net.random_init(spec, seed=0), spec, precision="bf16")
+    rng = np.random.default_rng(1)
+    states = positions(az, Game, n, rng, plies)
+    seeds = [1 + i for i in range(n)]
+    # Connect4's flat arena: every move's search counts; the wide games compact behind update_roots
+    mb = az.MCTSBatch(Game, n, 1.25, max_simulations=visits * moves if name == "connect4" else visits, seeds=seeds)
+    run_play_batch(az, mb, states, seeds, visits, net, moves)      # warm-up
+    a, b, launches, net_calls, loop_calls, same = [], [], 0, 0, 0, True
+    for which in ["a", "b"] * loop_reps + ["a"] * max(0, reps - loop_reps):
+        if which == "a":
+            dt, launches, net_calls, logs_a = run_play_batch(az, mb, states, seeds, visits, net, moves)
+            a.append(dt)
+        else:
+            dt, loop_calls, logs_b = run_play_loop(az, Game, states, seeds, visits, net, 1.25, moves)
+            b.append(dt)
+            same = same and logs_a == logs_b
+    rec = dict(mode="play", game=name, positions=n, visits=visits, moves=moves,
+               batch_s=dict(median=statistics.median(a), min=min(a), max=max(a), runs=len(a)),
+               batch_launches=launches, batch_net_calls=net_calls, finished=int(mb.finished().sum()))
+    if b:
+        rec.update(loop_s=dict(median=statistics.median(b), min=min(b), max=max(b), runs=len(b)), loop_device_calls=loop_calls,
+                   ratio=statistics.median(b) / statistics.median(a), same_move_logs=same)
+    print(json.dumps(rec), flush=True)
+
+
 def measure(az, name, n, visits, reps, loop_reps, leaves_per_step=1):
     from alphazero import torch_net
     Game, spec, plies = {"connect4": (az.Connect4GS, torch_net.connect4_spec(), 12),
@@ -121,15 +211,19 @@ def measure(az, name, n, visits, reps, loop_reps, leaves_per_step=1):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--game", default="both")
-    ap.add_argument("--n", type=int, default=0, help="positions (default: 1024 Connect4, 256 Tawlbwrdd)")
-    ap.add_argument("--visits", type=int, default=120)
+    ap.add_argument("--n", type=int, default=0, help="positions (default: 1024 Connect4, 256 Tawlbwrdd; with --play 256 and 32)")
+    ap.add_argument("--visits", type=int, default=0, help="default: 120, with --play 64")
+    ap.add_argument("--play", type=int, default=0, metavar="MOVES", help="time MCTSBatch.play over MOVES moves against the object loop")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop-reps", type=int, default=2, help="runs of the stand-alone-object loop (minutes each at full size; 0 = skip)")
     ap.add_argument("--leaves-per-step", type=int, default=1, help="K leaves of every tree in flight per step (1 = the plain search)")
     args = ap.parse_args()
     import alphazero as az
     for name in (["connect4", "tawlbwrdd"] if args.game == "both" else [args.game]):
-        measure(az, name, args.n or (1024 if name == "connect4" else 256), args.visits, args.reps, args.loop_reps, args.leaves_per_step)
+        if args.play:
+            measure_play(az, name, args.n or (256 if name == "connect4" else 32), args.visits or 64, args.reps, args.loop_reps, args.play)
+            continue
+        measure(az, name, args.n or (1024 if name == "connect4" else 256), args.visits or 120, args.reps, args.loop_reps, args.leaves_per_step)
 
 
 if __name__ == "__main__":
