@@ -594,7 +594,64 @@ class MCTSBatch:
     the same position both miss the cache and are both evaluated; search(visits) runs visits // K steps and one of
     visits % K descents; `max_simulations` and stats()["simulations"] count descents, stats()["steps"] counts steps.  After
     every completed step no in-flight mark is left.  Gumbel search needs K == 1 (the reference's batched descent is plain
-    PUCT, mcts.cc:752-784)."""
+    PUCT, mcts.cc:752-784).
+
+    The evaluator of search() / play(): `evaluator=None | "net" | "random" | "playout"` (or an EvalType member); None is the
+    net when one is given and RANDOM (dumb_eval) otherwise.  With "playout" every non-terminal leaf of tree i is evaluated on
+    the device as `alphazero.playout_eval(leaf, seed=s)` - the uniform policy over its legal moves, the scores of one
+    uniformly random rollout - and backed up by the unchanged process_result: the "playout" agent of play.py:306 and the
+    playout_eval_batch loops of mcts_analysis.py:649, with no net at all, for all five games.  Every rollout draws from a
+    fresh pcg32 stream, so a tree's result depends neither on n, on leaves_per_step's launch shape nor on the other trees:
+    the j-th rollout of tree i since reset() (j from 0, in descent order, running on across the moves of a game) has the
+    seed s = MCTSBatch.rollout_seed(rollout_seeds[i], j), and rollout_seeds[i] defaults to mix64(seeds[i] ^ kRollSalt)
+    (reset(..., rollout_seeds=...) sets them, rollout_seeds() reads them).  With leaves_per_step > 1 a playout leaf is an
+    immediate: its process_result_batched runs at once, in descent order, so the tree's next descent sees the back-up.  A
+    cache with "playout" is an error (the reference's playout branch bypasses the cache), as is "playout" or "random" with a
+    net and "net" without one.  stats()["evaluator_leaves"] counts the rollouts."""
+
+    _MASK64 = 0xFFFFFFFFFFFFFFFF
+    _ROLL_SALT = 0x9E3779B97F4A7C15      # kRollSalt, csrc/dev_rng.h
+
+    @staticmethod
+    def _mix64(x):                       # mix64, csrc/dev_rng.h
+        m = MCTSBatch._MASK64
+        x = (x + 0x9E3779B97F4A7C15) & m
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+        return x ^ (x >> 31)
+
+    @staticmethod
+    def rollout_seed(rollout_seed_i, j):
+        """The seed of the j-th rollout (j from 0) of a tree whose rollout seed is `rollout_seed_i`: playout_eval(leaf,
+        seed=MCTSBatch.rollout_seed(rs, j)) is that rollout.  Pure Python, no device."""
+        j = int(j)
+        if j < 0:
+            raise RuntimeError(f"rollout_seed: j counts from 0, got {j}")
+        m = MCTSBatch._MASK64
+        return MCTSBatch._mix64(((int(rollout_seed_i) & m) + MCTSBatch._ROLL_SALT * (j + 1)) & m)
+
+    @staticmethod
+    def _evaluator(what, evaluator, net, cache):
+        """-> the EvalType of a search()/play() call; every argument error before any device call"""
+        if evaluator is None:
+            return EvalType.NN if net is not None else EvalType.RANDOM
+        names = {"net": EvalType.NN, "random": EvalType.RANDOM, "playout": EvalType.PLAYOUT}
+        if isinstance(evaluator, str):
+            if evaluator not in names:
+                raise RuntimeError(f"{what}: evaluator must be None, 'net', 'random', 'playout' or an EvalType, got {evaluator!r}")
+            ev = names[evaluator]
+        elif isinstance(evaluator, EvalType):
+            ev = evaluator
+        else:
+            raise RuntimeError(f"{what}: evaluator must be None, 'net', 'random', 'playout' or an EvalType, got {evaluator!r}")
+        if ev == EvalType.NN and net is None:
+            raise RuntimeError(f"{what}: evaluator 'net' needs a net")
+        if ev != EvalType.NN and net is not None:
+            raise RuntimeError(f"{what}: evaluator '{ev.name.lower()}' takes no net")
+        if ev == EvalType.PLAYOUT and cache is not None:
+            raise RuntimeError(f"{what}: evaluator 'playout' takes no cache: the reference's playout branch bypasses it "
+                               "(a rollout's answer is not a function of the position)")
+        return ev
 
     def __init__(self, game, n, cpuct, epsilon=0.0, root_policy_temp=1.0, fpu_reduction=0.0, root_fpu_zero=False,
                  shaped_dirichlet=False, gumbel_enabled=False, gumbel_m=16, gumbel_c_visit=50.0, gumbel_c_scale=1.0,
@@ -633,16 +690,19 @@ class MCTSBatch:
     def __len__(self):
         return self._n
 
-    def _seed_array(self, seeds):
+    def _seed_array(self, seeds, what="seeds"):
         a = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
         if a.shape != (self._n,):
-            raise RuntimeError(f"seeds: one per tree ({self._n}), got {a.shape}")
+            raise RuntimeError(f"{what}: one per tree ({self._n}), got {a.shape}")
         return a
 
-    def reset(self, states, seeds=None):
+    def reset(self, states, seeds=None, rollout_seeds=None):
         """Positions + streams; the trees are emptied.  `states`: n GameState objects of the batch's game, any mix of positions.
-        `seeds` (default: the constructor's, else fresh random ones): tree i's stream is that of MCTS(seed=seeds[i])."""
+        `seeds` (default: the constructor's, else fresh random ones): tree i's stream is that of MCTS(seed=seeds[i]).
+        `rollout_seeds` (default: mix64(seeds[i] ^ kRollSalt)): the seeds of the "playout" evaluator's rollouts, whose
+        per-tree count starts again at 0."""
         states = list(states)
+        rs = None if rollout_seeds is None else self._seed_array(rollout_seeds, "rollout_seeds")
         if len(states) != self._n:
             raise RuntimeError(f"reset: {self._n} positions expected, got {len(states)}")
         for g in states:
@@ -666,18 +726,29 @@ class MCTSBatch:
         self._start = None
         check(lib.azmi_search_reset(self._h, None if init is None else init.ctypes.data, stride, moves.ctypes.data if moves.size else None,
                                     offs.ctypes.data, sd.ctypes.data))
+        if rs is not None:
+            check(lib.azmi_search_set_rollout_seeds(self._h, rs.ctypes.data))
+        self._roll = rs if rs is not None else np.array([self._mix64(int(x) ^ self._ROLL_SALT) for x in sd], dtype=np.uint64)
         self._start = [g.copy() for g in states]
 
-    def search(self, visits, net=None, cache=None, root_noise=False):
+    def rollout_seeds(self):
+        """uint64 [n]: the rollout seed of every tree since the last reset()."""
+        if self._start is None:
+            raise RuntimeError("rollout_seeds: the trees have no positions; call reset first")
+        return self._roll.copy()
+
+    def search(self, visits, net=None, cache=None, root_noise=False, evaluator=None):
         """`visits` simulations of every tree, enqueued without host synchronisation (the read-outs and synchronize() wait);
         with leaves_per_step = K: visits // K steps of K descents and one of visits % K.
-        net: a HipLeafNet (None = EvalType.RANDOM, dumb_eval); cache: a ShardedS3FIFOCache shared by all trees."""
+        net: a HipLeafNet (None = EvalType.RANDOM, dumb_eval); cache: a ShardedS3FIFOCache shared by all trees;
+        evaluator: None (the net if given, else RANDOM), "net", "random", "playout" or an EvalType - see the class."""
+        ev = self._evaluator("search", evaluator, net, cache)
         if net is not None and (net.desc.num_moves != self._M or (net.desc.in_channels, net.desc.height, net.desc.width) != self._chw):
             raise RuntimeError("search: the net's shape does not match the game")
         if cache is not None:
             cache._ensure_engine_layout()
-        check(lib.azmi_search_run(self._h, None if net is None else net._h, None if cache is None else cache._h, int(visits),
-                                  int(bool(root_noise)), C.c_void_p(-1)))
+        check(lib.azmi_search_run_eval(self._h, int(ev), None if net is None else net._h, None if cache is None else cache._h, int(visits),
+                                       int(bool(root_noise)), C.c_void_p(-1)))
 
     def synchronize(self):
         check(lib.azmi_search_sync(self._h))
@@ -705,16 +776,18 @@ class MCTSBatch:
     def add_root_noise(self): check(lib.azmi_search_root_prior(self._h, 0, 1, C.c_void_p(-1)))
     def apply_root_policy_temp(self): check(lib.azmi_search_root_prior(self._h, 1, 0, C.c_void_p(-1)))
 
-    def play(self, visits, net=None, cache=None, temp=1.0, max_moves=1, root_noise=False):
-        """max_moves x (search(visits, net, cache, root_noise); pick_moves(temp); update_roots(); on the reused root
+    def play(self, visits, net=None, cache=None, temp=1.0, max_moves=1, root_noise=False, evaluator=None):
+        """max_moves x (search(visits, net, cache, root_noise, evaluator); pick_moves(temp); update_roots(); on the reused root
         apply_root_policy_temp() when the root temperature is not 1 and add_root_noise() when root_noise), enqueued without
-        host synchronisation.  Finished trees are skipped, so `max_moves` of a game's length plays whole games."""
+        host synchronisation.  Finished trees are skipped, so `max_moves` of a game's length plays whole games.  The rollout
+        count of the "playout" evaluator runs on across the moves."""
+        ev = self._evaluator("play", evaluator, net, cache)
         if net is not None and (net.desc.num_moves != self._M or (net.desc.in_channels, net.desc.height, net.desc.width) != self._chw):
             raise RuntimeError("play: the net's shape does not match the game")
         if cache is not None:
             cache._ensure_engine_layout()
-        check(lib.azmi_search_play(self._h, None if net is None else net._h, None if cache is None else cache._h, int(visits), float(temp),
-                                   int(max_moves), int(bool(root_noise)), C.c_void_p(-1)))
+        check(lib.azmi_search_play_eval(self._h, int(ev), None if net is None else net._h, None if cache is None else cache._h, int(visits),
+                                        float(temp), int(max_moves), int(bool(root_noise)), C.c_void_p(-1)))
 
     def _game_state(self, log=False, final=False):
         cap = self._game.MAX_TURNS + 8

@@ -806,6 +806,16 @@ struct SlotCtx {
     sync_lanes();
     if (lane == 0) ar.roll[slot] = roll.state;
   }
+  // The same with a FRESH stream, seeded as k_playout seeds its own (the batched search's PLAYOUT evaluator: one stream per
+  // rollout, so that an answer does not depend on the shape of the batch).  The slot's rollout word carries the seeded state
+  // into the body above; every lane of the group stores the same word.
+  __device__ __forceinline__ void playout_eval(const typename GM::State& leaf, uint64_t seed) {
+    Pcg32 g;
+    g.seed(seed);
+    ar.roll[slot] = g.state;
+    sync_lanes();
+    playout_eval(leaf);
+  }
 
   // ---- lane-dense [M] vector helpers (lane m holds entry m) ------------------------------------
   template <class T>

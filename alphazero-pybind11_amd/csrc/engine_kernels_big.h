@@ -860,6 +860,23 @@ struct BigSlot {
     if (lane == 0) ar.roll[slot] = roll.state;
     sync();
   }
+  // The same with a FRESH stream, seeded as the stand-alone playout kernels seed theirs (the batched search's PLAYOUT
+  // evaluator: one stream per rollout), for a tree whose seat is not a PLAYOUT seat: process_result reads such a seat's
+  // priors from the slot's pi row, so the uniform policy of playout_eval is written there, at the moves of the leaf's
+  // children (expanded by find_leaf; `cur` is the leaf).  The slot's rollout word carries the seeded state into the body above.
+  __device__ __forceinline__ void playout_eval(const typename GM::State& leaf, uint64_t seed) {
+    Pcg32 g;
+    g.seed(seed);
+    ar.roll[slot] = g.state;      // every lane stores the same word
+    const size_t tb = tree_base(0);
+    const uint64_t meta = ar.META[tb + cur];
+    const uint32_t k = meta_nch(meta), c0 = meta_ch0(meta);
+    const float ksum = static_cast<float>(k & 0xFFu);      // Vector<uint8_t>::sum() wraps mod 256
+    for (uint32_t i = lane; i < k; i += G)
+      ar.pi[static_cast<size_t>(slot) * M + meta_mv(ar.META[tb + c0 + i])] = (ksum == 0.0f) ? 0.0f : 1.0f / ksum;
+    sync();
+    playout_eval(leaf);
+  }
 
   // ---- MCTS::process_result --------------------------------------------------------------------------------------------
   __device__ __forceinline__ void process_result(uint32_t seat, bool from_net, bool root_noise) {

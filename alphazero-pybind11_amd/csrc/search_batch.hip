@@ -6,6 +6,8 @@
 // root on the device (update_root with tree reuse) and cross moves without the host.
 // azmi_search_set_leaves_per_step(K > 1) switches every step to K descents per tree with K leaves in flight (WU-UCT): the *_wu
 // kernels and launch helpers below; K == 1 runs the original ones.
+// azmi_search_run_eval / play_eval with AZMI_EVAL_PLAYOUT evaluate every leaf by a random rollout on the device (the *_po kernels):
+// no compaction, no net call, no cache insert, at most 3 launches a step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,6 +54,9 @@ struct azmi_search {
   float* d_vrows_wu = nullptr;
   float* d_pirows_wu = nullptr;
   std::vector<void*> wu_allocs;
+  // EvalType::PLAYOUT: the rollout seed and rollout count of every tree, the parked leaf states of a Connect4 K == 1 step
+  SbRollArrays ro{};
+  std::vector<uint64_t> tree_seeds;   // seeds of the last reset: the default rollout seeds derive from them
 };
 
 namespace {
@@ -106,6 +111,10 @@ void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArr
     s->launches += 1;
   }
 }
+
+// EvalType::PLAYOUT steps (defined at the end of the file: kernels that are instantiated last leave the code objects of the others where they were)
+void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, hipStream_t st);
+void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st);
 
 // ---- K > 1: the same steps over K descents of every tree; the launch counts do not depend on N or K ---------------------------
 EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine arrays with the step-sized [K * N] row buffers in place
@@ -214,10 +223,20 @@ struct SearchArgs {
   EngineParams ep;
   EngineArrays ar;
   azmi_net* net = nullptr;
+  bool playout = false;
 };
-int search_args(azmi_search* s, azmi_net* net, azmi_cache* cache, SearchArgs* out) {
+// the evaluator of azmi_search_run_eval / play_eval: NN needs a net, RANDOM and PLAYOUT take none; PLAYOUT takes no cache either
+// (the reference's playout branch sits before the cache probe, play.py:306 / :320)
+int search_args(azmi_search* s, const char* what, int eval_type, azmi_net* net, azmi_cache* cache, SearchArgs* out) {
   azmi_pm* pm = s->pm;
-  out->ep = pm->ep; out->ar = pm->ar; out->net = net;
+  if (eval_type != AZMI_EVAL_NN && eval_type != AZMI_EVAL_RANDOM && eval_type != AZMI_EVAL_PLAYOUT)
+    return SB_FAIL(AZMI_ERR_INVALID, "%s: eval_type %d is none of NN, RANDOM, PLAYOUT", what, eval_type);
+  if (eval_type == AZMI_EVAL_NN && !net) return SB_FAIL(AZMI_ERR_INVALID, "%s: the NN evaluator needs a net", what);
+  if (eval_type != AZMI_EVAL_NN && net)
+    return SB_FAIL(AZMI_ERR_INVALID, "%s: the %s evaluator takes no net", what, eval_type == AZMI_EVAL_PLAYOUT ? "PLAYOUT" : "RANDOM");
+  if (eval_type == AZMI_EVAL_PLAYOUT && cache)
+    return SB_FAIL(AZMI_ERR_INVALID, "%s: the PLAYOUT evaluator takes no cache (a rollout's answer is not a function of the position)", what);
+  out->ep = pm->ep; out->ar = pm->ar; out->net = net; out->playout = eval_type == AZMI_EVAL_PLAYOUT;
   if (cache && net) {
     if (cache->device != pm->device) return SB_FAIL(AZMI_ERR_INVALID, "cache lives on another device");
     if (cache->c.np != pm->gi.M || cache->c.nv != pm->gi.P + 1) return SB_FAIL(AZMI_ERR_INVALID, "cache: num_policy / num_value do not match the game");
@@ -237,6 +256,21 @@ int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_
   azmi_net* net = a.net;
   int rc = AZMI_OK;
   if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
+  if (a.playout) {
+    if (s->k_leaves > 1) {
+      for (uint32_t left = visits; left;) {
+        const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
+        launch_step_playout_wu(s, ep, ar, kk, rn, st);
+        left -= kk; s->steps += 1;
+      }
+    } else {
+      for (uint32_t i = 0; i < visits; ++i) launch_step_playout(s, ep, ar, rn, st);
+      s->steps += visits;
+    }
+    SB_TRY(hipGetLastError());
+    s->sims_done += visits;
+    return AZMI_OK;
+  }
   if (s->k_leaves > 1) {
     // visits / K steps of K descents and one of the remainder, enqueued back to back like the K == 1 steps below
     const EngineArrays aw = wu_rows(s, ar);
@@ -380,6 +414,8 @@ int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, 
   if (rc == AZMI_OK) rc = A(s->d_qf, N * s->vec_f); if (rc == AZMI_OK) rc = A(s->d_qu, N * s->vec_u);
   if (rc == AZMI_OK) rc = A(s->pl.move, N); if (rc == AZMI_OK) rc = A(s->pl.log, N * s->pl.log_cap); if (rc == AZMI_OK) rc = A(s->pl.log_len, N);
   if (rc == AZMI_OK) rc = A(s->pl.final, N * (pm->gi.P + 1)); if (rc == AZMI_OK) rc = A(s->d_moves_in, N);
+  if (rc == AZMI_OK) rc = A(s->ro.seeds, N); if (rc == AZMI_OK) rc = A(s->ro.count, N);
+  if (rc == AZMI_OK) rc = A(s->ro.states, game == AZMI_GAME_CONNECT4 ? N * sizeof(Connect4::State) : 1);
   if (rc != AZMI_OK) { azmi_pm_destroy(pm); delete s; return rc; }
   *out = s;
   return AZMI_OK;
@@ -461,6 +497,9 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->stream;
   s->ready = false; s->step_pending = false; s->sims_done = 0;
+  s->tree_seeds.assign(seeds, seeds + n);
+  std::vector<uint64_t> roll(n);      // the default rollout seeds (azmi_search_set_rollout_seeds replaces them)
+  for (uint32_t i = 0; i < n; ++i) roll[i] = mix64(seeds[i] ^ kRollSalt);
   DevTemps tmp(16);
   uint8_t* d_init = nullptr; int32_t* d_moves = nullptr; uint32_t* d_offs = nullptr; uint64_t* d_seeds = nullptr;
   auto stage = [&]() -> hipError_t {      // uploads, resets and the seed launch, queued on st; the first error ends it
@@ -471,6 +510,8 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
     if (e == hipSuccess) e = hipMemsetAsync(pm->ar.ctl, 0, sizeof(Control), st);       // a stopped search does not outlive its positions
     if (e == hipSuccess) e = hipMemsetAsync(s->pl.log_len, 0, static_cast<size_t>(n) * 4, st);      // nor do the moves played on the old ones
     if (e == hipSuccess) e = hipMemsetAsync(s->pl.move, 0xFF, static_cast<size_t>(n) * 4, st);      // (-1: nothing picked yet)
+    if (e == hipSuccess) e = hipMemcpyAsync(s->ro.seeds, roll.data(), static_cast<size_t>(n) * 8, hipMemcpyHostToDevice, st);      // (st is synchronised below)
+    if (e == hipSuccess) e = hipMemsetAsync(s->ro.count, 0, static_cast<size_t>(n) * 4, st);
     if (e == hipSuccess && pm->ep.half_nodes) e = hipMemsetAsync(pm->ar.compact_flag, 0, static_cast<size_t>(n) * pm->gi.P * 4, st);
     if (e == hipSuccess && s->k_leaves > 1)     // the in-flight mark of every root (node 0 of its tree); every other node gets its mark cleared when it is created
       e = hipMemset2DAsync(s->wu.wu.nif, static_cast<size_t>(pm->gi.P) * pm->ep.cap * 4, 0, 4, n, st);
@@ -574,14 +615,29 @@ int azmi_search_process_results_host(azmi_search* s, const float* v, const float
   return AZMI_OK;
 }
 
-int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream) {
+int azmi_search_run_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream) {
   int rc = begin_step(s, "search"); if (rc) return rc;
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "search: a find_leaves step is pending; call process_results first");
   rc = check_budget(s, "search", visits); if (rc) return rc;
   SearchArgs a;
-  rc = search_args(s, net, cache, &a); if (rc) return rc;
+  rc = search_args(s, "search", eval_type, net, cache, &a); if (rc) return rc;
   SB_TRY(hipSetDevice(s->pm->device));
   return enqueue_search(s, a, visits, root_noise_enabled ? 1u : 0u, s->pm->pick(stream));
+}
+
+int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream) {
+  return azmi_search_run_eval(s, net ? AZMI_EVAL_NN : AZMI_EVAL_RANDOM, net, cache, visits, root_noise_enabled, stream);
+}
+
+int azmi_search_set_rollout_seeds(azmi_search* s, const uint64_t* seeds) {
+  int rc = begin_move(s, "set_rollout_seeds"); if (rc) return rc;
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  std::vector<uint64_t> roll(s->n);
+  for (uint32_t i = 0; i < s->n; ++i) roll[i] = seeds ? seeds[i] : mix64(s->tree_seeds[i] ^ kRollSalt);
+  SB_TRY(hipStreamSynchronize(pm->last));      // a search that is still running reads the old ones
+  SB_TRY(hipMemcpy(s->ro.seeds, roll.data(), static_cast<size_t>(s->n) * 8, hipMemcpyHostToDevice));
+  return AZMI_OK;
 }
 
 int azmi_search_pick_moves(azmi_search* s, float temp, int32_t* host_moves, void* stream) {
@@ -631,12 +687,17 @@ int azmi_search_root_prior(azmi_search* s, int apply_temp, int add_noise, void* 
 
 int azmi_search_play(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves, int root_noise,
                      void* stream) {
+  return azmi_search_play_eval(s, net ? AZMI_EVAL_NN : AZMI_EVAL_RANDOM, net, cache, visits, temp, max_moves, root_noise, stream);
+}
+
+int azmi_search_play_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves,
+                          int root_noise, void* stream) {
   int rc = begin_move(s, "play"); if (rc) return rc;
   // the whole call's budget before anything is enqueued: Connect4 counts every move's search; a wide game's first search comes on
   // top of the descents since the last update_roots, and every later one starts behind a compaction
   rc = check_budget(s, "play", s->flat_arena ? static_cast<uint64_t>(visits) * max_moves : (max_moves ? visits : 0u)); if (rc) return rc;
   SearchArgs a;
-  rc = search_args(s, net, cache, &a); if (rc) return rc;
+  rc = search_args(s, "play", eval_type, net, cache, &a); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
@@ -704,3 +765,28 @@ int azmi_search_stats(azmi_search* s, uint64_t out[6]) {
 }
 
 }  // extern "C"
+
+namespace {
+
+// ---- EvalType::PLAYOUT: rollouts on the device; see search_batch_kernels.h for the three step shapes ----------------------------
+void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, hipStream_t st) {
+  const uint32_t n = s->n;
+  sb_for_game(s->pm->game,
+              [&](auto tag) {
+                using GM = decltype(tag);
+                k_sb_find_po<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->ro, n);
+                k_sb_rollout<GM><<<(n + 63) / 64, 64, 0, st>>>(ar, s->sb, s->ro, n);
+                s->launches += 2;
+              },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_find_po<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->ro, n); s->launches += 1; });
+  launch_process(s, ep, ar, root_noise, nullptr, nullptr, st);
+}
+
+void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st) {
+  const uint32_t n = s->n;
+  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_find_wu_po<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->wu, s->ro, n, kk, root_noise); },
+              [&](auto tag) { using GM = decltype(tag); k_sb_big_find_wu_po<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->wu, s->ro, n, kk, root_noise); });
+  s->launches += 1;
+}
+
+}  // namespace

@@ -23,7 +23,8 @@ enum SbPend : uint8_t {
   kPendNone = 0,    // nothing to back up: terminal leaf (backed up by the find kernel), or a stopped tree
   kPendRow = 1,     // the leaf's planes are in the slot's canonical row: the evaluator's answer is awaited
   kPendCached = 2,  // a cache hit: the answer is already in the slot's (v, pi) rows
-  kPendRandom = 3   // EvalType::RANDOM: process_result synthesises dumb_eval
+  kPendRandom = 3,  // EvalType::RANDOM: process_result synthesises dumb_eval
+  kPendRollout = 4  // EvalType::PLAYOUT: the answer of the leaf's rollout is (Connect4: will be, behind k_sb_rollout) in the slot's (v, pi) rows
 };
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;
 
@@ -709,6 +710,199 @@ __global__ __launch_bounds__(64) void k_sb_big_root_prior(EngineParams ep, Engin
   if (apply_temp) mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQApplyRootTemp, 0.0f, 0u, f, u);
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   if (noise) mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQAddRootNoise, 0.0f, 0u, f, u);
+}
+
+// ======================= EvalType::PLAYOUT: every non-terminal leaf is evaluated by a random rollout on the device =================
+// alphazero.playout_eval(leaf, seed) (game_state.cc:10-95; play.py:306, mcts_analysis.py:649): the uniform policy over the leaf's
+// legal moves and the scores of one uniformly random rollout, backed up by the unchanged process_result.  Every rollout draws
+// from a FRESH pcg32 stream, so a tree's search depends neither on N, K nor on the launch geometry: the j-th rollout of tree i
+// since reset (j counts from 0, in descent order) is seeded sb_rollout_seed(seeds[i], j), the way k_playout seeds its own.
+// No compaction, no net call, no cache.
+//   Connect4, K == 1   k_sb_find_po parks the leaf state, k_sb_rollout runs ONE LANE per pending rollout (inside the find kernel
+//                      the 8 lanes of a tree's group would all play the same rollout), k_sb_process backs up: 3 launches a step
+//   wide games, K == 1 the rules are wave-cooperative and the rollout continues the descent's path-local repetition list, so it
+//                      runs in k_sb_big_find_po behind the descent; k_sb_big_process backs up: 2 launches a step
+//   K > 1              a playout leaf is an immediate: its process_result_batched runs before the tree's next descent, which has to
+//                      see the back-up and not the in-flight mark (play.py:306-307).  So the rollout sits between two descents of
+//                      one tree, inside the *_find_wu_po loop, and a step is 1 launch
+struct SbRollArrays {
+  uint64_t* seeds;     // [N] rollout_seeds
+  uint32_t* count;     // [N] rollouts of tree i since the last reset: the j of its next one
+  uint8_t* states;     // [N] GM::State (Connect4, K == 1): the leaf that awaits k_sb_rollout
+};
+__host__ __device__ __forceinline__ uint64_t sb_rollout_seed(uint64_t tree_seed, uint32_t j) {
+  return mix64(tree_seed + kRollSalt * (static_cast<uint64_t>(j) + 1));
+}
+
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_find_po(EngineParams ep, EngineArrays ar, SbArrays sb, SbRollArrays ro, uint32_t n) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) {
+    if (lane == 0) sb.pend[slot] = kPendNone;
+    return;
+  }
+  SlotCtx<GM> c(ep, ar, slot, lane);
+  c.load();
+  typename GM::State leaf;
+  uint32_t term = 0;
+  uint8_t pend = kPendNone;
+  if (!c.find_leaf(0, leaf, term)) {
+    if (lane == 0) sb.status[slot] = -2;
+  } else if (term != 0) {
+    c.process_result(0, true, false);
+    if (lane == 0) sb.n_term[slot] += 1;
+  } else {
+    if (lane == 0) { reinterpret_cast<typename GM::State*>(ro.states)[slot] = leaf; ar.c_evals[slot] += 1; }
+    pend = kPendRollout;
+  }
+  if (lane == 0) sb.pend[slot] = pend;
+  c.store(kSlotWaitEval);
+}
+
+// one lane per pending rollout: k_playout's body from the parked leaf state; the answer goes to the tree's (v, pi) rows, where
+// k_sb_process reads a net's
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_rollout(EngineArrays ar, SbArrays sb, SbRollArrays ro, uint32_t n) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n || sb.pend[g] != kPendRollout) return;
+  typename GM::State s = reinterpret_cast<const typename GM::State*>(ro.states)[g];
+  const uint32_t j = ro.count[g];
+  ro.count[g] = j + 1;
+  const uint32_t kl = GM::num_valid(s);
+  const float ksum = static_cast<float>(kl & 0xFFu);
+  for (int m = 0; m < GM::M; ++m)
+    ar.pi[static_cast<size_t>(g) * GM::M + m] = (((GM::valid_mask(s) >> m) & 1u) && ksum > 0.0f) ? 1.0f / ksum : 0.0f;
+  Pcg32 roll;
+  roll.seed(sb_rollout_seed(ro.seeds[g], j));
+  uint32_t term = GM::terminal(s);
+  while (term == 0) {
+    const uint32_t k = GM::num_valid(s);
+    if (k == 0) break;
+    GM::play(s, GM::nth_valid(s, lemire_below(roll, k)));
+    term = GM::terminal(s);
+  }
+  for (int i = 0; i <= GM::P; ++i)
+    ar.v[static_cast<size_t>(g) * (GM::P + 1) + i] = term ? ((static_cast<int>(term) - 1 == i) ? 1.0f : 0.0f) : static_cast<float>(1.0 / (GM::P + 1));
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_find_po(EngineParams ep, EngineArrays ar, SbArrays sb, SbRollArrays ro, uint32_t n) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n) return;
+  if (sb.status[slot] != 0) {
+    if (lane == 0) sb.pend[slot] = kPendNone;
+    return;
+  }
+  BigSlot<GM> c(ep, ar, sm, slot, lane);
+  c.load();
+  typename GM::State leaf;
+  uint32_t term = 0;
+  uint8_t pend = kPendNone;
+  if (!c.find_leaf(0, leaf, term)) {
+    if (lane == 0) sb.status[slot] = -2;
+  } else if (term != 0) {
+    c.process_result(0, true, false);
+    if (lane == 0) sb.n_term[slot] += 1;
+  } else {
+    const uint32_t j = ro.count[slot];
+    c.playout_eval(leaf, sb_rollout_seed(ro.seeds[slot], j));      // (ends with the wavefront's fence: every lane has read j)
+    if (lane == 0) { ro.count[slot] = j + 1; ar.c_evals[slot] += 1; }
+    pend = kPendRollout;
+  }
+  if (lane == 0) sb.pend[slot] = pend;
+  c.sync();
+  c.store(kSlotWaitEval);
+}
+
+// K > 1: `kk` <= K x (find_leaf_batched, the rollout of a non-terminal leaf, process_result_batched at once).  Every descent is
+// backed up here, so no in-flight record and no pending entry is left behind; entry k * N + i still holds the (v, pi) rows of
+// descent k of tree i, as for the other evaluators
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_find_wu_po(EngineParams ep, EngineArrays ar, SbArrays sb, SbWuArrays w, SbRollArrays ro, uint32_t n,
+                                                       uint32_t kk, uint32_t root_noise) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n || sb.status[slot] != 0) return;
+  EngineArrays al = ar;
+  SlotCtx<GM> c(ep, al, slot, lane);
+  c.load();
+  uint32_t* nif = w.wu.nif + c.tree_base(0);
+  const uint32_t* path = ar.path + static_cast<size_t>(slot) * ep.max_depth;
+  const uint64_t tree_seed = ro.seeds[slot];
+  uint32_t j = ro.count[slot], n_term = 0;
+  const uint32_t j0 = j;
+  for (uint32_t k = 0; k < kk; ++k) {
+    sb_wu_point(al, w, static_cast<size_t>(k) * n, GM::CANON, GM::P + 1, GM::M);
+    typename GM::State leaf;
+    uint32_t term = 0;
+    if (!c.find_leaf_wu(0, leaf, term, nif)) {      // the tree stops (reset() clears the root's mark, new nodes get theirs cleared)
+      if (lane == 0) sb.status[slot] = -2;
+      break;
+    }
+    if (term != 0) ++n_term;
+    else c.playout_eval(leaf, sb_rollout_seed(tree_seed, j++));
+    if (lane == 0) { --nif[c.cur]; for (uint32_t i = 0; i < c.plen; ++i) --nif[path[i]]; }
+    c.sync_lanes();
+    c.process_result(0, true, term == 0 && root_noise != 0);
+  }
+  if (lane == 0) { ro.count[slot] = j; ar.c_evals[slot] += j - j0; sb.n_term[slot] += n_term; }
+  c.store(kSlotWaitEval);
+}
+
+// find_leaf leaves the path-local repetition bookkeeping of its descent in leaf_rep_len / leaf_base_valid for the rollout;
+// find_leaf_wu keeps it to itself, so the recorded path is played once more (a few moves next to the rollout's many)
+template <class GM>
+__device__ __forceinline__ void sb_big_replay_path(BigSlot<GM>& c, const uint32_t* path) {
+  typename GM::State st = c.gs;
+  const size_t tb = c.tree_base(0);
+  uint32_t len = 0;
+  bool base_valid = true;
+  for (uint32_t i = 0; i < c.plen; ++i) {
+    const uint32_t node = (i + 1 < c.plen) ? path[i + 1] : c.cur;
+    if (!c.step_state(st, meta_mv(c.ar.META[tb + node]), c.path_list(), len, base_valid, c.glen)) break;      // (find_leaf_wu took every one of them)
+  }
+  c.leaf_rep_len = len; c.leaf_base_valid = base_valid;
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_find_wu_po(EngineParams ep, EngineArrays ar, SbArrays sb, SbWuArrays w, SbRollArrays ro, uint32_t n,
+                                                          uint32_t kk, uint32_t root_noise) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n || sb.status[slot] != 0) return;
+  EngineArrays al = ar;
+  BigSlot<GM> c(ep, al, sm, slot, lane);
+  c.load();
+  uint32_t* nif = w.wu.nif + c.tree_base(0);
+  const uint32_t* path = ar.path + static_cast<size_t>(slot) * ep.max_depth;
+  const uint64_t tree_seed = ro.seeds[slot];
+  uint32_t j = ro.count[slot], n_term = 0;
+  const uint32_t j0 = j;
+  for (uint32_t k = 0; k < kk; ++k) {
+    sb_wu_point(al, w, static_cast<size_t>(k) * n, GM::CANON, GM::P + 1, GM::M);
+    typename GM::State leaf;
+    uint32_t term = 0;
+    if (!c.find_leaf_wu(0, leaf, term, nif)) {
+      if (lane == 0) sb.status[slot] = -2;
+      break;
+    }
+    if (term != 0) ++n_term;
+    else {
+      sb_big_replay_path(c, path);
+      c.playout_eval(leaf, sb_rollout_seed(tree_seed, j++));
+    }
+    if (lane == 0) { --nif[c.cur]; for (uint32_t i = 0; i < c.plen; ++i) --nif[path[i]]; }
+    c.sync();
+    c.process_result(0, true, term == 0 && root_noise != 0);
+  }
+  c.sync();
+  if (lane == 0) { ro.count[slot] = j; ar.c_evals[slot] += j - j0; sb.n_term[slot] += n_term; }
+  c.store(kSlotWaitEval);
 }
 
 }  // namespace azmi

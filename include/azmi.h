@@ -448,6 +448,28 @@ int azmi_search_root_prior(azmi_search* s, int apply_temp, int add_noise, void* 
 int azmi_search_play(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves, int root_noise,
                      void* stream);
 int azmi_search_game_state(azmi_search* s, int32_t* status, uint32_t* log_len, int32_t* log, float* final_scores);
+/* ---- the evaluator of a batched search named outright, EvalType::PLAYOUT among them (play.py:306, mcts_analysis.py:649,
+ * game_state.cc:10-95).  run_eval / play_eval are run / play with eval_type (azmi_eval_type): AZMI_EVAL_NN needs a net,
+ * AZMI_EVAL_RANDOM and AZMI_EVAL_PLAYOUT take none, AZMI_EVAL_PLAYOUT takes no cache either (the reference's playout branch sits
+ * before its cache probe); anything else is AZMI_ERR_INVALID before a launch.  run / play are these with NN when a net is given and
+ * RANDOM otherwise.  The step API (find_leaves / process_results) is the same for every evaluator.
+ *   AZMI_EVAL_PLAYOUT   every non-terminal leaf is evaluated as azmi_playout_eval evaluates it - the uniform policy over its legal
+ *                 moves (u8 sum wrap of dumb_eval), the scores of one uniformly random rollout, 1 / (P + 1) each if the rollout
+ *                 cannot reach an end - on the device, and backed up by the unchanged process_result.  Every rollout has a FRESH
+ *                 pcg32 stream, so a tree's result does not depend on n_trees, on leaves_per_step's launch shape or on the other
+ *                 trees: the j-th rollout of tree i since reset (j from 0, in descent order, running on across moves) is seeded
+ *                 mix64(rollout_seeds[i] + 0x9E3779B97F4A7C15 * (j + 1)) the way azmi_playout_eval seeds its stream from seeds[g],
+ *                 with mix64 the splitmix64 finaliser of x + 0x9E3779B97F4A7C15.  With leaves_per_step > 1 a playout leaf is an
+ *                 immediate: its process_result_batched runs at once, in descent order, before the tree's next descent
+ *                 (play.py:306-307).  No compaction, no net call, no cache insert: a step is at most 3 launches whatever
+ *                 n_trees and leaves_per_step are.  `leaves given to the evaluator` of stats counts the rollouts.
+ *   set_rollout_seeds   rollout_seeds[i] of every tree from a HOST array [n_trees]; NULL: the default, which every reset
+ *                 restores, mix64(seeds[i] ^ 0x9E3779B97F4A7C15) of the reset's seeds.  After a reset; the rollout counts are
+ *                 the reset's to clear.  Synchronises. */
+int azmi_search_run_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream);
+int azmi_search_play_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves,
+                          int root_noise, void* stream);
+int azmi_search_set_rollout_seeds(azmi_search* s, const uint64_t* seeds);
 
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
  *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------

@@ -7,7 +7,7 @@
 for Connect4 (N positions x VISITS, the 6b64c bf16 net) and Tawlbwrdd (the configs/tawlbwrdd.yaml net).  Warm-up first, then
 the two versions alternate in one process; every time is taken around a device synchronise; median and spread are printed.
   python scripts/search_batch_speed.py [--game connect4|tawlbwrdd|both] [--n N] [--visits V] [--reps R] [--loop-reps L]
-                                       [--leaves-per-step K] [--play MOVES]
+                                       [--leaves-per-step K] [--play MOVES] [--evaluator net|playout]
 One JSON line per game on stdout.  --leaves-per-step K > 1 times (a) with K leaves of every tree in flight per step (WU-UCT: a
 different search, so (b) is not run beside it); every line carries the steps, the time per step and the rows per net call.
 
@@ -15,7 +15,14 @@ different search, so (b) is not run beside it); every line carries the steps, th
 update_roots) enqueued in one call - against (b) the same trees as stand-alone MCTS objects stepped from Python: one net.process
 per step, then pick_move(probs(1.0)) and update_root per object per move.  The equal-answers check compares the move logs of the
 two versions (defaults: 256 Connect4 positions x 64 visits x 8 moves with --play 8, 32 Tawlbwrdd positions x 64 visits x 4 moves
-with --play 4)."""
+with --play 4).
+
+--evaluator playout times the PLAYOUT evaluator instead of the net: (a) MCTSBatch.search(visits, evaluator="playout") - the
+rollouts on the device - against (b) the loop it replaces (mcts_analysis.py:649): the same trees as MCTS objects stepped from
+Python, one playout_eval_batch(leaves, seeds) per step, with the seeds of (a) (MCTSBatch.rollout_seed), so that the counts of every
+pair are compared.  With --leaves-per-step K > 1 (b) is the batched object calls, every leaf's playout_eval answered at once.
+Without --n / --visits it runs the four workloads of DESIGN.md 8.3: Connect4 1024 x 120, Connect4 16 x 1600 at K = 1 and K = 8,
+Tawlbwrdd 64 x 64."""
 import argparse
 import json
 import os
@@ -88,6 +95,87 @@ def run_loop(az, Game, states, seeds, visits, net, cpuct):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return dt, calls, np.stack([m.counts() for m in trees])
+
+
+def run_playout_batch(az, mb, states, seeds, visits):
+    import torch
+    mb.reset(states, seeds=seeds)
+    torch.cuda.synchronize()
+    l0 = mb.stats()
+    t0 = time.perf_counter()
+    mb.search(visits, evaluator="playout")
+    mb.synchronize()
+    dt = time.perf_counter() - t0
+    l1 = mb.stats()
+    return dt, l1["launches"] - l0["launches"], l1["steps"] - l0["steps"], l1["evaluator_leaves"], mb.counts()
+
+
+def run_playout_loop(az, Game, states, seeds, rs, visits, cpuct, K):
+    """The loop the device rollouts replace: MCTS objects stepped from Python, one playout_eval_batch per step (K == 1); K > 1: the
+    batched object calls with every leaf's playout_eval answered at once, in descent order.  Object creation is not timed."""
+    import torch
+    P, M, chw = Game._info()
+    trees = [az.MCTS(cpuct, P, M, game=Game, seed=int(s), max_simulations=visits) for s in seeds]
+    dummy_v, dummy_pi = np.full(P + 1, 1.0 / (P + 1), np.float32), np.full(M, 1.0 / M, np.float32)
+    j = [0] * len(trees)
+    seed_of = az.MCTSBatch.rollout_seed
+    torch.cuda.synchronize()
+    calls = 0
+    t0 = time.perf_counter()
+    if K == 1:
+        for _ in range(visits):
+            leaves = [m.find_leaf(gs) for m, gs in zip(trees, states)]
+            live = [i for i, leaf in enumerate(leaves) if leaf.scores() is None]
+            calls += 2 * len(trees)
+            if live:
+                v, pi = az.playout_eval_batch([leaves[i] for i in live], [seed_of(rs[i], j[i]) for i in live])
+                calls += 1
+            row = {i: r for r, i in enumerate(live)}
+            for i, (m, gs) in enumerate(zip(trees, states)):
+                if i in row:
+                    m.process_result(gs, v[row[i]], pi[row[i]]); j[i] += 1
+                else:
+                    m.process_result(gs, dummy_v, dummy_pi)
+                calls += 1
+    else:
+        for left in range(visits, 0, -K):
+            for i, (m, gs) in enumerate(zip(trees, states)):
+                for k in range(min(K, left)):
+                    leaf = m.find_leaf_batched(gs)
+                    v, pi = (dummy_v, dummy_pi) if leaf.scores() is not None else az.playout_eval(leaf, seed=seed_of(rs[i], j[i]))
+                    j[i] += leaf.scores() is None
+                    m.process_result_batched(gs, k, v, pi)
+                    calls += 4
+                m.reset_batch()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return dt, calls, np.stack([m.counts() for m in trees])
+
+
+def measure_playout(az, name, n, visits, reps, loop_reps, K):
+    Game, plies = {"connect4": (az.Connect4GS, 12), "tawlbwrdd": (az.TawlbwrddGS, 6)}[name]
+    rng = np.random.default_rng(1)
+    states = positions(az, Game, n, rng, plies)
+    seeds = [1 + i for i in range(n)]
+    mb = az.MCTSBatch(Game, n, 1.25, max_simulations=visits, seeds=seeds, leaves_per_step=K)
+    run_playout_batch(az, mb, states, seeds, visits)               # warm-up
+    rs = [int(x) for x in mb.rollout_seeds()]
+    a, b, launches, steps, rollouts, loop_calls, same = [], [], 0, 1, 0, 0, True
+    for which in ["a", "b"] * loop_reps + ["a"] * max(0, reps - loop_reps):
+        if which == "a":
+            dt, launches, steps, rollouts, counts_a = run_playout_batch(az, mb, states, seeds, visits)
+            a.append(dt)
+        else:
+            dt, loop_calls, counts_b = run_playout_loop(az, Game, states, seeds, rs, visits, 1.25, K)
+            b.append(dt)
+            same = same and bool(np.array_equal(counts_a, counts_b))
+    rec = dict(mode="playout", game=name, positions=n, visits=visits, leaves_per_step=K,
+               batch_s=dict(median=statistics.median(a), min=min(a), max=max(a), runs=len(a)),
+               batch_launches=launches, steps=steps, rollouts=rollouts, step_us=1e6 * statistics.median(a) / steps)
+    if b:
+        rec.update(loop_s=dict(median=statistics.median(b), min=min(b), max=max(b), runs=len(b)), loop_device_calls=loop_calls,
+                   ratio=statistics.median(b) / statistics.median(a), same_counts=same)
+    print(json.dumps(rec), flush=True)
 
 
 def run_play_batch(az, mb, states, seeds, visits, net, moves):
@@ -217,8 +305,20 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop-reps", type=int, default=2, help="runs of the stand-alone-object loop (minutes each at full size; 0 = skip)")
     ap.add_argument("--leaves-per-step", type=int, default=1, help="K leaves of every tree in flight per step (1 = the plain search)")
+    ap.add_argument("--evaluator", default="net", choices=["net", "playout"], help="playout: rollouts on the device against the playout_eval_batch loop")
     args = ap.parse_args()
     import alphazero as az
+    if args.evaluator == "playout":
+        if args.play:
+            ap.error("--evaluator playout times search(), not --play")
+        if args.n or args.visits:
+            for name in (["connect4", "tawlbwrdd"] if args.game == "both" else [args.game]):
+                measure_playout(az, name, args.n or 64, args.visits or 64, args.reps, args.loop_reps, args.leaves_per_step)
+            return
+        for name, n, visits, K in (("connect4", 1024, 120, 1), ("connect4", 16, 1600, 1), ("connect4", 16, 1600, 8), ("tawlbwrdd", 64, 64, 1)):
+            if args.game in ("both", name):
+                measure_playout(az, name, n, visits, args.reps, args.loop_reps, K)
+        return
     for name in (["connect4", "tawlbwrdd"] if args.game == "both" else [args.game]):
         if args.play:
             measure_play(az, name, args.n or (256 if name == "connect4" else 32), args.visits or 64, args.reps, args.loop_reps, args.play)
