@@ -76,36 +76,36 @@ void sb_for_game(int game, Small&& small, Big&& big) {
   }
 }
 
+// one launch of a step over the s->n trees: Connect4's kernel on its 8-lane groups, the wide games' on one wavefront per tree
+#define SB_LAUNCH(s, st, k_small, k_big, ...)                                                                                              \
+  do {                                                                                                                                     \
+    sb_for_game((s)->pm->game,                                                                                                             \
+                [&](auto tag) { using GM = decltype(tag); k_small<GM><<<small_blocks((s)->n), kSmallThreads, 0, st>>>(__VA_ARGS__); },     \
+                [&](auto tag) { using GM = decltype(tag); k_big<GM><<<(s)->n, 64, 0, st>>>(__VA_ARGS__); });                               \
+    (s)->launches += 1;                                                                                                                    \
+  } while (0)
+
 void launch_find(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t eval_random, hipStream_t st) {
-  const uint32_t n = s->n;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_find<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, eval_random); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_find<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, eval_random); });
-  k_sb_compact<<<1, 1024, 0, st>>>(s->sb, n);
-  s->launches += 2;
+  SB_LAUNCH(s, st, k_sb_find, k_sb_big_find, ep, ar, s->sb, s->n, eval_random);
+  k_sb_compact<<<1, 1024, 0, st>>>(s->sb, s->n);
+  s->launches += 1;
 }
 
 void launch_process(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, const float* v_rows, const float* pi_rows,
                     hipStream_t st) {
-  const uint32_t n = s->n;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_process<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_process<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, root_noise, v_rows, pi_rows); });
-  s->launches += 1;
+  SB_LAUNCH(s, st, k_sb_process, k_sb_big_process, ep, ar, s->sb, s->n, root_noise, v_rows, pi_rows);
 }
 
 void launch_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, hipStream_t st) {
-  const uint32_t n = s->n;
-  const EngineParams& ep = s->pm->ep;
-  const EngineArrays& ar = s->pm->ar;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_query<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_query<GM><<<n, 64, 0, st>>>(ep, ar, n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u); });
-  s->launches += 1;
+  SB_LAUNCH(s, st, k_sb_query, k_sb_big_query, s->pm->ep, s->pm->ar, s->n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
 }
 
 // the answers of the step's net call go into the cache (PlayManager::update_inferences -> insert_many, play_manager.cc:631-640):
-// keys left by the find kernel, slot-indexed (pi, v) rows; ceil(N / kApplyMax) launches
-void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, hipStream_t st) {
-  for (uint32_t off = 0; off < s->n; off += kApplyMax) {
-    const uint32_t m = std::min<uint32_t>(kApplyMax, s->n - off);
+// keys left by the find kernel in ar.cache_keys, (pi, v) rows indexed like them; `total` = N entries (K > 1: the kk * N of the
+// step, `ar` = wu_rows); ceil(total / kApplyMax) launches
+void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t total, hipStream_t st) {
+  for (uint32_t off = 0; off < total; off += kApplyMax) {
+    const uint32_t m = std::min<uint32_t>(kApplyMax, total - off);
     auto insert = [&](auto tag) { using GM = decltype(tag); k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u); };
     sb_for_game(s->pm->game, insert, insert);
     s->launches += 1;
@@ -123,31 +123,14 @@ EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine 
 }
 
 void launch_find_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t eval_random, uint32_t root_noise, hipStream_t st) {
-  const uint32_t n = s->n;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_find_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_find_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->wu, n, kk, eval_random, root_noise); });
-  k_sb_compact_wu<<<1, 1024, 0, st>>>(s->sb, s->wu, n, kk);
-  s->launches += 2;
+  SB_LAUNCH(s, st, k_sb_find_wu, k_sb_big_find_wu, ep, ar, s->sb, s->wu, s->n, kk, eval_random, root_noise);
+  k_sb_compact_wu<<<1, 1024, 0, st>>>(s->sb, s->wu, s->n, kk);
+  s->launches += 1;
 }
 
 void launch_process_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, const float* v_rows,
                        const float* pi_rows, hipStream_t st) {
-  const uint32_t n = s->n;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_process_wu<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_process_wu<GM><<<n, 64, 0, st>>>(ep, ar, s->wu, n, kk, root_noise, v_rows, pi_rows); });
-  s->launches += 1;
-}
-
-// as launch_cache_insert, over the kk * N entries of the step: ceil(N * kk / kApplyMax) launches
-void launch_cache_insert_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, hipStream_t st) {
-  const EngineArrays aw = wu_rows(s, ar);
-  const uint32_t total = s->n * kk;
-  for (uint32_t off = 0; off < total; off += kApplyMax) {
-    const uint32_t m = std::min<uint32_t>(kApplyMax, total - off);
-    auto insert = [&](auto tag) { using GM = decltype(tag); k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, aw, aw.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u); };
-    sb_for_game(s->pm->game, insert, insert);
-    s->launches += 1;
-  }
+  SB_LAUNCH(s, st, k_sb_process_wu, k_sb_big_process_wu, ep, ar, s->wu, s->n, kk, root_noise, v_rows, pi_rows);
 }
 
 void wu_free(azmi_search* s) {
@@ -281,7 +264,7 @@ int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_
         rc = azmi_net_forward_rows(net, aw.canon, aw.v, aw.pi, s->wu.rows, s->sb.n_rows, s->n * kk, st);
         if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
         s->net_calls += 1;
-        if (ep.cache_on) launch_cache_insert_wu(s, ep, ar, kk, st);
+        if (ep.cache_on) launch_cache_insert(s, ep, aw, s->n * kk, st);
       }
       launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
       left -= kk; s->steps += 1;
@@ -297,7 +280,7 @@ int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_
       rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
       if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
       s->net_calls += 1;
-      if (ep.cache_on) launch_cache_insert(s, ep, ar, st);
+      if (ep.cache_on) launch_cache_insert(s, ep, ar, s->n, st);
     }
     launch_process(s, ep, ar, rn, nullptr, nullptr, st);
   }
@@ -308,36 +291,21 @@ int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_
 
 // ---- a move: pick, update-root (+ compaction for the wide games), root prior; one launch each, whatever N is ------------------
 void launch_pick(azmi_search* s, float temp, hipStream_t st) {
-  const uint32_t n = s->n;
-  const EngineParams& ep = s->pm->ep;
-  const EngineArrays& ar = s->pm->ar;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_pick<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->pl, n, temp, s->d_qf, s->vec_f, s->d_qu, s->vec_u); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_pick<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->pl, n, temp, s->d_qf, s->vec_f, s->d_qu, s->vec_u); });
-  s->launches += 1;
+  SB_LAUNCH(s, st, k_sb_pick, k_sb_big_pick, s->pm->ep, s->pm->ar, s->sb, s->pl, s->n, temp, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
 }
 
 // `moves`: [N] on the device.  The wide games compact behind it (k_compact lives in engine.hip's device module)
 void launch_update_root(azmi_search* s, const int32_t* moves, hipStream_t st) {
-  const uint32_t n = s->n;
-  const EngineParams& ep = s->pm->ep;
-  const EngineArrays& ar = s->pm->ar;
   uint32_t* nif = s->k_leaves > 1 ? s->wu.wu.nif : nullptr;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_update_root<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->pl, n, moves, nif); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_update_root<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->pl, n, moves, nif); });
-  s->launches += 1;
-  if (ep.half_nodes) {
-    azmi_host_launch_compact(s->pm, st, n * s->pm->gi.P, nif);
+  SB_LAUNCH(s, st, k_sb_update_root, k_sb_big_update_root, s->pm->ep, s->pm->ar, s->sb, s->pl, s->n, moves, nif);
+  if (s->pm->ep.half_nodes) {
+    azmi_host_launch_compact(s->pm, st, s->n * s->pm->gi.P, nif);
     s->launches += 1;
   }
 }
 
 void launch_root_prior(azmi_search* s, uint32_t apply_temp, uint32_t noise, hipStream_t st) {
-  const uint32_t n = s->n;
-  const EngineParams& ep = s->pm->ep;
-  const EngineArrays& ar = s->pm->ar;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_root_prior<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, n, apply_temp, noise, s->d_qf, s->vec_f, s->d_qu, s->vec_u); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_root_prior<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, n, apply_temp, noise, s->d_qf, s->vec_f, s->d_qu, s->vec_u); });
-  s->launches += 1;
+  SB_LAUNCH(s, st, k_sb_root_prior, k_sb_big_root_prior, s->pm->ep, s->pm->ar, s->sb, s->n, apply_temp, noise, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
 }
 
 // A NULL handle is what a caller holds whose create failed.  On a machine without a device that failure was the no-device one, and
@@ -516,9 +484,7 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
     if (e == hipSuccess && s->k_leaves > 1)     // the in-flight mark of every root (node 0 of its tree); every other node gets its mark cleared when it is created
       e = hipMemset2DAsync(s->wu.wu.nif, static_cast<size_t>(pm->gi.P) * pm->ep.cap * 4, 0, 4, n, st);
     if (e != hipSuccess) return e;
-    sb_for_game(pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_seed<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds); },
-                [&](auto tag) { using GM = decltype(tag); k_sb_big_seed<GM><<<n, 64, 0, st>>>(pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds); });
-    s->launches += 1;
+    SB_LAUNCH(s, st, k_sb_seed, k_sb_big_seed, pm->ep, pm->ar, s->sb, n, d_init, init_stride, d_moves, d_offs, d_seeds);
     return hipGetLastError();
   };
   const hipError_t e = stage();
@@ -783,10 +749,7 @@ void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArr
 }
 
 void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st) {
-  const uint32_t n = s->n;
-  sb_for_game(s->pm->game, [&](auto tag) { using GM = decltype(tag); k_sb_find_wu_po<GM><<<small_blocks(n), kSmallThreads, 0, st>>>(ep, ar, s->sb, s->wu, s->ro, n, kk, root_noise); },
-              [&](auto tag) { using GM = decltype(tag); k_sb_big_find_wu_po<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->wu, s->ro, n, kk, root_noise); });
-  s->launches += 1;
+  SB_LAUNCH(s, st, k_sb_find_wu_po, k_sb_big_find_wu_po, ep, ar, s->sb, s->wu, s->ro, s->n, kk, root_noise);
 }
 
 }  // namespace

@@ -7,13 +7,16 @@
 // driven by the same per-tree functions: SlotCtx / BigSlot load, find_leaf, process_result, cache_lookup, emit_leaf, and the
 // read-outs of mcts_query_slot.  The kernels here only map the grid to slots and keep the per-tree bookkeeping of a step:
 //   pend[i]    what the tree's pending simulation waits for (SbPend)
-//   status[i]  0, or why the tree stopped (-1 bad start position, -2 find_leaf failed: arena / path capacity, -3 update_root
-//              was given a move the root does not have, -4 a move was asked of a root without visits, -5 the root state did
-//              not take a move its tree has), or +1: the game is
-//              over (a move played on the batch reached a terminal state).  Every kernel skips a tree whose status != 0
+//   status[i]  0, or why the tree stopped (SbStatus, < 0), or kSbFinished: the game is over (a move played on the batch
+//              reached a terminal state).  Every kernel skips a tree whose status != 0
 //   row_of[i]  row of the compacted leaf batch that holds tree i's leaf (kNoRow = none)
 //   rows[r]    tree index of compacted row r, ascending;  *n_rows = number of rows
 //   n_term[i]  simulations of tree i that ended in a terminal leaf
+//
+// Every step has two kernels: k_sb_X for Connect4's 8-lane engine (SlotCtx, 256 threads, slot = thread / GROUP) and k_sb_big_X
+// for the wavefront-per-tree engine (BigSlot, 64 threads, slot = block, BigScratch in LDS).  They stay plain twins: a body
+// shared through a template over the context type computes the same, but the compiler then allocates registers differently
+// in most of them.  Shared is what compiles to the same code: the seed kernels' tail and the compaction kernels' scan.
 #pragma once
 #include "mcts_object_kernels.h"
 
@@ -25,6 +28,14 @@ enum SbPend : uint8_t {
   kPendCached = 2,  // a cache hit: the answer is already in the slot's (v, pi) rows
   kPendRandom = 3,  // EvalType::RANDOM: process_result synthesises dumb_eval
   kPendRollout = 4  // EvalType::PLAYOUT: the answer of the leaf's rollout is (Connect4: will be, behind k_sb_rollout) in the slot's (v, pi) rows
+};
+enum SbStatus : int32_t {
+  kSbFinished = 1,     // the game is over
+  kSbBadStart = -1,    // bad start position
+  kSbFindFailed = -2,  // find_leaf failed: arena / path capacity
+  kSbBadMove = -3,     // update_root was given a move the root does not have
+  kSbNoVisits = -4,    // a move was asked of a root without visits
+  kSbBadState = -5     // the root state did not take a move its tree has
 };
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;
 
@@ -39,6 +50,18 @@ struct SbArrays {
 
 // ---- seed: N serialized positions -> N root states, N empty trees, one pcg32 stream per tree -----------------------------
 // moves[offs[i] .. offs[i + 1]) are tree i's moves from its start position (init + i * init_stride, NULL = initial position)
+// what both seed kernels end with (before their store): the tree's pcg32 stream, no pending simulation, the tree's bookkeeping rows
+template <class Ctx>
+__device__ __forceinline__ void sb_seed_tail(Ctx& c, const SbArrays& sb, bool ok, uint64_t seed) {
+  Pcg32 g; g.seed(seed);       // MCTS::seed_thread_rng(seed): the stream of MCTS(seed=...)
+  c.rng.state = g.state;
+  c.cur = 0; c.plen = 0; c.flags = 0;
+  if (c.lane == 0) {
+    sb.status[c.slot] = ok ? 0 : kSbBadStart; sb.pend[c.slot] = kPendNone; sb.row_of[c.slot] = kNoRow; sb.n_term[c.slot] = 0;
+    c.ar.c_sims[c.slot] = 0; c.ar.c_evals[c.slot] = 0;
+  }
+}
+
 template <class GM>
 __global__ __launch_bounds__(256) void k_sb_seed(EngineParams ep, EngineArrays ar, SbArrays sb, uint32_t n, const uint8_t* init, uint32_t init_stride,
                                                  const int32_t* moves, const uint32_t* offs, const uint64_t* seeds) {
@@ -53,13 +76,7 @@ __global__ __launch_bounds__(256) void k_sb_seed(EngineParams ep, EngineArrays a
   const uint32_t o0 = offs[slot], o1 = offs[slot + 1];
   const bool ok = mcts_replay_state<GM>(init ? init + static_cast<size_t>(slot) * init_stride : nullptr, moves + o0, o1 - o0, st);
   if (ok) c.gs = st;
-  Pcg32 g; g.seed(seeds[slot]);       // MCTS::seed_thread_rng(seed): the stream of MCTS(seed=...)
-  c.rng.state = g.state;
-  c.cur = 0; c.plen = 0; c.flags = 0;
-  if (lane == 0) {
-    sb.status[slot] = ok ? 0 : -1; sb.pend[slot] = kPendNone; sb.row_of[slot] = kNoRow; sb.n_term[slot] = 0;
-    ar.c_sims[slot] = 0; ar.c_evals[slot] = 0;
-  }
+  sb_seed_tail(c, sb, ok, seeds[slot]);
   c.store(kSlotWaitEval);
 }
 
@@ -83,13 +100,7 @@ __global__ __launch_bounds__(64) void k_sb_big_seed(EngineParams ep, EngineArray
     uint64_t* gl = ar.rep_list + static_cast<size_t>(slot) * (GM::MAX_TURNS + 2);
     for (uint32_t i = lane; i < c.glen; i += 64) gl[i] = sm.glist[i];
   }
-  Pcg32 g; g.seed(seeds[slot]);
-  c.rng.state = g.state;
-  c.cur = 0; c.plen = 0; c.flags = 0;
-  if (lane == 0) {
-    sb.status[slot] = ok ? 0 : -1; sb.pend[slot] = kPendNone; sb.row_of[slot] = kNoRow; sb.n_term[slot] = 0;
-    ar.c_sims[slot] = 0; ar.c_evals[slot] = 0;
-  }
+  sb_seed_tail(c, sb, ok, seeds[slot]);
   c.sync();
   c.store(kSlotWaitEval);
 }
@@ -115,7 +126,7 @@ __global__ __launch_bounds__(256) void k_sb_find(EngineParams ep, EngineArrays a
   uint8_t pend = kPendNone;
   uint64_t ins_key = 0;
   if (!c.find_leaf(0, leaf, term)) {
-    if (lane == 0) sb.status[slot] = -2;
+    if (lane == 0) sb.status[slot] = kSbFindFailed;
   } else if (term != 0) {
     c.process_result(0, true, false);     // the cached terminal scores; neither priors nor root noise are involved
     if (lane == 0) sb.n_term[slot] += 1;
@@ -152,7 +163,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find(EngineParams ep, EngineArray
   uint8_t pend = kPendNone;
   uint64_t ins_key = 0;
   if (!c.find_leaf(0, leaf, term)) {
-    if (lane == 0) sb.status[slot] = -2;
+    if (lane == 0) sb.status[slot] = kSbFindFailed;
   } else if (term != 0) {
     c.process_result(0, true, false);
     if (lane == 0) sb.n_term[slot] += 1;
@@ -173,6 +184,20 @@ __global__ __launch_bounds__(64) void k_sb_big_find(EngineParams ep, EngineArray
 }
 
 // ---- compaction: the kPendRow trees in ascending tree order (one workgroup; the order is deterministic) ---------------------
+// Inclusive scan of the 1024 threads' counts: -> the thread's exclusive prefix; s_sum[1023] is the total
+__device__ __forceinline__ uint32_t sb_scan_1024(uint32_t* s_sum, uint32_t cnt) {
+  const uint32_t tid = threadIdx.x;
+  s_sum[tid] = cnt;
+  __syncthreads();
+  for (uint32_t off = 1; off < 1024u; off <<= 1) {
+    const uint32_t add = tid >= off ? s_sum[tid - off] : 0u;
+    __syncthreads();
+    s_sum[tid] += add;
+    __syncthreads();
+  }
+  return s_sum[tid] - cnt;
+}
+
 __global__ __launch_bounds__(1024) void k_sb_compact(SbArrays sb, uint32_t n) {
   __shared__ uint32_t s_sum[1024];
   const uint32_t tid = threadIdx.x;
@@ -180,15 +205,7 @@ __global__ __launch_bounds__(1024) void k_sb_compact(SbArrays sb, uint32_t n) {
   const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
   uint32_t cnt = 0;
   for (uint32_t i = lo; i < hi; ++i) cnt += sb.pend[i] == kPendRow ? 1u : 0u;
-  s_sum[tid] = cnt;
-  __syncthreads();
-  for (uint32_t off = 1; off < 1024u; off <<= 1) {     // inclusive scan
-    const uint32_t add = tid >= off ? s_sum[tid - off] : 0u;
-    __syncthreads();
-    s_sum[tid] += add;
-    __syncthreads();
-  }
-  uint32_t row = s_sum[tid] - cnt;
+  uint32_t row = sb_scan_1024(s_sum, cnt);
   for (uint32_t i = lo; i < hi; ++i) {
     if (sb.pend[i] == kPendRow) { sb.row_of[i] = row; sb.rows[row] = i; ++row; }
     else sb.row_of[i] = kNoRow;
@@ -307,7 +324,7 @@ __global__ __launch_bounds__(256) void k_sb_find_wu(EngineParams ep, EngineArray
     bool now = false, from_net = true;      // back up at once / with the (v, pi) rows of the entry
     if (!c.find_leaf_wu(0, leaf, term, nif)) {
       // the tree stops: nothing of this step is backed up (reset() clears the root's mark, new nodes get theirs cleared)
-      if (lane == 0) { sb.status[slot] = -2; for (uint32_t j = 0; j < kk; ++j) { w.pend[j * n + slot] = kPendNone; w.keys[j * n + slot] = 0; } }
+      if (lane == 0) { sb.status[slot] = kSbFindFailed; for (uint32_t j = 0; j < kk; ++j) { w.pend[j * n + slot] = kPendNone; w.keys[j * n + slot] = 0; } }
       break;
     }
     if (term != 0) {
@@ -364,7 +381,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find_wu(EngineParams ep, EngineAr
     uint64_t ins_key = 0;
     bool now = false, from_net = true;
     if (!c.find_leaf_wu(0, leaf, term, nif)) {
-      if (lane == 0) { sb.status[slot] = -2; for (uint32_t j = 0; j < kk; ++j) { w.pend[j * n + slot] = kPendNone; w.keys[j * n + slot] = 0; } }
+      if (lane == 0) { sb.status[slot] = kSbFindFailed; for (uint32_t j = 0; j < kk; ++j) { w.pend[j * n + slot] = kPendNone; w.keys[j * n + slot] = 0; } }
       break;
     }
     if (term != 0) {
@@ -405,15 +422,7 @@ __global__ __launch_bounds__(1024) void k_sb_compact_wu(SbArrays sb, SbWuArrays 
   const uint32_t lo = min(total, tid * per), hi = min(total, lo + per);
   uint32_t cnt = 0;
   for (uint32_t j = lo; j < hi; ++j) cnt += w.pend[(j % kk) * n + j / kk] == kPendRow ? 1u : 0u;
-  s_sum[tid] = cnt;
-  __syncthreads();
-  for (uint32_t off = 1; off < 1024u; off <<= 1) {     // inclusive scan
-    const uint32_t add = tid >= off ? s_sum[tid - off] : 0u;
-    __syncthreads();
-    s_sum[tid] += add;
-    __syncthreads();
-  }
-  uint32_t row = s_sum[tid] - cnt;
+  uint32_t row = sb_scan_1024(s_sum, cnt);
   for (uint32_t j = lo; j < hi; ++j) {
     const uint32_t tree = j / kk, e = (j % kk) * n + tree;
     if (w.pend[e] == kPendRow) { w.row_of[e] = row; w.rows[row] = e; w.tree_of[row] = tree; ++row; }
@@ -537,7 +546,6 @@ struct SbPlayArrays {
   float* final;        // [N, P + 1]
   uint32_t log_cap;
 };
-enum SbStatus : int32_t { kSbFinished = 1, kSbBadStart = -1, kSbFindFailed = -2, kSbBadMove = -3, kSbNoVisits = -4, kSbBadState = -5 };
 
 // what the two update-root kernels share once the tree is re-rooted and `mv` is played: move log, finished rule
 template <class GM, class State>
@@ -750,7 +758,7 @@ __global__ __launch_bounds__(256) void k_sb_find_po(EngineParams ep, EngineArray
   uint32_t term = 0;
   uint8_t pend = kPendNone;
   if (!c.find_leaf(0, leaf, term)) {
-    if (lane == 0) sb.status[slot] = -2;
+    if (lane == 0) sb.status[slot] = kSbFindFailed;
   } else if (term != 0) {
     c.process_result(0, true, false);
     if (lane == 0) sb.n_term[slot] += 1;
@@ -803,7 +811,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find_po(EngineParams ep, EngineAr
   uint32_t term = 0;
   uint8_t pend = kPendNone;
   if (!c.find_leaf(0, leaf, term)) {
-    if (lane == 0) sb.status[slot] = -2;
+    if (lane == 0) sb.status[slot] = kSbFindFailed;
   } else if (term != 0) {
     c.process_result(0, true, false);
     if (lane == 0) sb.n_term[slot] += 1;
@@ -841,7 +849,7 @@ __global__ __launch_bounds__(256) void k_sb_find_wu_po(EngineParams ep, EngineAr
     typename GM::State leaf;
     uint32_t term = 0;
     if (!c.find_leaf_wu(0, leaf, term, nif)) {      // the tree stops (reset() clears the root's mark, new nodes get theirs cleared)
-      if (lane == 0) sb.status[slot] = -2;
+      if (lane == 0) sb.status[slot] = kSbFindFailed;
       break;
     }
     if (term != 0) ++n_term;
@@ -888,7 +896,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find_wu_po(EngineParams ep, Engin
     typename GM::State leaf;
     uint32_t term = 0;
     if (!c.find_leaf_wu(0, leaf, term, nif)) {
-      if (lane == 0) sb.status[slot] = -2;
+      if (lane == 0) sb.status[slot] = kSbFindFailed;
       break;
     }
     if (term != 0) ++n_term;

@@ -281,6 +281,57 @@ def test_cache_serves_the_answers_the_net_gave(az, c4_net, net_search):
     assert cache2.hits() + cache2.misses() == st2["simulations"] - st2["terminal_leaves"]
 
 
+@pytest.fixture(scope="module")
+def brandubh_net(az):
+    from alphazero import torch_net
+    spec = torch_net.brandubh_spec()
+    return az.HipLeafNet(torch_net.random_init(spec, seed=3), spec, precision="bf16")
+
+
+def _assert_cache_accounts_for_every_leaf(mb, cache):
+    st = mb.stats()
+    assert cache.hits() + cache.misses() == st["simulations"] - st["terminal_leaves"]
+    assert cache.misses() == st["evaluator_leaves"]
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_wide_game_cache_serves_the_answers_the_net_gave(az, brandubh_net, K):
+    """The cache on the wavefront-per-tree engine (Brandubh), which writes a leaf's planes before it probes (Connect4 probes
+    first), with K leaves of every tree in flight per step.  (a) 3 trees on 3 positions, 24 visits: every read-out with a cache
+    equals the one without, and every non-terminal leaf is either a hit or a miss that went to the net.  (b) 4 trees on the start
+    position told apart by root noise: what one tree asked the net, another finds in the cache.
+    (a)'s equality is asserted for K = 3 as for K = 1."""
+    visits = 24
+    kw = dict(max_simulations=visits, leaves_per_step=K)
+    rng = np.random.default_rng(17)
+    states, gs = [], az.BrandubhGS()
+    for _ in range(3):
+        for _ in range(2):                      # the next position is two plies further down a random playout
+            gs.play_move(int(rng.choice(np.flatnonzero(gs.valid_moves()))))
+            assert gs.scores() is None
+        states.append(gs.copy())
+    seeds = [41, 42, 43]
+    plain = az.MCTSBatch(az.BrandubhGS, 3, 1.25, fpu_reduction=0.25, seeds=seeds, **kw)
+    plain.reset(states)
+    plain.search(visits, net=brandubh_net)
+    cache = az.ShardedS3FIFOCache.for_engine(1 << 12, az.BrandubhGS.NUM_MOVES(), 3)
+    mb = az.MCTSBatch(az.BrandubhGS, 3, 1.25, fpu_reduction=0.25, seeds=seeds, **kw)
+    mb.reset(states)
+    mb.search(visits, net=brandubh_net, cache=cache)
+    assert mb.depths().tolist() == [visits] * 3
+    _assert_same(_readout(plain), _readout(mb), f"K = {K}: with a cache vs without")
+    assert mb.stats()["simulations"] == 3 * visits
+    _assert_cache_accounts_for_every_leaf(mb, cache)
+
+    cache2 = az.ShardedS3FIFOCache.for_engine(1 << 12, az.BrandubhGS.NUM_MOVES(), 3)
+    mb2 = az.MCTSBatch(az.BrandubhGS, 4, 1.25, epsilon=0.25, seeds=[1, 2, 3, 4], **kw)
+    mb2.reset([az.BrandubhGS() for _ in range(4)])
+    mb2.search(visits, net=brandubh_net, cache=cache2, root_noise=True)
+    assert int(mb2.depths().min()) == visits
+    assert cache2.hits() > 0
+    _assert_cache_accounts_for_every_leaf(mb2, cache2)
+
+
 # ---- 6. order independence -------------------------------------------------------------------------------------------------------
 def test_order_independence_and_a_batch_of_one(az):
     n, visits = 48, 50
