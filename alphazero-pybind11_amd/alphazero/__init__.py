@@ -607,7 +607,11 @@ class MCTSBatch:
     (reset(..., rollout_seeds=...) sets them, rollout_seeds() reads them).  With leaves_per_step > 1 a playout leaf is an
     immediate: its process_result_batched runs at once, in descent order, so the tree's next descent sees the back-up.  A
     cache with "playout" is an error (the reference's playout branch bypasses the cache), as is "playout" or "random" with a
-    net and "net" without one.  stats()["evaluator_leaves"] counts the rollouts."""
+    net and "net" without one.  stats()["evaluator_leaves"] counts the rollouts.
+
+    A visit sweep (mcts_analysis.py:884-972): search_to(targets, ..., checkpoints=(c0, c1, ...)) searches tree i until
+    root_n(i) >= targets[i] and records counts / probs / root_values / root_q_values on the device the first time root_n(i)
+    reaches each checkpoint; checkpoints() returns the snapshots.  See search_to()."""
 
     _MASK64 = 0xFFFFFFFFFFFFFFFF
     _ROLL_SALT = 0x9E3779B97F4A7C15      # kRollSalt, csrc/dev_rng.h
@@ -749,6 +753,59 @@ class MCTSBatch:
             cache._ensure_engine_layout()
         check(lib.azmi_search_run_eval(self._h, int(ev), None if net is None else net._h, None if cache is None else cache._h, int(visits),
                                        int(bool(root_noise)), C.c_void_p(-1)))
+
+    def search_to(self, targets, net=None, cache=None, root_noise=False, evaluator=None, checkpoints=None, temp=1.0, pruned=False):
+        """Search every tree to its own visit target: tree i descends while root_n(i) < targets[i] (`targets`: an int or n
+        integers) - the `while mcts.root_n() < target` loop of mcts_analysis.py:884-972.  A tree at or above its target (a root
+        reused by update_roots() already holds visits) and a finished tree take no descent.  net / cache / root_noise /
+        evaluator are search()'s.  With leaves_per_step = K every step is K descents of every tree still below its target, so
+        a tree may overshoot by fewer than K (mcts_analysis.py:982-1058).
+        `checkpoints`: None, or at most 32 strictly ascending positive visit counts.  Snapshot j of tree i is taken once, on the
+        device, at the first step boundary at which root_n(i) >= checkpoints[j] - before the first descent for a tree that
+        starts there; a checkpoint above the tree's target is never taken.  checkpoints() returns the snapshots; every
+        search_to starts a fresh set.  `temp`, `pruned`: the snapshots hold probs(temp), or probs_pruned(temp).
+        The call reads root_n once, then enqueues every step without reading anything back; the budget is checked for the
+        longest tree's steps x K before anything is enqueued.  A Gumbel batch raises: use search(visits)."""
+        ev = self._evaluator("search_to", evaluator, net, cache)
+        if net is not None and (net.desc.num_moves != self._M or (net.desc.in_channels, net.desc.height, net.desc.width) != self._chw):
+            raise RuntimeError("search_to: the net's shape does not match the game")
+        if self._gumbel:
+            raise RuntimeError("search_to on a Gumbel batch: sequential halving plans a fixed budget at its first descent, and a "
+                               "root_n target on a reused tree is not one; use search(visits)")
+        tg = [int(targets)] * self._n if np.ndim(targets) == 0 else [int(x) for x in targets]
+        if len(tg) != self._n:
+            raise RuntimeError(f"search_to: one target per tree ({self._n}), got {len(tg)}")
+        if any(x < 0 or x > 0xFFFFFFFF for x in tg):
+            raise RuntimeError("search_to: targets must be visit counts in [0, 2^32)")
+        cp = [] if checkpoints is None else [int(x) for x in checkpoints]
+        if len(cp) > 32:
+            raise RuntimeError(f"search_to: at most 32 checkpoints, got {len(cp)}")
+        if any(x <= 0 or x > 0xFFFFFFFF for x in cp) or any(b <= a for a, b in zip(cp, cp[1:])):
+            raise RuntimeError(f"search_to: checkpoints must be positive and strictly ascending, got {cp}")
+        if cache is not None:
+            cache._ensure_engine_layout()
+        tga, cpa = np.ascontiguousarray(tg, dtype=np.uint32), np.ascontiguousarray(cp, dtype=np.uint32)
+        check(lib.azmi_search_run_to(self._h, int(ev), None if net is None else net._h, None if cache is None else cache._h,
+                                     tga.ctypes.data, cpa.ctypes.data if cp else None, len(cp), float(temp), int(bool(pruned)),
+                                     int(bool(root_noise)), C.c_void_p(-1)))
+        self._sweep_j = len(cp)
+
+    def checkpoints(self):
+        """The snapshots of the last search_to(), one row per tree and checkpoint, as recorded on the device at snapshot time:
+        taken bool [n, J], root_n uint32 [n, J], counts uint32 [n, J, M], probs float32 [n, J, M] (probs(temp), or
+        probs_pruned(temp) with pruned=True), root_values float32 [n, J, 3], root_q_values float32 [n, J, M].  Rows that were
+        not taken are zero.  Synchronises."""
+        J = getattr(self, "_sweep_j", None)
+        if J is None:
+            raise RuntimeError("checkpoints: no search_to call has been made on this batch")
+        n, M = self._n, self._M
+        mask = np.zeros(n, np.uint32)
+        out = dict(root_n=np.zeros((n, J), np.uint32), counts=np.zeros((n, J, M), np.uint32), probs=np.zeros((n, J, M), np.float32),
+                   root_values=np.zeros((n, J, 3), np.float32), root_q_values=np.zeros((n, J, M), np.float32))
+        check(lib.azmi_search_checkpoints(self._h, mask.ctypes.data, out["root_n"].ctypes.data, out["counts"].ctypes.data,
+                                          out["probs"].ctypes.data, out["root_values"].ctypes.data, out["root_q_values"].ctypes.data))
+        out["taken"] = ((mask[:, None] >> np.arange(J, dtype=np.uint32)[None, :]) & 1).astype(bool)
+        return out
 
     def synchronize(self):
         check(lib.azmi_search_sync(self._h))

@@ -212,6 +212,8 @@ SYMBOLS = {
     "azmi_search_run_eval": (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_uint32, C.c_int, _VP]),
     "azmi_search_play_eval": (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_uint32, C.c_float, C.c_uint32, C.c_int, _VP]),
     "azmi_search_set_rollout_seeds": (C.c_int, [_VP, _VP]),
+    "azmi_search_run_to": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, C.c_uint32, C.c_float, C.c_int, C.c_int, _VP]),
+    "azmi_search_checkpoints": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "azmi_game_replay_ex": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32]),
     "azmi_game_replay_from": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "azmi_playout_eval": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP]),

@@ -8,6 +8,8 @@
 // kernels and launch helpers below; K == 1 runs the original ones.
 // azmi_search_run_eval / play_eval with AZMI_EVAL_PLAYOUT evaluate every leaf by a random rollout on the device (the *_po kernels):
 // no compaction, no net call, no cache insert, at most 3 launches a step.
+// azmi_search_run_to searches every tree to its own root_n target and snapshots the read-outs at checkpoints on the way
+// (mcts_analysis.py:884-972): the steps above, plus the checkpoint kernel at the steps the host knows something can happen at.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,6 +59,13 @@ struct azmi_search {
   // EvalType::PLAYOUT: the rollout seed and rollout count of every tree, the parked leaf states of a Connect4 K == 1 step
   SbRollArrays ro{};
   std::vector<uint64_t> tree_seeds;   // seeds of the last reset: the default rollout seeds derive from them
+  // search to targets (azmi_search_run_to): allocated by the first call, regrown when it brings more checkpoints
+  SbSweepArrays sw{};
+  void* sw_block = nullptr;           // one allocation behind every sw pointer
+  size_t sw_clear_bytes = 0;          // its leading part that every call clears: taken masks and snapshot rows
+  uint32_t sw_cap = 0;                // checkpoints the block has room for
+  bool sw_valid = false;              // a run_to call has defined the snapshot set
+  std::vector<uint32_t> sw_upload;    // targets [N] + checkpoints [32]: the host side of the call's upload (kept until the next call)
 };
 
 namespace {
@@ -115,6 +124,8 @@ void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArr
 // EvalType::PLAYOUT steps (defined at the end of the file: kernels that are instantiated last leave the code objects of the others where they were)
 void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, hipStream_t st);
 void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st);
+// the checkpoint kernel of azmi_search_run_to (also at the end of the file)
+void launch_checkpoint(azmi_search* s, float temp, uint32_t pruned, uint32_t resume, hipStream_t st);
 
 // ---- K > 1: the same steps over K descents of every tree; the launch counts do not depend on N or K ---------------------------
 EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine arrays with the step-sized [K * N] row buffers in place
@@ -232,60 +243,50 @@ int search_args(azmi_search* s, const char* what, int eval_type, azmi_net* net, 
   return AZMI_OK;
 }
 
-// the steps of search(visits) on `st`, nothing read back: azmi_search_run, and every move of azmi_search_play
-int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
+// one step of every live tree on `st`: `kk` descents each (1 unless leaves_per_step > 1), the evaluator, the back-up
+int enqueue_step(azmi_search* s, const SearchArgs& a, uint32_t kk, uint32_t rn, hipStream_t st) {
   const EngineParams& ep = a.ep;
   const EngineArrays& ar = a.ar;
   azmi_net* net = a.net;
-  int rc = AZMI_OK;
-  if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
   if (a.playout) {
-    if (s->k_leaves > 1) {
-      for (uint32_t left = visits; left;) {
-        const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
-        launch_step_playout_wu(s, ep, ar, kk, rn, st);
-        left -= kk; s->steps += 1;
-      }
-    } else {
-      for (uint32_t i = 0; i < visits; ++i) launch_step_playout(s, ep, ar, rn, st);
-      s->steps += visits;
-    }
-    SB_TRY(hipGetLastError());
-    s->sims_done += visits;
-    return AZMI_OK;
-  }
-  if (s->k_leaves > 1) {
-    // visits / K steps of K descents and one of the remainder, enqueued back to back like the K == 1 steps below
+    if (s->k_leaves > 1) launch_step_playout_wu(s, ep, ar, kk, rn, st);
+    else launch_step_playout(s, ep, ar, rn, st);
+  } else if (s->k_leaves > 1) {
     const EngineArrays aw = wu_rows(s, ar);
-    for (uint32_t left = visits; left;) {
-      const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
-      launch_find_wu(s, ep, ar, kk, net ? 0u : 1u, rn, st);
-      if (net) {
-        rc = azmi_net_forward_rows(net, aw.canon, aw.v, aw.pi, s->wu.rows, s->sb.n_rows, s->n * kk, st);
-        if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
-        s->net_calls += 1;
-        if (ep.cache_on) launch_cache_insert(s, ep, aw, s->n * kk, st);
-      }
-      launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
-      left -= kk; s->steps += 1;
+    launch_find_wu(s, ep, ar, kk, net ? 0u : 1u, rn, st);
+    if (net) {
+      const int rc = azmi_net_forward_rows(net, aw.canon, aw.v, aw.pi, s->wu.rows, s->sb.n_rows, s->n * kk, st);
+      if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
+      s->net_calls += 1;
+      if (ep.cache_on) launch_cache_insert(s, ep, aw, s->n * kk, st);
     }
-    SB_TRY(hipGetLastError());
-    s->sims_done += visits;
-    return AZMI_OK;
-  }
-  // `visits` step pairs, enqueued back to back: the row count of a step never leaves the device
-  for (uint32_t i = 0; i < visits; ++i) {
+    launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
+  } else {
     launch_find(s, ep, ar, net ? 0u : 1u, st);
     if (net) {
-      rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
+      const int rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
       if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
       s->net_calls += 1;
       if (ep.cache_on) launch_cache_insert(s, ep, ar, s->n, st);
     }
     launch_process(s, ep, ar, rn, nullptr, nullptr, st);
   }
+  s->steps += 1;
+  return AZMI_OK;
+}
+
+// the steps of search(visits) on `st`, nothing read back: azmi_search_run, and every move of azmi_search_play.  Enqueued back to
+// back: the row count of a step never leaves the device.  K > 1: visits / K steps of K descents and one of the remainder
+int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
+  if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
+  for (uint32_t left = visits; left;) {
+    const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
+    const int rc = enqueue_step(s, a, kk, rn, st);
+    if (rc != AZMI_OK) return rc;
+    left -= kk;
+  }
   SB_TRY(hipGetLastError());
-  s->sims_done += visits; s->steps += visits;
+  s->sims_done += visits;
   return AZMI_OK;
 }
 
@@ -393,6 +394,7 @@ void azmi_search_destroy(azmi_search* s) {
   if (!s) return;
   (void)hipSetDevice(s->pm->device);
   wu_free(s);        // (hipFree waits for the device)
+  if (s->sw_block) (void)hipFree(s->sw_block);
   azmi_pm_destroy(s->pm);
   delete s;
 }
@@ -753,3 +755,129 @@ void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const Engine
 }
 
 }  // namespace
+
+// ---- search to per-tree root_n targets, snapshots at checkpoints (mcts_analysis.py:884-972, 975-1063) ---------------------------
+namespace {
+
+void launch_checkpoint(azmi_search* s, float temp, uint32_t pruned, uint32_t resume, hipStream_t st) {
+  SB_LAUNCH(s, st, k_sb_checkpoint, k_sb_big_checkpoint, s->pm->ep, s->pm->ar, s->sb, s->sw, s->n, temp, pruned, resume);
+}
+
+// room for `j` checkpoints: one block, [taken | root_n | counts | probs | root_values | root_q] (cleared by every call) and
+// [target | cps] behind them (uploaded by every call).  Rows are indexed with the call's own J, so a block grown for more
+// checkpoints serves fewer
+int sweep_reserve(azmi_search* s, uint32_t j) {
+  const size_t N = s->n, M = s->pm->gi.M;
+  if (!s->sw_block || j > s->sw_cap) {
+    const size_t cap = std::max<uint32_t>(j, 1u);
+    const size_t clear_words = N * (1 + cap * (1 + 3 * M + 3));
+    void* q = nullptr;
+    SB_TRY(hipMalloc(&q, (clear_words + N + kSbMaxCheckpoints) * 4));
+    if (s->sw_block) (void)hipFree(s->sw_block);      // (waits for the device)
+    s->sw_block = q; s->sw_cap = static_cast<uint32_t>(cap); s->sw_clear_bytes = clear_words * 4;
+    uint32_t* w = static_cast<uint32_t*>(q);
+    s->sw.taken = w; w += N;
+    s->sw.root_n = w; w += N * cap;
+    s->sw.counts = w; w += N * cap * M;
+    s->sw.probs = reinterpret_cast<float*>(w); w += N * cap * M;
+    s->sw.root_values = reinterpret_cast<float*>(w); w += N * cap * 3;
+    s->sw.root_q = reinterpret_cast<float*>(w); w += N * cap * M;
+    s->sw.target = w; w += N;
+    s->sw.cps = w;
+  }
+  s->sw.n_cp = j;
+  return AZMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int azmi_search_run_to(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, const uint32_t* targets, const uint32_t* checkpoints,
+                       uint32_t n_checkpoints, float temp, int pruned, int root_noise_enabled, void* stream) {
+  int rc = begin_step(s, "search_to"); if (rc) return rc;
+  if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "search_to: a find_leaves step is pending; call process_results first");
+  if (!targets || (n_checkpoints && !checkpoints)) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (s->gumbel)
+    return SB_FAIL(AZMI_ERR_INVALID, "search_to on a Gumbel batch: sequential halving plans a fixed budget at its first descent, and a "
+                   "root_n target on a reused tree is not one; use search(visits)");
+  if (n_checkpoints > kSbMaxCheckpoints) return SB_FAIL(AZMI_ERR_INVALID, "search_to: at most %u checkpoints, got %u", kSbMaxCheckpoints, n_checkpoints);
+  for (uint32_t j = 0; j < n_checkpoints; ++j)
+    if (checkpoints[j] == 0 || (j && checkpoints[j] <= checkpoints[j - 1]))
+      return SB_FAIL(AZMI_ERR_INVALID, "search_to: checkpoints must be positive and strictly ascending (checkpoint %u is %u)", j, checkpoints[j]);
+  SearchArgs a;
+  rc = search_args(s, "search_to", eval_type, net, cache, &a); if (rc) return rc;
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t prev = pm->last;
+  hipStream_t st = pm->pick(stream);
+  if (prev != st) SB_TRY(hipStreamSynchronize(prev));      // the previous call's upload may still read sw_upload
+  const uint32_t n = s->n, K = s->k_leaves, J = n_checkpoints;
+  // the one read of the call: root_n (kind-5 read-out, column 1) and the status of every tree.  `launches` counts what the call
+  // enqueues behind it
+  std::vector<uint32_t> r(n);
+  std::vector<int32_t> status(n);
+  launch_query(s, kQScalars, 0.0f, 0u, st);
+  s->launches -= 1;
+  SB_TRY(hipGetLastError());
+  SB_TRY(hipMemcpy2DAsync(r.data(), 4, s->d_qu + 1, static_cast<size_t>(s->vec_u) * 4, 4, n, hipMemcpyDeviceToHost, st));
+  SB_TRY(hipMemcpyAsync(status.data(), s->sb.status, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st));
+  SB_TRY(hipStreamSynchronize(st));
+  // root_n rises by exactly one per backed-up simulation, so tree i holds r[i] + t * K after step t until it reaches its target,
+  // at step ceil(rem / K): the steps at which a tree newly reaches a checkpoint or its target are known here
+  uint32_t T = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (status[i] == 0 && targets[i] > r[i]) T = std::max(T, (targets[i] - r[i] + K - 1) / K);
+  rc = check_budget(s, "search_to", static_cast<uint64_t>(T) * K); if (rc) return rc;
+  std::vector<uint8_t> event(static_cast<size_t>(T) + 1, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (status[i] != 0) continue;
+    const uint32_t ti = targets[i] > r[i] ? (targets[i] - r[i] + K - 1) / K : 0u;
+    if (T) event[ti] = 1;      // the pause (with T == 0 no step follows that a pause could keep a tree out of)
+    for (uint32_t j = 0; j < J; ++j) {
+      const uint32_t tj = checkpoints[j] > r[i] ? (checkpoints[j] - r[i] + K - 1) / K : 0u;
+      if (tj <= ti) event[tj] = 1;
+    }
+  }
+  if (T) event[T] = 1;         // the resume
+  rc = sweep_reserve(s, J); if (rc) return rc;
+  s->sw_upload.assign(targets, targets + n);
+  if (J) s->sw_upload.insert(s->sw_upload.end(), checkpoints, checkpoints + J);
+  s->sw_upload.resize(static_cast<size_t>(n) + kSbMaxCheckpoints, 0u);
+  SB_TRY(hipMemsetAsync(s->sw_block, 0, s->sw_clear_bytes, st));
+  SB_TRY(hipMemcpyAsync(s->sw.target, s->sw_upload.data(), s->sw_upload.size() * 4, hipMemcpyHostToDevice, st));
+  s->sw_valid = true;
+  if (T == 0 && !event[0]) return AZMI_OK;
+  const uint32_t rn = root_noise_enabled ? 1u : 0u, pr = pruned ? 1u : 0u;
+  // from the first checkpoint launch on a tree may be paused: every way out goes through a launch that resumes
+  rc = AZMI_OK;
+  for (uint32_t t = 0; t < T && rc == AZMI_OK; ++t) {
+    if (event[t]) launch_checkpoint(s, temp, pr, 0u, st);
+    rc = enqueue_step(s, a, K, rn, st);
+    if (rc == AZMI_OK) s->sims_done += K;
+  }
+  launch_checkpoint(s, temp, pr, 1u, st);
+  if (rc != AZMI_OK) return rc;
+  SB_TRY(hipGetLastError());
+  return AZMI_OK;
+}
+
+int azmi_search_checkpoints(azmi_search* s, uint32_t* taken_mask, uint32_t* root_n, uint32_t* counts, float* probs, float* root_values,
+                            float* root_q) {
+  int rc = begin_read(s, "checkpoints"); if (rc) return rc;
+  if (!s->sw_valid) return SB_FAIL(AZMI_ERR_STATE, "checkpoints: no search_to call has been made on this batch");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  rc = check_device(s, pm->last); if (rc) return rc;      // (synchronises)
+  const size_t N = s->n, J = s->sw.n_cp, M = pm->gi.M;
+  if (taken_mask) SB_TRY(hipMemcpy(taken_mask, s->sw.taken, N * 4, hipMemcpyDeviceToHost));
+  if (!J) return AZMI_OK;
+  if (root_n) SB_TRY(hipMemcpy(root_n, s->sw.root_n, N * J * 4, hipMemcpyDeviceToHost));
+  if (counts) SB_TRY(hipMemcpy(counts, s->sw.counts, N * J * M * 4, hipMemcpyDeviceToHost));
+  if (probs) SB_TRY(hipMemcpy(probs, s->sw.probs, N * J * M * 4, hipMemcpyDeviceToHost));
+  if (root_values) SB_TRY(hipMemcpy(root_values, s->sw.root_values, N * J * 3 * 4, hipMemcpyDeviceToHost));
+  if (root_q) SB_TRY(hipMemcpy(root_q, s->sw.root_q, N * J * M * 4, hipMemcpyDeviceToHost));
+  return AZMI_OK;
+}
+
+}  // extern "C"

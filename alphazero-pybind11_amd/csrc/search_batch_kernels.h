@@ -31,6 +31,7 @@ enum SbPend : uint8_t {
 };
 enum SbStatus : int32_t {
   kSbFinished = 1,     // the game is over
+  kSbPaused = 2,       // the tree has reached its target of the running search_to call: set and cleared by the checkpoint kernels alone
   kSbBadStart = -1,    // bad start position
   kSbFindFailed = -2,  // find_leaf failed: arena / path capacity
   kSbBadMove = -3,     // update_root was given a move the root does not have
@@ -911,6 +912,111 @@ __global__ __launch_bounds__(64) void k_sb_big_find_wu_po(EngineParams ep, Engin
   c.sync();
   if (lane == 0) { ro.count[slot] = j; ar.c_evals[slot] += j - j0; sb.n_term[slot] += n_term; }
   c.store(kSlotWaitEval);
+}
+
+// ======================= search to per-tree visit targets, snapshots at checkpoints ================================================
+// The inner loop of mcts_analysis.py:run_analysis (:884-972, batched :975-1063): `while mcts.root_n() < target` with the policy and
+// the value captured once at every smaller visit count of the sweep.  The step kernels above stay as they are: a tree that has
+// reached its target gets status kSbPaused (> 0: no error; not kSbFinished) here, which every one of them skips like any other non-zero status, and the call's
+// last checkpoint launch turns every kSbPaused back to 0 (`resume`), so the value never outlives the call that set it.
+//   target[i]     tree i descends while root_n(i) < target[i]
+//   cps[j]        the J <= 32 checkpoints, strictly ascending
+//   taken[i]      bit j: snapshot j of tree i is taken; it is taken once, at the first launch that sees root_n(i) >= cps[j]
+//   root_n / counts / probs / root_values / root_q   row (i, j) of [N, J] / [N, J, M] / [N, J, M] / [N, J, 3] / [N, J, M]
+// The rows are written by the read-out bodies of kinds 0, 1 | 2, 3, 4 (mcts_query_slot / mcts_big_query_slot), the same bodies
+// the pick kernel reuses; rows that were not taken keep the zeros the host cleared them to.
+constexpr uint32_t kSbMaxCheckpoints = 32;
+
+struct SbSweepArrays {
+  uint32_t* target;     // [N]
+  uint32_t* cps;        // [kSbMaxCheckpoints]
+  uint32_t* taken;      // [N]
+  uint32_t* root_n;     // [N, J]
+  uint32_t* counts;     // [N, J, M]
+  float* probs;         // [N, J, M]
+  float* root_values;   // [N, J, 3]
+  float* root_q;        // [N, J, M]
+  uint32_t n_cp;        // J
+};
+
+// what both checkpoint kernels end with: pause at the target, resume at the end of the call (lane 0 of the tree)
+__device__ __forceinline__ void sb_checkpoint_tail(const SbArrays& sb, const SbSweepArrays& sw, uint32_t slot, int32_t status, uint32_t root_n,
+                                                   uint32_t resume) {
+  int32_t next = status;
+  if (next == 0 && root_n >= sw.target[slot]) next = kSbPaused;
+  if (resume && next == kSbPaused) next = 0;
+  if (next != status) sb.status[slot] = next;
+}
+
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_checkpoint(EngineParams ep, EngineArrays ar, SbArrays sb, SbSweepArrays sw, uint32_t n, float temp,
+                                                       uint32_t pruned, uint32_t resume) {
+  constexpr int G = GM::GROUP;
+  constexpr uint32_t M = GM::M;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (slot >= n) return;
+  const int32_t status = sb.status[slot];
+  uint32_t root_n = 0;
+  if (status == 0) {
+    const uint32_t t = slot * GM::P;
+    root_n = ar.nodes[static_cast<size_t>(t) * ep.cap + ar.root[t]].n;
+    const uint32_t taken = sw.taken[slot];
+    uint32_t now = taken;
+    for (uint32_t j = 0; j < sw.n_cp; ++j) {
+      if (((now >> j) & 1u) || sw.cps[j] > root_n) continue;
+      const size_t row = static_cast<size_t>(slot) * sw.n_cp + j;
+      uint32_t* cu = sw.counts + row * M;
+      float* pf = sw.probs + row * M;
+      mcts_query_slot<GM>(ep, ar, slot, lane, kQCounts, 0.0f, 0u, pf, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      // the slot state lane 0 stored is loaded again by every lane
+      mcts_query_slot<GM>(ep, ar, slot, lane, pruned ? kQProbsPruned : kQProbs, temp, 0u, pf, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      mcts_query_slot<GM>(ep, ar, slot, lane, kQRootValue, 0.0f, 0u, sw.root_values + row * 3, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      mcts_query_slot<GM>(ep, ar, slot, lane, kQRootQ, 0.0f, 0u, sw.root_q + row * M, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      if (lane == 0) sw.root_n[row] = root_n;
+      now |= 1u << j;
+    }
+    if (lane == 0 && now != taken) sw.taken[slot] = now;
+  }
+  if (lane == 0) sb_checkpoint_tail(sb, sw, slot, status, root_n, resume);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_checkpoint(EngineParams ep, EngineArrays ar, SbArrays sb, SbSweepArrays sw, uint32_t n, float temp,
+                                                          uint32_t pruned, uint32_t resume) {
+  __shared__ BigScratch<GM> sm;
+  constexpr uint32_t M = GM::M;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot >= n) return;
+  const int32_t status = sb.status[slot];
+  uint32_t root_n = 0;
+  if (status == 0) {
+    const uint32_t t = slot * GM::P;
+    root_n = ar.N[static_cast<size_t>(t) * ep.cap + ar.root[t]];
+    const uint32_t taken = sw.taken[slot];
+    uint32_t now = taken;
+    for (uint32_t j = 0; j < sw.n_cp; ++j) {
+      if (((now >> j) & 1u) || sw.cps[j] > root_n) continue;
+      const size_t row = static_cast<size_t>(slot) * sw.n_cp + j;
+      uint32_t* cu = sw.counts + row * M;
+      float* pf = sw.probs + row * M;
+      mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQCounts, 0.0f, 0u, pf, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, pruned ? kQProbsPruned : kQProbs, temp, 0u, pf, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQRootValue, 0.0f, 0u, sw.root_values + row * 3, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      mcts_big_query_slot<GM>(ep, ar, sm, slot, lane, kQRootQ, 0.0f, 0u, sw.root_q + row * M, cu);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      if (lane == 0) sw.root_n[row] = root_n;
+      now |= 1u << j;
+    }
+    if (lane == 0 && now != taken) sw.taken[slot] = now;
+  }
+  if (lane == 0) sb_checkpoint_tail(sb, sw, slot, status, root_n, resume);
 }
 
 }  // namespace azmi

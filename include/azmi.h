@@ -470,6 +470,34 @@ int azmi_search_run_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cach
 int azmi_search_play_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves,
                           int root_noise, void* stream);
 int azmi_search_set_rollout_seeds(azmi_search* s, const uint64_t* seeds);
+/* ---- search to per-tree visit targets, snapshots at checkpoints: the inner loop of mcts_analysis.py:run_analysis
+ * (mcts_analysis.py:884-972, batched :975-1063) - `while mcts.root_n() < target: find_leaf / evaluate / process_result`, with
+ * probs(temp) | probs_pruned(temp) and root_value() captured once at every smaller visit count of the sweep (:903-905, :960-972).
+ *   run_to        tree i descends while root_n(i) < targets[i] (HOST array [n_trees]); a tree at or above its target, a finished
+ *                 or a stopped tree takes no descent.  A reused root (update_roots) already holds visits, so it needs fewer
+ *                 descents than its target.  `checkpoints`: HOST array of n_checkpoints <= 32 strictly ascending positive visit
+ *                 counts, or NULL with 0.  Snapshot j of tree i is taken once, on the device, at the first step boundary at which
+ *                 root_n(i) >= checkpoints[j] - before the first descent for a tree that starts there; a checkpoint above the
+ *                 tree's target is never taken.  With leaves_per_step = K > 1 every step is K descents of every tree still below
+ *                 its target (a tree may overshoot by fewer than K, mcts_analysis.py:982-1058) and the snapshots are taken at
+ *                 step boundaries.  Evaluator, net, cache and root noise are run_eval's.  The call reads root_n of every tree once
+ *                 (it synchronises `stream` for that), then enqueues T = max_i ceil((targets[i] - root_n(i)) / K) steps and reads
+ *                 nothing back; the budget (see above) is checked for T * K descents before anything is enqueued.  The
+ *                 checkpoint kernel runs only at the steps at which, by root_n(i) + t * K, some tree newly reaches a checkpoint or
+ *                 its target, and once behind the last step: `launches` of stats rises by those of run_eval(T * K) plus the
+ *                 number of such steps, whatever n_trees is (the read before the run is not counted).  A tree at its target is
+ *                 held out of the remaining steps by a status of its own that the call's last launch clears on every return
+ *                 path, so that game_state never shows it.  Every call starts a fresh snapshot set.  A Gumbel batch is
+ *                 AZMI_ERR_INVALID: sequential halving plans a fixed budget at its first descent, and a root_n target on a reused
+ *                 tree is not one.
+ *   checkpoints   the snapshot set of the last run_to into HOST buffers, any of them NULL: taken_mask [n_trees] (bit j: snapshot j
+ *                 was taken), root_n [n_trees, J], counts [n_trees, J, M], probs [n_trees, J, M] (probs(temp), or
+ *                 probs_pruned(temp) with `pruned`), root_values [n_trees, J, 3], root_q [n_trees, J, M]; rows not taken are zero.
+ *                 Synchronises.  AZMI_ERR_STATE before any run_to. */
+int azmi_search_run_to(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, const uint32_t* targets, const uint32_t* checkpoints,
+                       uint32_t n_checkpoints, float temp, int pruned, int root_noise_enabled, void* stream);
+int azmi_search_checkpoints(azmi_search* s, uint32_t* taken_mask, uint32_t* root_n, uint32_t* counts, float* probs, float* root_values,
+                            float* root_q);
 
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
  *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------

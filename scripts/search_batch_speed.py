@@ -7,7 +7,7 @@
 for Connect4 (N positions x VISITS, the 6b64c bf16 net) and Tawlbwrdd (the configs/tawlbwrdd.yaml net).  Warm-up first, then
 the two versions alternate in one process; every time is taken around a device synchronise; median and spread are printed.
   python scripts/search_batch_speed.py [--game connect4|tawlbwrdd|both] [--n N] [--visits V] [--reps R] [--loop-reps L]
-                                       [--leaves-per-step K] [--play MOVES] [--evaluator net|playout]
+                                       [--leaves-per-step K] [--play MOVES] [--evaluator net|playout] [--sweep C0,C1,...]
 One JSON line per game on stdout.  --leaves-per-step K > 1 times (a) with K leaves of every tree in flight per step (WU-UCT: a
 different search, so (b) is not run beside it); every line carries the steps, the time per step and the rows per net call.
 
@@ -22,7 +22,13 @@ rollouts on the device - against (b) the loop it replaces (mcts_analysis.py:649)
 Python, one playout_eval_batch(leaves, seeds) per step, with the seeds of (a) (MCTSBatch.rollout_seed), so that the counts of every
 pair are compared.  With --leaves-per-step K > 1 (b) is the batched object calls, every leaf's playout_eval answered at once.
 Without --n / --visits it runs the four workloads of DESIGN.md 8.3: Connect4 1024 x 120, Connect4 16 x 1600 at K = 1 and K = 8,
-Tawlbwrdd 64 x 64."""
+Tawlbwrdd 64 x 64.
+
+--sweep c0,c1,... times a visit sweep on one set of trees (the inner loop of mcts_analysis.py:run_analysis): (a) one
+MCTSBatch.search_to(max, net, checkpoints=(c0, c1, ...)) plus checkpoints() - the snapshots recorded on the device on the way -
+against (b) what the batch offered before: per checkpoint search(delta, net), then counts(), probs(1.0), root_values() and
+root_q_values().  The snapshots of (a) must equal the read-outs of (b).  The same line carries the cost of the target rule itself:
+search_to(max) without checkpoints against search(max), alternating."""
 import argparse
 import json
 import os
@@ -262,6 +268,76 @@ def measure_play(az, name, n, visits, reps, loop_reps, moves):
     print(json.dumps(rec), flush=True)
 
 
+def run_sweep_to(az, mb, states, seeds, cps, net):
+    import torch
+    mb.reset(states, seeds=seeds)
+    torch.cuda.synchronize()
+    l0 = mb.stats()["launches"]
+    t0 = time.perf_counter()
+    mb.search_to(cps[-1], net=net, checkpoints=cps)
+    snap = mb.checkpoints()
+    dt = time.perf_counter() - t0
+    return dt, mb.stats()["launches"] - l0, snap
+
+
+def run_sweep_loop(az, mb, states, seeds, cps, net):
+    """The sweep without search_to: every checkpoint ends the enqueued run, four read-outs and four copies each."""
+    import torch
+    mb.reset(states, seeds=seeds)
+    torch.cuda.synchronize()
+    l0 = mb.stats()["launches"]
+    t0 = time.perf_counter()
+    prev, rows = 0, []
+    for c in cps:
+        mb.search(c - prev, net=net)
+        rows.append((mb.counts(), mb.probs(1.0), mb.root_values(), mb.root_q_values()))
+        prev = c
+    dt = time.perf_counter() - t0
+    snap = {k: np.stack([r[i] for r in rows], axis=1) for i, k in enumerate(("counts", "probs", "root_values", "root_q_values"))}
+    return dt, mb.stats()["launches"] - l0, snap
+
+
+def run_plain(az, mb, states, seeds, visits, net, to):
+    import torch
+    mb.reset(states, seeds=seeds)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if to:
+        mb.search_to(visits, net=net)
+    else:
+        mb.search(visits, net=net)
+    mb.synchronize()
+    return time.perf_counter() - t0
+
+
+def measure_sweep(az, name, n, cps, reps):
+    from alphazero import torch_net
+    Game, spec, plies = {"connect4": (az.Connect4GS, torch_net.connect4_spec(), 12),
+                         "tawlbwrdd": (az.TawlbwrddGS, torch_net.tawlbwrdd_spec(), 6)}[name]
+    net = az.HipLeafNet(torch_net.random_init(spec, seed=0), spec, precision="bf16")
+    rng = np.random.default_rng(1)
+    states = positions(az, Game, n, rng, plies)
+    seeds = [1 + i for i in range(n)]
+    mb = az.MCTSBatch(Game, n, 1.25, max_simulations=cps[-1], seeds=seeds)
+    stats = lambda x: dict(median=statistics.median(x), min=min(x), max=max(x), runs=len(x))
+    rec = dict(mode="sweep", game=name, positions=n, checkpoints=list(cps))
+    run_plain(az, mb, states, seeds, cps[-1], net, False)          # warm-up (code objects, the net's scratch)
+    run_sweep_to(az, mb, states, seeds, cps, net)
+    a, b, s_plain, s_to, la, lb, same = [], [], [], [], 0, 0, True
+    for _ in range(reps):
+        s_plain.append(run_plain(az, mb, states, seeds, cps[-1], net, False))
+        s_to.append(run_plain(az, mb, states, seeds, cps[-1], net, True))
+        dt, la, snap_a = run_sweep_to(az, mb, states, seeds, cps, net)
+        a.append(dt)
+        dt, lb, snap_b = run_sweep_loop(az, mb, states, seeds, cps, net)
+        b.append(dt)
+        same = same and bool(snap_a["taken"].all()) and all(np.array_equal(snap_a[k], snap_b[k]) for k in snap_b)
+    rec.update(search_s=stats(s_plain), search_to_s=stats(s_to), search_to_over_search=statistics.median(s_to) / statistics.median(s_plain),
+               sweep_to_s=stats(a), sweep_loop_s=stats(b), ratio=statistics.median(b) / statistics.median(a), sweep_to_launches=la,
+               sweep_loop_launches=lb, same_snapshots=same)
+    print(json.dumps(rec), flush=True)
+
+
 def measure(az, name, n, visits, reps, loop_reps, leaves_per_step=1):
     from alphazero import torch_net
     Game, spec, plies = {"connect4": (az.Connect4GS, torch_net.connect4_spec(), 12),
@@ -306,8 +382,14 @@ def main():
     ap.add_argument("--loop-reps", type=int, default=2, help="runs of the stand-alone-object loop (minutes each at full size; 0 = skip)")
     ap.add_argument("--leaves-per-step", type=int, default=1, help="K leaves of every tree in flight per step (1 = the plain search)")
     ap.add_argument("--evaluator", default="net", choices=["net", "playout"], help="playout: rollouts on the device against the playout_eval_batch loop")
+    ap.add_argument("--sweep", default="", metavar="C0,C1,...", help="time search_to(max, checkpoints) + checkpoints() against per-checkpoint search + read-outs")
     args = ap.parse_args()
     import alphazero as az
+    if args.sweep:
+        cps = tuple(int(x) for x in args.sweep.split(","))
+        for name in (["connect4", "tawlbwrdd"] if args.game == "both" else [args.game]):
+            measure_sweep(az, name, args.n or (1024 if name == "connect4" else 256), cps, args.reps)
+        return
     if args.evaluator == "playout":
         if args.play:
             ap.error("--evaluator playout times search(), not --play")
