@@ -166,15 +166,16 @@ def self_play(game, params, net=None, engines=None, seed=20240601, device=0, str
         simulations=sum(c["sims"] for c in cn), leaf_evaluations=sum(c["evals"] for c in cn), samples=n_samples)
     # per-variant read-out: the shards' raw sums (azmi_pm_variant_sums) added up, then the reference's own divisions
     for vid in range(pms[0].num_tracked_variants()):
-        vs = np.sum([pm.variant_sums(vid) for pm in pms], 0)
+        vs = dict(zip(PlayManager._SUM_KEYS, np.sum([pm.variant_sums(vid) for pm in pms], 0)))
         vscores = np.sum([pm.variant_scores(vid) for pm in pms], 0)
-        res.variant_game_counts[vid] = int(vs[1])
-        if vs[1] > 0:
+        res.variant_game_counts[vid] = int(vs["games"])
+        if vs["games"] > 0:
             vn = float(vscores.sum())
             res.variant_win_rates[vid] = [div(float(x), vn) for x in vscores]
-            res.variant_metrics[vid] = dict(game_length=div(vs[0], vs[1]), avg_depth=div(vs[5], vs[3]), avg_entropy=div(vs[6], vs[3]),
-                                            avg_mpt=div(vs[2], vs[0]), avg_vm=div(vs[9], vs[2]), fast_avg_depth=div(vs[7], vs[4]),
-                                            fast_avg_entropy=div(vs[8], vs[4]))
+            res.variant_metrics[vid] = dict(game_length=div(vs["game_length"], vs["games"]), avg_depth=div(vs["leaf_depth"], vs["full_moves"]),
+                                            avg_entropy=div(vs["entropy"], vs["full_moves"]), avg_mpt=div(vs["moves"], vs["game_length"]),
+                                            avg_vm=div(vs["valid_moves"], vs["moves"]), fast_avg_depth=div(vs["fast_leaf_depth"], vs["fast_moves"]),
+                                            fast_avg_entropy=div(vs["fast_entropy"], vs["fast_moves"]))
     if no_net:
         res.driver_used = "none"
     else:

@@ -61,7 +61,7 @@ MAP = {
         "GameState.ScoresNotOverInitially": SG + "case_initial_state",
         "GameState.ValidMovesOnTurnOne": SG + "case_turn_one_is_deploy_only", "GameState.DeployAction": SG + "case_deploy_switches_player",
         "GameState.CopyEquality": SG + "case_deploy_switches_player", "GameState.Canonicalized": SG + "case_initial_state (shape) / case_observation_channels (contents)",
-        "GameState.DumpOutput": NB + "dump() of the Python object prints the same header lines (alphazero/__init__.py), not pinned",
+        "GameState.DumpOutput": NB + "dump() of the Python object prints the same header lines (alphazero/games.py), not pinned",
         "TurnStructure.TurnOneIsDeployOnly": SG + "case_turn_one_is_deploy_only",
         "TurnStructure.AfterTurnOneCanMoveAndFire": SG + "case_notation_game / case_fire_and_damage",
         "Combat.CannonInfo*": SG + "case_unit_and_action_space_constants (cannon slots of a fresh unit: 1 / 3 / 4) + case_fire_and_damage (ranges, damage)",

@@ -79,7 +79,7 @@ def test_evaluator_argument_errors_come_before_any_device_call(capi, monkeypatch
     import alphazero as az
     mb = object.__new__(az.MCTSBatch)                          # no device: the checks below need none
     mb._h = None
-    monkeypatch.setattr(az, "lib", _Lib())
+    monkeypatch.setattr(az.search_batch, "lib", _Lib())
     net, cache = object(), object()
     for call in (mb.search, mb.play):
         with pytest.raises(RuntimeError, match="takes no cache"):
