@@ -204,6 +204,8 @@ SYMBOLS = {
     "azmi_search_sync": (C.c_int, [_VP]),
     "azmi_search_stats": (C.c_int, [_VP, _VP]),
     "azmi_search_set_leaves_per_step": (C.c_int, [_VP, C.c_uint32]),
+    "azmi_search_set_descents_per_step": (C.c_int, [_VP, C.c_uint32]),
+    "azmi_search_host_reads": (C.c_int, [_VP, _VP]),
     "azmi_search_pick_moves": (C.c_int, [_VP, C.c_float, _VP, _VP]),
     "azmi_search_update_roots": (C.c_int, [_VP, _VP, _VP]),
     "azmi_search_root_prior": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),

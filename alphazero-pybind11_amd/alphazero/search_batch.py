@@ -62,6 +62,35 @@ class MCTSBatch:
     cache with "playout" is an error (the reference's playout branch bypasses the cache), as is "playout" or "random" with a
     net and "net" without one.  stats()["evaluator_leaves"] counts the rollouts.
 
+    `descents_per_step=L` (1 <= L <= 256, default 1: everything above unchanged) keeps a tree descending inside a step while
+    its leaves need nothing from the net - the per-tree loop of mcts_analysis.py:921-951.  With L > 1 one step of a live tree i
+    of search() / play() is
+
+        d = 0
+        while d < L and todo[i] > 0:
+            leaf = find_leaf(root); d += 1; todo[i] -= 1
+            terminal leaf, RANDOM evaluator or cache hit: process_result at once, continue
+            otherwise: the leaf's planes become the tree's ONE row of the step ("playout": its one rollout); break
+        evaluate all rows in one call; insert them into the cache
+        process_result for every tree with a pending row
+
+    so a search needs fewer steps than visits where the leaves are mostly immediate for every tree at once: a warm shared
+    cache (measured 2.0 x / 2.7 x faster at L = 4 / 16), evaluator="random", where search(visits) is ceil(visits / L) launches,
+    the last plies of games.  A step lasts as long as the longest chain of immediate descents among the trees and the step
+    count falls only as fast as the least lucky tree allows, so with a cold cache, and over whole games from the opening,
+    L > 1 measured slower than L = 1: the default stays 1.  Tree i makes the same find_leaf /
+    process_result calls in the same order as with L = 1 and stays bit for bit the stand-alone MCTS(seed=seeds[i]); only the
+    cache's hit / miss counts and eviction state may differ.  The j-th rollout of a tree keeps its seed; a Gumbel batch is the
+    same loop.  search(visits) and every move of play() give every live tree exactly `visits` descents through a per-tree
+    counter on the device.  The read policy: "random" enqueues exactly ceil(visits / L) steps and reads nothing; with a net or
+    "playout" the call enqueues ceil(visits / L) steps, then repeats { read r, the largest count any tree has left (one
+    4-byte word); stop at 0; enqueue m more steps }, where m = ceil(r / L) behind the first read (the fewest steps that can
+    finish), max(ceil(r / L), twice the previous m) behind every later one, and never more than r.  Every step gives every
+    unfinished tree at least one descent, so r steps always finish and the rounds at least double: at most
+    1 + ceil(log2(visits)) reads per search, counted in stats()["host_reads"]; stats()["steps"] counts enqueued steps, those in which no tree had work left included.  play()
+    picks a move only behind the read of 0.  L > 1 together with leaves_per_step > 1, search_to() and the step API
+    (find_leaves / process_results: the caller owns the evaluator and the step) raise RuntimeError before any launch.
+
     A visit sweep (mcts_analysis.py:884-972): search_to(targets, ..., checkpoints=(c0, c1, ...)) searches tree i until
     root_n(i) >= targets[i] and records counts / probs / root_values / root_q_values on the device the first time root_n(i)
     reaches each checkpoint; checkpoints() returns the snapshots.  See search_to()."""
@@ -112,9 +141,17 @@ class MCTSBatch:
 
     def __init__(self, game, n, cpuct, epsilon=0.0, root_policy_temp=1.0, fpu_reduction=0.0, root_fpu_zero=False,
                  shaped_dirichlet=False, gumbel_enabled=False, gumbel_m=16, gumbel_c_visit=50.0, gumbel_c_scale=1.0,
-                 gumbel_full=False, *, max_simulations, seeds=None, device=0, leaves_per_step=1):
+                 gumbel_full=False, *, max_simulations, seeds=None, device=0, leaves_per_step=1,
+                 descents_per_step=1):
         if isinstance(leaves_per_step, bool) or not isinstance(leaves_per_step, (int, np.integer)) or not 1 <= leaves_per_step <= 64:
             raise RuntimeError(f"leaves_per_step must be an integer in [1, 64], got {leaves_per_step!r}")
+        if (isinstance(descents_per_step, bool) or not isinstance(descents_per_step, (int, np.integer))
+                or not 1 <= descents_per_step <= 256):
+            raise RuntimeError(f"descents_per_step must be an integer in [1, 256], got {descents_per_step!r}")
+        if descents_per_step > 1 and leaves_per_step > 1:
+            raise RuntimeError(f"descents_per_step = {descents_per_step} with leaves_per_step = {leaves_per_step}: a step holds "
+                               "either several leaves of a tree in flight or goes on descending past the leaves that need no "
+                               "evaluator, not both")
         if leaves_per_step > 1 and gumbel_enabled:
             raise RuntimeError(f"leaves_per_step = {leaves_per_step} with gumbel_enabled: the batched descent (find_leaf_batched) "
                                "is plain PUCT; use leaves_per_step = 1 for a Gumbel search")
@@ -132,12 +169,25 @@ class MCTSBatch:
         self._rows = None          # rows of the pending find_leaves() batch
         self._start = None         # the states of the last reset()
         self._k = int(leaves_per_step)
+        self._dl = 1
         if self._k > 1:
             check(lib.azmi_search_set_leaves_per_step(self._h, self._k))
+        if descents_per_step > 1:
+            check(lib.azmi_search_set_descents_per_step(self._h, int(descents_per_step)))
+            self._dl = int(descents_per_step)
 
     @property
     def leaves_per_step(self):
         return self._k
+
+    @property
+    def descents_per_step(self):
+        return getattr(self, "_dl", 1)
+
+    def _one_descent_per_step(self, what, why):
+        if self.descents_per_step > 1:
+            raise RuntimeError(f"{what} with descents_per_step = {self.descents_per_step}: {why}; use search / play, or "
+                               "descents_per_step = 1")
 
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:
@@ -196,7 +246,10 @@ class MCTSBatch:
 
     def search(self, visits, net=None, cache=None, root_noise=False, evaluator=None):
         """`visits` simulations of every tree, enqueued without host synchronisation (the read-outs and synchronize() wait);
-        with leaves_per_step = K: visits // K steps of K descents and one of visits % K.
+        with leaves_per_step = K: visits // K steps of K descents and one of visits % K.  With descents_per_step = L > 1 the
+        call gives every live tree exactly `visits` descents in ceil(visits / L) steps ("random": exactly, nothing read) or
+        more (net, "playout": one 4-byte read after them, then more steps per read of r > 0, at most
+        1 + ceil(log2(visits)) reads; the call returns behind the read of 0) - see the class for the policy.
         net: a HipLeafNet (None = EvalType.RANDOM, dumb_eval); cache: a ShardedS3FIFOCache shared by all trees;
         evaluator: None (the net if given, else RANDOM), "net", "random", "playout" or an EvalType - see the class."""
         ev = self._evaluator("search", evaluator, net, cache)
@@ -219,6 +272,8 @@ class MCTSBatch:
         search_to starts a fresh set.  `temp`, `pruned`: the snapshots hold probs(temp), or probs_pruned(temp).
         The call reads root_n once, then enqueues every step without reading anything back; the budget is checked for the
         longest tree's steps x K before anything is enqueued.  A Gumbel batch raises: use search(visits)."""
+        self._one_descent_per_step("search_to", "the checkpoint launches are planned from one root_n read and one descent of "
+                                   "every tree per step")
         ev = self._evaluator("search_to", evaluator, net, cache)
         if net is not None and (net.desc.num_moves != self._M or (net.desc.in_channels, net.desc.height, net.desc.width) != self._chw):
             raise RuntimeError("search_to: the net's shape does not match the game")
@@ -342,6 +397,7 @@ class MCTSBatch:
         order, then descent order (terminal leaves are backed up at once and take no row).  Device tensors
         (views of the object's buffers, valid until the next find_leaves) when torch is importable, numpy arrays otherwise or
         with numpy=True."""
+        self._one_descent_per_step("find_leaves", "the step API's caller owns the evaluator and the step")
         pc, pt, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
         check(lib.azmi_search_find_leaves(self._h, _ENGINE_STREAM, C.byref(pc), C.byref(pt), C.byref(n)))
         self._rows = n.value
@@ -369,6 +425,7 @@ class MCTSBatch:
     def process_results(self, v, pi, root_noise=False):
         """The evaluator's answers for the rows of the last find_leaves(): v [n_rows, P+1], pi [n_rows, M] probabilities,
         device tensors or numpy arrays."""
+        self._one_descent_per_step("process_results", "the step API's caller owns the evaluator and the step")
         if self._rows is None:
             raise RuntimeError("process_results: no leaf batch is pending; call find_leaves first")
         rows = self._rows
@@ -412,7 +469,12 @@ class MCTSBatch:
 
     def stats(self):
         """launches: kernel launches the object has enqueued since creation (the net's own not included); net_calls; steps;
-        simulations / evaluator_leaves / terminal_leaves since the last reset, summed over the trees."""
+        simulations / evaluator_leaves / terminal_leaves since the last reset, summed over the trees; host_reads: the 4-byte
+        reads search() / play() have made since creation (descents_per_step > 1 with a net or "playout"; 0 otherwise)."""
         out = np.zeros(6, np.uint64)
         check(lib.azmi_search_stats(self._h, out.ctypes.data))
-        return dict(zip(("launches", "net_calls", "steps", "simulations", "evaluator_leaves", "terminal_leaves"), (int(x) for x in out)))
+        reads = C.c_uint64()
+        check(lib.azmi_search_host_reads(self._h, C.byref(reads)))
+        st = dict(zip(("launches", "net_calls", "steps", "simulations", "evaluator_leaves", "terminal_leaves"), (int(x) for x in out)))
+        st["host_reads"] = int(reads.value)
+        return st

@@ -8,6 +8,8 @@
 // kernels and launch helpers below; K == 1 runs the original ones.
 // azmi_search_run_eval / play_eval with AZMI_EVAL_PLAYOUT evaluate every leaf by a random rollout on the device (the *_po kernels):
 // no compaction, no net call, no cache insert, at most 3 launches a step.
+// azmi_search_set_descents_per_step(L > 1) lets a tree go on descending inside a step while its leaves need no evaluator (terminal,
+// RANDOM, cache hit): the *_dl kernels; a search then needs fewer steps than visits, and reads one word back to know how many.
 // azmi_search_run_to searches every tree to its own root_n target and snapshots the read-outs at checkpoints on the way
 // (mcts_analysis.py:884-972): the steps above, plus the checkpoint kernel at the steps the host knows something can happen at.
 #include <hip/hip_runtime.h>
@@ -66,6 +68,11 @@ struct azmi_search {
   uint32_t sw_cap = 0;                // checkpoints the block has room for
   bool sw_valid = false;              // a run_to call has defined the snapshot set
   std::vector<uint32_t> sw_upload;    // targets [N] + checkpoints [32]: the host side of the call's upload (kept until the next call)
+  // descents_per_step (azmi_search_set_descents_per_step): up to L descents of a tree per step while its leaves need no evaluator
+  uint32_t dl_L = 1;
+  SbDlArrays dl{};                    // todo [N], todo_max [2]
+  uint32_t dl_parity = 0;             // parity of the next step of the running search: the todo_max word it raises
+  uint64_t host_reads = 0;            // 4-byte reads of todo_max since creation
 };
 
 namespace {
@@ -126,6 +133,11 @@ void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArr
 void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st);
 // the checkpoint kernel of azmi_search_run_to (also at the end of the file)
 void launch_checkpoint(azmi_search* s, float temp, uint32_t pruned, uint32_t resume, hipStream_t st);
+// descents_per_step > 1 (also at the end of the file): the counter launch of a search, the find launch(es) of a step
+void launch_todo_set(azmi_search* s, uint32_t visits, hipStream_t st);
+void launch_find_dl(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, uint32_t eval_random, uint32_t root_noise,
+                    hipStream_t st);
+void launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, hipStream_t st);
 
 // ---- K > 1: the same steps over K descents of every tree; the launch counts do not depend on N or K ---------------------------
 EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine arrays with the step-sized [K * N] row buffers in place
@@ -248,7 +260,22 @@ int enqueue_step(azmi_search* s, const SearchArgs& a, uint32_t kk, uint32_t rn, 
   const EngineParams& ep = a.ep;
   const EngineArrays& ar = a.ar;
   azmi_net* net = a.net;
-  if (a.playout) {
+  if (s->dl_L > 1) {      // up to L descents of every tree that still owes some; at most one row per tree, so the rest of the step is K == 1's
+    const uint32_t parity = s->dl_parity;
+    s->dl_parity ^= 1u;
+    if (a.playout) launch_find_dl_playout(s, ep, ar, parity, st);
+    else {
+      launch_find_dl(s, ep, ar, parity, net ? 0u : 1u, rn, st);
+      if (net) {
+        const int rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
+        if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
+        s->net_calls += 1;
+        if (ep.cache_on) launch_cache_insert(s, ep, ar, s->n, st);
+      }
+    }
+    // RANDOM leaves nothing pending (every descent is backed up by the find kernel): no process launch
+    if (net || a.playout) launch_process(s, ep, ar, rn, nullptr, nullptr, st);
+  } else if (a.playout) {
     if (s->k_leaves > 1) launch_step_playout_wu(s, ep, ar, kk, rn, st);
     else launch_step_playout(s, ep, ar, rn, st);
   } else if (s->k_leaves > 1) {
@@ -275,10 +302,46 @@ int enqueue_step(azmi_search* s, const SearchArgs& a, uint32_t kk, uint32_t rn, 
   return AZMI_OK;
 }
 
+// descents_per_step = L > 1: every live tree owes `visits` descents (todo, set by one launch) and pays up to L of them per step, as
+// long as they need no evaluator.  RANDOM: every descent is immediate, so ceil(visits / L) steps complete the search and nothing
+// is read.  Net / PLAYOUT: ceil(visits / L) steps, then repeat { read r = the largest todo the last step left (4 bytes); stop at 0;
+// enqueue m more steps }: m = ceil(r / L) behind the first read (the fewest steps that can finish: all that a search whose leaves
+// are terminal or cached needs), max(ceil(r / L), twice the previous m) behind every later one, and never more than r.  Every step
+// gives every tree that owes descents at least one, so r steps always finish, and round k >= 1 holds at least 2^(k-1) steps unless it
+// is capped at r: the search is complete behind round ceil(log2(visits)) at the latest, after at most 1 + ceil(log2(visits)) reads.
+// (Halving r instead - max(1, ceil(r / 2)) steps per read - takes 1 + visits / 2 steps where the leaves are all immediate and 2 do.)
+// The call returns behind the read of 0: only the last step's back-up may still be running
+int enqueue_search_dl(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
+  if (!visits) return AZMI_OK;
+  launch_todo_set(s, visits, st);
+  s->dl_parity = 0;
+  const bool blind = !a.net && !a.playout;
+  uint32_t more = (visits + s->dl_L - 1) / s->dl_L;
+  for (uint32_t reads = 0;; ++reads) {      // round `reads` of `more` steps
+    for (uint32_t i = 0; i < more; ++i) {
+      const int rc = enqueue_step(s, a, 1, rn, st);
+      if (rc != AZMI_OK) return rc;
+    }
+    SB_TRY(hipGetLastError());
+    if (blind) break;
+    if (reads > 40) return SB_FAIL(AZMI_ERR_STATE, "search: the trees' descent counters did not reach 0 (descents_per_step)");      // (unreachable: 33 reads bound a uint32 budget)
+    uint32_t r = 0;
+    SB_TRY(hipMemcpyAsync(&r, s->dl.todo_max + (s->dl_parity ^ 1u), 4, hipMemcpyDeviceToHost, st));
+    SB_TRY(hipStreamSynchronize(st));
+    s->host_reads += 1;
+    if (r == 0) break;
+    const uint32_t fewest = (r + s->dl_L - 1) / s->dl_L;
+    more = std::min<uint32_t>(r, reads == 0 ? fewest : std::max<uint32_t>(fewest, more > 0x7FFFFFFFu ? more : 2u * more));
+  }
+  s->sims_done += visits;
+  return AZMI_OK;
+}
+
 // the steps of search(visits) on `st`, nothing read back: azmi_search_run, and every move of azmi_search_play.  Enqueued back to
 // back: the row count of a step never leaves the device.  K > 1: visits / K steps of K descents and one of the remainder
 int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
   if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
+  if (s->dl_L > 1) return enqueue_search_dl(s, a, visits, rn, st);
   for (uint32_t left = visits; left;) {
     const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
     const int rc = enqueue_step(s, a, kk, rn, st);
@@ -385,6 +448,7 @@ int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, 
   if (rc == AZMI_OK) rc = A(s->pl.final, N * (pm->gi.P + 1)); if (rc == AZMI_OK) rc = A(s->d_moves_in, N);
   if (rc == AZMI_OK) rc = A(s->ro.seeds, N); if (rc == AZMI_OK) rc = A(s->ro.count, N);
   if (rc == AZMI_OK) rc = A(s->ro.states, game == AZMI_GAME_CONNECT4 ? N * sizeof(Connect4::State) : 1);
+  if (rc == AZMI_OK) rc = A(s->dl.todo, N); if (rc == AZMI_OK) rc = A(s->dl.todo_max, 2);
   if (rc != AZMI_OK) { azmi_pm_destroy(pm); delete s; return rc; }
   *out = s;
   return AZMI_OK;
@@ -405,6 +469,9 @@ int azmi_search_set_leaves_per_step(azmi_search* s, uint32_t k) {
   if (k > 1 && s->gumbel)
     return SB_FAIL(AZMI_ERR_INVALID, "leaves_per_step = %u with gumbel_enabled: the batched descent (find_leaf_batched) is plain PUCT; "
                    "use leaves_per_step = 1 for a Gumbel search", k);
+  if (k > 1 && s->dl_L > 1)
+    return SB_FAIL(AZMI_ERR_INVALID, "leaves_per_step = %u with descents_per_step = %u: a step holds either several leaves of a tree in flight "
+                   "or goes on descending past the leaves that need no evaluator, not both", k, s->dl_L);
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "set_leaves_per_step: a find_leaves step is pending; call process_results first");
   if (s->sims_done != 0) return SB_FAIL(AZMI_ERR_STATE, "set_leaves_per_step: the trees have been searched; call reset first");
   azmi_pm* pm = s->pm;
@@ -444,6 +511,24 @@ int azmi_search_set_leaves_per_step(azmi_search* s, uint32_t k) {
     return SB_FAIL(AZMI_ERR_OOM, "leaves_per_step = %u: %llu bytes of device memory: %s", k, need, hipGetErrorString(e));
   }
   s->k_leaves = k;
+  return AZMI_OK;
+}
+
+int azmi_search_set_descents_per_step(azmi_search* s, uint32_t l) {
+  if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (l < 1 || l > 256) return SB_FAIL(AZMI_ERR_INVALID, "descents_per_step must be in [1, 256], got %u", l);
+  if (l > 1 && s->k_leaves > 1)
+    return SB_FAIL(AZMI_ERR_INVALID, "descents_per_step = %u with leaves_per_step = %u: a step holds either several leaves of a tree in flight "
+                   "or goes on descending past the leaves that need no evaluator, not both", l, s->k_leaves);
+  if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "set_descents_per_step: a find_leaves step is pending; call process_results first");
+  if (s->sims_done != 0) return SB_FAIL(AZMI_ERR_STATE, "set_descents_per_step: the trees have been searched; call reset first");
+  s->dl_L = l;
+  return AZMI_OK;
+}
+
+int azmi_search_host_reads(azmi_search* s, uint64_t* out) {
+  if (!s || !out) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  *out = s->host_reads;
   return AZMI_OK;
 }
 
@@ -505,6 +590,9 @@ int azmi_search_find_leaves(azmi_search* s, void* stream, float** dev_canonical,
   int rc = begin_step(s, "find_leaves"); if (rc) return rc;
   if (!n_rows) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "find_leaves: the previous step's process_results has not been called");
+  if (s->dl_L > 1)
+    return SB_FAIL(AZMI_ERR_INVALID, "find_leaves with descents_per_step = %u: the step API's caller owns the evaluator and the step, one "
+                   "descent of every tree each; use search / play, or descents_per_step = 1", s->dl_L);
   rc = check_budget(s, "find_leaves", 1); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
@@ -798,6 +886,9 @@ int azmi_search_run_to(azmi_search* s, int eval_type, azmi_net* net, azmi_cache*
   int rc = begin_step(s, "search_to"); if (rc) return rc;
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "search_to: a find_leaves step is pending; call process_results first");
   if (!targets || (n_checkpoints && !checkpoints)) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (s->dl_L > 1)
+    return SB_FAIL(AZMI_ERR_INVALID, "search_to with descents_per_step = %u: the checkpoint launches are planned from one root_n read and one "
+                   "descent of every tree per step; use search(visits), or descents_per_step = 1", s->dl_L);
   if (s->gumbel)
     return SB_FAIL(AZMI_ERR_INVALID, "search_to on a Gumbel batch: sequential halving plans a fixed budget at its first descent, and a "
                    "root_n target on a reused tree is not one; use search(visits)");
@@ -881,3 +972,29 @@ int azmi_search_checkpoints(azmi_search* s, uint32_t* taken_mask, uint32_t* root
 }
 
 }  // extern "C"
+
+// ---- descents_per_step > 1: the kernels of search_batch_kernels.h's last section, instantiated behind everything else -------------
+namespace {
+
+void launch_todo_set(azmi_search* s, uint32_t visits, hipStream_t st) {
+  k_sb_todo_set<<<(s->n + 255) / 256, 256, 0, st>>>(s->sb, s->dl, s->n, visits);
+  s->launches += 1;
+}
+
+void launch_find_dl(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, uint32_t eval_random, uint32_t root_noise,
+                    hipStream_t st) {
+  SB_LAUNCH(s, st, k_sb_find_dl, k_sb_big_find_dl, ep, ar, s->sb, s->dl, s->n, s->dl_L, parity, eval_random, root_noise);
+  if (eval_random) return;      // no row is ever pending: nothing to number
+  k_sb_compact<<<1, 1024, 0, st>>>(s->sb, s->n);
+  s->launches += 1;
+}
+
+void launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, hipStream_t st) {
+  const uint32_t n = s->n;
+  SB_LAUNCH(s, st, k_sb_find_dl_po, k_sb_big_find_dl_po, ep, ar, s->sb, s->dl, s->ro, n, s->dl_L, parity);
+  sb_for_game(s->pm->game,
+              [&](auto tag) { using GM = decltype(tag); k_sb_rollout<GM><<<(n + 63) / 64, 64, 0, st>>>(ar, s->sb, s->ro, n); s->launches += 1; },
+              [&](auto) {});
+}
+
+}  // namespace

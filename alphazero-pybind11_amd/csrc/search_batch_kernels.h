@@ -1019,4 +1019,215 @@ __global__ __launch_bounds__(64) void k_sb_big_checkpoint(EngineParams ep, Engin
   if (lane == 0) sb_checkpoint_tail(sb, sw, slot, status, root_n, resume);
 }
 
+// ======================= descents that need no evaluator do not end a tree's step (descents_per_step = L > 1) ======================
+// The per-tree loop of the evaluation tools (mcts_analysis.py:921-951): `while root_n < target: find_leaf; a cache hit is backed up
+// and the loop goes on; a miss ends the tree's turn in the round`.  One step of a live tree is up to L calls of find_leaf, each
+// backed up at once by process_result while it needs nothing from the evaluator (terminal leaf, RANDOM, cache hit); the first leaf
+// that does becomes the tree's ONE row of the step and ends its loop, so k_sb_compact, the net call over the row list,
+// k_cache_insert, k_sb_rollout and the process kernels run behind these kernels as they run behind k_sb_find / k_sb_find_po.  The
+// calls a tree makes, and their order, are those of L == 1: only where the step boundaries fall changes.
+//   todo[i]       descents tree i still owes the running search / move (set by k_sb_todo_set, 0 for a finished or stopped tree)
+//   todo_max[2]   the largest todo a step leaves behind, by step parity: the find kernel of step t raises word t & 1 with one
+//                 atomicMax per tree that still owes descents and clears word (t + 1) & 1 for the step behind it, so the word
+//                 costs no launch of its own.  The host reads word t & 1 behind step t: 0 = the search is complete
+struct SbDlArrays {
+  uint32_t* todo;       // [N]
+  uint32_t* todo_max;   // [2]
+};
+
+__global__ __launch_bounds__(256) void k_sb_todo_set(SbArrays sb, SbDlArrays dl, uint32_t n, uint32_t visits) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 2) dl.todo_max[i] = 0;
+  if (i < n) dl.todo[i] = sb.status[i] == 0 ? visits : 0u;
+}
+
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_find_dl(EngineParams ep, EngineArrays ar, SbArrays sb, SbDlArrays dl, uint32_t n, uint32_t L,
+                                                    uint32_t parity, uint32_t eval_random, uint32_t root_noise) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (gtid == 0) dl.todo_max[parity ^ 1u] = 0;
+  if (slot >= n) return;
+  uint32_t left = dl.todo[slot];
+  if (sb.status[slot] != 0 || left == 0) {      // (the step before left nothing pending)
+    if (lane == 0) { sb.pend[slot] = kPendNone; if (ep.cache_on) ar.cache_keys[slot] = 0; }
+    return;
+  }
+  SlotCtx<GM> c(ep, ar, slot, lane);
+  c.load();
+  uint32_t pend = kPendNone, n_term = 0;
+  uint64_t ins_key = 0;
+  for (uint32_t d = 0; d < L && left > 0; ++d) {
+    --left;
+    typename GM::State leaf;
+    uint32_t term = 0, from_net = 1;
+    if (!c.find_leaf(0, leaf, term)) {      // the tree stops: it owes nothing more
+      if (lane == 0) sb.status[slot] = kSbFindFailed;
+      left = 0;
+      break;
+    }
+    if (term != 0) ++n_term;
+    else if (eval_random) from_net = 0;
+    else {
+      const uint64_t key = GM::key(leaf);
+      float hit_pi = 0.0f, hit_v = 0.0f;
+      if (!(ep.cache_on && c.cache_lookup(key, 0, hit_pi, hit_v))) {
+        c.emit_leaf(leaf, key);
+        if (lane == 0) ar.c_evals[slot] += 1;
+        ins_key = cache_key(key);
+        pend = kPendRow;
+        break;
+      }
+    }
+    c.process_result(0, from_net != 0, term == 0 && root_noise != 0);     // what k_sb_find / k_sb_process pass for this kind of leaf
+  }
+  if (lane == 0) {
+    sb.pend[slot] = static_cast<uint8_t>(pend);
+    if (ep.cache_on) ar.cache_keys[slot] = ins_key;
+    if (n_term) sb.n_term[slot] += n_term;
+    dl.todo[slot] = left;
+    if (left) atomicMax(&dl.todo_max[parity], left);
+  }
+  c.store(kSlotWaitEval);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_find_dl(EngineParams ep, EngineArrays ar, SbArrays sb, SbDlArrays dl, uint32_t n, uint32_t L,
+                                                       uint32_t parity, uint32_t eval_random, uint32_t root_noise) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot == 0 && lane == 0) dl.todo_max[parity ^ 1u] = 0;
+  if (slot >= n) return;
+  uint32_t left = dl.todo[slot];
+  if (sb.status[slot] != 0 || left == 0) {
+    if (lane == 0) { sb.pend[slot] = kPendNone; if (ep.cache_on) ar.cache_keys[slot] = 0; }
+    return;
+  }
+  BigSlot<GM> c(ep, ar, sm, slot, lane);
+  c.load();
+  uint32_t pend = kPendNone, n_term = 0;
+  uint64_t ins_key = 0;
+  for (uint32_t d = 0; d < L && left > 0; ++d) {
+    --left;
+    typename GM::State leaf;
+    uint32_t term = 0, from_net = 1;
+    if (!c.find_leaf(0, leaf, term)) {
+      if (lane == 0) sb.status[slot] = kSbFindFailed;
+      left = 0;
+      break;
+    }
+    if (term != 0) ++n_term;
+    else if (eval_random) from_net = 0;
+    else {
+      const uint64_t key = c.emit_leaf(leaf);
+      if (!(ep.cache_on && c.cache_lookup(key, 0))) {
+        if (lane == 0) ar.c_evals[slot] += 1;
+        ins_key = cache_key(key);
+        pend = kPendRow;
+        break;
+      }
+    }
+    c.process_result(0, from_net != 0, term == 0 && root_noise != 0);
+  }
+  if (lane == 0) {
+    sb.pend[slot] = static_cast<uint8_t>(pend);
+    if (ep.cache_on) ar.cache_keys[slot] = ins_key;
+    if (n_term) sb.n_term[slot] += n_term;
+    dl.todo[slot] = left;
+    if (left) atomicMax(&dl.todo_max[parity], left);
+  }
+  c.sync();
+  c.store(kSlotWaitEval);
+}
+
+// EvalType::PLAYOUT: a terminal leaf is free, a leaf that needs a rollout ends the tree's step like a net row (Connect4: parked
+// for k_sb_rollout; wide games: rolled out here, behind its descent).  No further rollout is inlined, so the j-th rollout of a
+// tree is the j-th of the L == 1 search and keeps its seed
+template <class GM>
+__global__ __launch_bounds__(256) void k_sb_find_dl_po(EngineParams ep, EngineArrays ar, SbArrays sb, SbDlArrays dl, SbRollArrays ro, uint32_t n,
+                                                       uint32_t L, uint32_t parity) {
+  constexpr int G = GM::GROUP;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t slot = gtid / G, lane = gtid % G;
+  if (gtid == 0) dl.todo_max[parity ^ 1u] = 0;
+  if (slot >= n) return;
+  uint32_t left = dl.todo[slot];
+  if (sb.status[slot] != 0 || left == 0) {
+    if (lane == 0) sb.pend[slot] = kPendNone;
+    return;
+  }
+  SlotCtx<GM> c(ep, ar, slot, lane);
+  c.load();
+  uint32_t pend = kPendNone, n_term = 0;
+  for (uint32_t d = 0; d < L && left > 0; ++d) {
+    --left;
+    typename GM::State leaf;
+    uint32_t term = 0;
+    if (!c.find_leaf(0, leaf, term)) {
+      if (lane == 0) sb.status[slot] = kSbFindFailed;
+      left = 0;
+      break;
+    }
+    if (term == 0) {
+      if (lane == 0) { reinterpret_cast<typename GM::State*>(ro.states)[slot] = leaf; ar.c_evals[slot] += 1; }
+      pend = kPendRollout;
+      break;
+    }
+    ++n_term;
+    c.process_result(0, true, false);
+  }
+  if (lane == 0) {
+    sb.pend[slot] = static_cast<uint8_t>(pend);
+    if (n_term) sb.n_term[slot] += n_term;
+    dl.todo[slot] = left;
+    if (left) atomicMax(&dl.todo_max[parity], left);
+  }
+  c.store(kSlotWaitEval);
+}
+
+template <class GM>
+__global__ __launch_bounds__(64) void k_sb_big_find_dl_po(EngineParams ep, EngineArrays ar, SbArrays sb, SbDlArrays dl, SbRollArrays ro, uint32_t n,
+                                                          uint32_t L, uint32_t parity) {
+  __shared__ BigScratch<GM> sm;
+  const uint32_t slot = blockIdx.x, lane = threadIdx.x;
+  if (slot == 0 && lane == 0) dl.todo_max[parity ^ 1u] = 0;
+  if (slot >= n) return;
+  uint32_t left = dl.todo[slot];
+  if (sb.status[slot] != 0 || left == 0) {
+    if (lane == 0) sb.pend[slot] = kPendNone;
+    return;
+  }
+  BigSlot<GM> c(ep, ar, sm, slot, lane);
+  c.load();
+  uint32_t pend = kPendNone, n_term = 0;
+  for (uint32_t d = 0; d < L && left > 0; ++d) {
+    --left;
+    typename GM::State leaf;
+    uint32_t term = 0;
+    if (!c.find_leaf(0, leaf, term)) {
+      if (lane == 0) sb.status[slot] = kSbFindFailed;
+      left = 0;
+      break;
+    }
+    if (term == 0) {
+      const uint32_t j = ro.count[slot];
+      c.playout_eval(leaf, sb_rollout_seed(ro.seeds[slot], j));      // (ends with the wavefront's fence: every lane has read j)
+      if (lane == 0) { ro.count[slot] = j + 1; ar.c_evals[slot] += 1; }
+      pend = kPendRollout;
+      break;
+    }
+    ++n_term;
+    c.process_result(0, true, false);
+  }
+  if (lane == 0) {
+    sb.pend[slot] = static_cast<uint8_t>(pend);
+    if (n_term) sb.n_term[slot] += n_term;
+    dl.todo[slot] = left;
+    if (left) atomicMax(&dl.todo_max[parity], left);
+  }
+  c.sync();
+  c.store(kSlotWaitEval);
+}
+
 }  // namespace azmi

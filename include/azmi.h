@@ -388,7 +388,25 @@ int azmi_mcts_query(azmi_mcts* m, uint32_t kind, float temp, uint32_t arg, const
  *            descents left runs those.  Two in-flight leaves on one position both miss the cache and are both evaluated.
  *            Legal before the first reset and after a reset, before anything is searched; (re)allocates the in-flight records
  *            and step-sized row buffers and fails with the byte count when they do not fit.  gumbel_enabled with k > 1 is
- *            AZMI_ERR_INVALID: the batched descent is plain PUCT (mcts.cc:752-784) */
+ *            AZMI_ERR_INVALID: the batched descent is plain PUCT (mcts.cc:752-784)
+ *   set_descents_per_step   l in [1, 256] descents of a tree per step of run / play (1, the default, is everything above
+ *            unchanged: the same launches with the same arguments, nothing read back).  With l > 1 a step of a live tree is the
+ *            per-tree loop of mcts_analysis.py:921-951: up to l x { find_leaf; a terminal leaf, a dumb_eval leaf (RANDOM) or a
+ *            cache hit gets its process_result at once and the loop goes on; the first leaf that needs the net (PLAYOUT: a
+ *            rollout) becomes the tree's ONE row of the step and ends it }, then one evaluator call, the cache insert and the
+ *            back-up of the pending rows as with l == 1.  Tree i makes the same find_leaf / process_result calls in the same order
+ *            as with l == 1 and stays bit for bit the stand-alone azmi_mcts; only the cache's hit / miss counts and eviction state
+ *            may differ.  The j-th rollout of a tree keeps its seed.  Gumbel batches are supported (the K == 1 descent).
+ *            run(visits) / every move of play gives every live tree exactly `visits` descents through a per-tree device counter
+ *            set by one launch: RANDOM enqueues exactly ceil(visits / l) steps and reads nothing; with a net or PLAYOUT the call
+ *            enqueues ceil(visits / l) steps, then repeats { read r = the largest count left (ONE 4-byte word, synchronising
+ *            `stream`); stop at 0; enqueue m more steps }, m = ceil(r / l) behind the first read (the fewest that can finish),
+ *            max(ceil(r / l), twice the previous m) behind every later one, never more than r.  Every step gives every tree that
+ *            owes descents at least one: at most 1 + ceil(log2(visits)) reads, counted by host_reads.  `steps` of stats counts enqueued steps, those with no work left included.  play picks a move only behind
+ *            the read of 0.  Same state rules as set_leaves_per_step.  AZMI_ERR_INVALID before any launch: l > 1 together with
+ *            leaves_per_step > 1 (from either setter), run_to and find_leaves on a batch with l > 1 (the checkpoint launches are
+ *            planned for one descent per step; the step API's caller owns the step).
+ *   host_reads   *out = the 4-byte reads run / play have made for descents_per_step > 1 since creation */
 typedef struct azmi_search azmi_search;
 int azmi_search_create(int game, const azmi_mcts_config* cfg, uint32_t n_trees, int device, azmi_search** out);
 void azmi_search_destroy(azmi_search* s);
@@ -404,6 +422,8 @@ int azmi_search_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, f
 int azmi_search_sync(azmi_search* s);
 int azmi_search_stats(azmi_search* s, uint64_t out[6]);
 int azmi_search_set_leaves_per_step(azmi_search* s, uint32_t k);
+int azmi_search_set_descents_per_step(azmi_search* s, uint32_t l);
+int azmi_search_host_reads(azmi_search* s, uint64_t* out);
 /* ---- moves on a batched search: what the evaluation tools do between two searches of a game they walk (play.py:274-346,
  * mcts_analysis.py:995-1051): pick a move, MCTS::update_root on every tree (mcts.cc:151-173), search the successor with the reused
  * subtree.  The root state of every tree is advanced on the device; tree i stays bit for bit the stand-alone azmi_mcts driven by
