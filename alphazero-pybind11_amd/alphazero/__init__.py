@@ -26,7 +26,7 @@ from .evaluators import dumb_eval, playout_eval_batch, playout_eval
 from .cache import ShardedS3FIFOCache, S3FIFOCache
 from .play_manager import GameData, PlayManager, _f32
 from .drivers import (run_rounds, run_rounds_groups, pipeline_supported, pipeline_supported_groups, run_pipeline, run_pipeline_groups,
-                      _pipe_stats, _PIPE_KEYS, pipeline_log_duplicates, rng_probe, tracy_is_enabled, tracy_frame_mark,
+                      _pipe_stats, _PIPE_KEYS, pipeline_log_duplicates, cache_find_group, cache_insert_locked, rng_probe, tracy_is_enabled, tracy_frame_mark,
                       _tracy_zone_begin, _tracy_zone_end, _tracy_set_thread_name)
 
 

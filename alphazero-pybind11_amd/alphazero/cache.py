@@ -27,17 +27,19 @@ class ShardedS3FIFOCache:
         """Called when the cache is handed to a PlayManager: the engine probes 64-entry shards, the reference's callers pass
         any `shards` (cache_utils.create_sharded_cache defaults to 1).  A cache that has not been used yet is re-created in
         the engine's layout behind the same object (capacity rounded down to a multiple of 64; max_size() keeps reporting
-        the requested size, like the reference's own shard rounding); one that already holds entries cannot be converted."""
+        the requested size, like the reference's own shard rounding; a ghost ring longer than the cache is clamped to it: a
+        64-entry shard keeps at most 64 ghost keys); one that already holds entries cannot be converted."""
         max_size, shards, ghost, device = self._args
-        if max_size // max(1, shards) == 64:
+        if max_size // max(1, shards) == 64 and ghost // max(1, shards) <= 64:      # (a wave shard keeps at most 64 ghost keys)
             return
         st = self._stats()
         if st["hits"] or st["misses"] or st["size"]:
-            raise RuntimeError("this cache has been used with another shard layout; create it with ShardedS3FIFOCache.for_engine "
-                               "before the first use to share it with a PlayManager")
+            raise RuntimeError("this cache has been used with another shard layout (max_size / shards != 64, or ghost_size / shards "
+                               "> 64); create it with ShardedS3FIFOCache.for_engine before the first use to share it with a PlayManager")
         new_shards = max(1, max_size // 64)
         h = C.c_void_p()
-        rc = lib.azmi_cache_create(new_shards * 64, new_shards, max(0, min(ghost, new_shards * 64)), self._np, self._nv, device, C.byref(h))
+        ghost = max(0, min(ghost, new_shards * 64))
+        rc = lib.azmi_cache_create(new_shards * 64, new_shards, ghost, self._np, self._nv, device, C.byref(h))
         if rc != 0:
             raise RuntimeError(lib.azmi_cache_last_error().decode())
         lib.azmi_cache_destroy(self._h)

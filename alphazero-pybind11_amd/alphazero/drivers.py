@@ -103,6 +103,33 @@ def rng_probe(kind, seed, n, param=0.0, reps=1, device=0):
     return out.reshape(reps, n) if k == 1 else out
 
 
+def _cache_check(rc):
+    if rc != 0:
+        raise RuntimeError(lib.azmi_cache_last_error().decode("utf-8", "replace") or f"azmi error {rc}")
+
+
+def cache_find_group(cache, group_lanes, hashes):
+    """azmi_debug_cache_find_group: ShardedS3FIFOCache.find_many with the probe of a `group_lanes`-lane group (8 or 64, the
+    engines' GM::GROUP) -> (hit, policy, value)."""
+    h = np.ascontiguousarray(hashes, np.uint64)
+    hit = np.zeros(len(h), np.uint8)
+    p = np.zeros((len(h), cache._np), np.float32)
+    v = np.zeros((len(h), cache._nv), np.float32)
+    _cache_check(lib.azmi_debug_cache_find_group(cache._h, int(group_lanes), h.ctypes.data, len(h), hit.ctypes.data, p.ctypes.data, v.ctypes.data))
+    return hit.astype(bool), p, v
+
+
+def cache_insert_locked(cache, hashes, policies, values, waves):
+    """azmi_debug_cache_insert_locked: the pipeline's locked insert (one wavefront per entry, `waves` wavefronts in one kernel) of
+    host rows -> the number of entries whose shard lock was not had (0 unless something is wrong)."""
+    h = np.ascontiguousarray(hashes, np.uint64)
+    p = np.ascontiguousarray(policies, np.float32).reshape(len(h), cache._np)
+    v = np.ascontiguousarray(values, np.float32).reshape(len(h), cache._nv)
+    failed = C.c_uint32(0)
+    _cache_check(lib.azmi_debug_cache_insert_locked(cache._h, h.ctypes.data, p.ctypes.data, v.ctypes.data, len(h), int(waves), C.byref(failed)))
+    return int(failed.value)
+
+
 # Tracy stubs — py_wrapper.cc:772-787: must exist even as no-ops
 def tracy_is_enabled():
     return False

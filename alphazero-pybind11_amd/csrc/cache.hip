@@ -46,22 +46,24 @@ __global__ void k_cache_insert_many(CacheView c, const uint64_t* hashes, const f
 
 __global__ __launch_bounds__(256) void k_cache_apply_wave(CacheView c, const uint64_t* keys, const float* policy, const float* value, uint32_t n) {
   __shared__ uint32_t s_sid[kApplyMax];
-  cache_apply_batch(c, keys, policy, value, n, s_sid);
+  cache_apply_batch<true>(c, keys, policy, value, n, s_sid);      // hash 0 is a key here (s3fifo_cache.h has no reserved key)
 }
 
-// 8 lanes per query (the lane-group shape the engine uses)
+// G lanes per query: the lane-group shapes the engines use (GM::GROUP: 8 = the DPP reduction, 64 = the shuffle reduction).  The
+// stand-alone cache probes with 8; azmi_debug_cache_find_group chooses
+template <int G>
 __global__ void k_cache_find_wave(CacheView c, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy, float* value) {
   const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t i = gtid / 8, gl = gtid % 8;
+  const uint32_t i = gtid / G, gl = gtid % G;
   if (i >= n) return;
   uint32_t sh;
-  const int slot = wave_shard_find<8>(c, hashes[i], gl, &sh);
+  const int slot = wave_shard_find<G>(c, hashes[i], gl, &sh);
   if (gl == 0) { wave_shard_find_account(c, hashes[i], sh, slot); hit[i] = slot >= 0; }
   if (slot < 0) return;
   const float* sp = c.policy + (static_cast<size_t>(sh) * kWaveCap + slot) * c.np;
   const float* sv = c.value + (static_cast<size_t>(sh) * kWaveCap + slot) * c.nv;
-  for (uint32_t j = gl; j < c.np; j += 8) policy[static_cast<size_t>(i) * c.np + j] = sp[j];
-  for (uint32_t j = gl; j < c.nv; j += 8) value[static_cast<size_t>(i) * c.nv + j] = sv[j];
+  for (uint32_t j = gl; j < c.np; j += G) policy[static_cast<size_t>(i) * c.np + j] = sp[j];
+  for (uint32_t j = gl; j < c.nv; j += G) value[static_cast<size_t>(i) * c.nv + j] = sv[j];
 }
 
 __global__ void k_cache_find_many(CacheView c, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy, float* value) {
@@ -77,6 +79,47 @@ __global__ void k_cache_find_many(CacheView c, const uint64_t* hashes, uint32_t 
   for (uint32_t j = 0; j < c.np; ++j) policy[static_cast<size_t>(i) * c.np + j] = sp[j];
   for (uint32_t j = 0; j < c.nv; ++j) value[static_cast<size_t>(i) * c.nv + j] = sv[j];
 }
+
+// k_pipe_cache_insert's shape (pipeline.hip) on host-given entries: `waves` wavefronts stride over the n entries, each entry
+// under its shard's insert lock
+__global__ __launch_bounds__(256) void k_debug_insert_locked(CacheView c, uint32_t* locks, const uint64_t* keys, const float* policy,
+                                                             const float* value, uint32_t n, uint32_t waves, uint32_t* failed) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+  if (wave >= waves) return;
+  for (uint32_t i = wave; i < n; i += waves) {
+    const float p = lane < c.np ? policy[static_cast<size_t>(i) * c.np + lane] : 0.0f;
+    const float v = lane < c.nv ? value[static_cast<size_t>(i) * c.nv + lane] : 0.0f;
+    const bool ok = wave_shard_insert_locked<false>(c, locks, keys[i], p, v, lane);
+    if (!ok && lane == 0) atomicAdd(failed, 1u);
+  }
+}
+
+// the finds of one call: host arrays in, host arrays out.  group_lanes = 0: the generic tables, one lane per query
+int find_many(azmi_cache* c, uint32_t group_lanes, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy, float* value) {
+  (void)hipSetDevice(c->device);
+  uint64_t* dh = nullptr; uint8_t* dhit = nullptr; float *dp = nullptr, *dv = nullptr;
+  hipError_t e = hipMalloc(&dh, n * 8ULL);
+  if (e == hipSuccess) e = hipMalloc(&dhit, n);
+  if (e == hipSuccess) e = hipMalloc(&dp, static_cast<size_t>(n) * c->c.np * 4);
+  if (e == hipSuccess) e = hipMalloc(&dv, static_cast<size_t>(n) * c->c.nv * 4);
+  if (e == hipSuccess) e = hipMemcpy(dh, hashes, n * 8ULL, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dp, 0, static_cast<size_t>(n) * c->c.np * 4);
+  if (e == hipSuccess) e = hipMemset(dv, 0, static_cast<size_t>(n) * c->c.nv * 4);
+  if (e == hipSuccess) {
+    const uint32_t blocks = static_cast<uint32_t>((static_cast<uint64_t>(n) * (group_lanes ? group_lanes : 1u) + 255u) / 256u);
+    if (group_lanes == 8u) k_cache_find_wave<8><<<blocks, 256>>>(c->c, dh, n, dhit, dp, dv);
+    else if (group_lanes == 64u) k_cache_find_wave<64><<<blocks, 256>>>(c->c, dh, n, dhit, dp, dv);
+    else k_cache_find_many<<<blocks, 256>>>(c->c, dh, n, dhit, dp, dv);
+    e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(hit, dhit, n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(policy, dp, static_cast<size_t>(n) * c->c.np * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(value, dv, static_cast<size_t>(n) * c->c.nv * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(dh); (void)hipFree(dhit); (void)hipFree(dp); (void)hipFree(dv);
+  return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "cache find: %s", hipGetErrorString(e));
+}
+
 }  // namespace
 
 
@@ -115,7 +158,7 @@ int azmi_cache_insert_many(azmi_cache* c, const uint64_t* hashes, const float* p
   if (e == hipSuccess) e = hipMemcpy(dp, policy, static_cast<size_t>(n) * c->c.np * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dv, value, static_cast<size_t>(n) * c->c.nv * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    if (c->c.cap == kWaveCap) {
+    if (wave_layout(c->c)) {
       for (uint32_t off = 0; off < n && e == hipSuccess; off += kApplyMax) {  // chunks keep batch order
         const uint32_t m = std::min<uint32_t>(kApplyMax, n - off);
         k_cache_apply_wave<<<(m + 3) / 4, 256>>>(c->c, dh + off, dp + static_cast<size_t>(off) * c->c.np, dv + static_cast<size_t>(off) * c->c.nv, m);
@@ -133,25 +176,51 @@ int azmi_cache_insert_many(azmi_cache* c, const uint64_t* hashes, const float* p
 int azmi_cache_find_many(azmi_cache* c, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy, float* value) {
   if (!c || (n && (!hashes || !hit || !policy || !value))) return cfail(AZMI_ERR_INVALID, "null argument");
   if (n == 0) return AZMI_OK;
+  return find_many(c, wave_layout(c->c) ? 8u : 0u, hashes, n, hit, policy, value);
+}
+
+int azmi_debug_cache_find_group(azmi_cache* c, uint32_t group_lanes, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy, float* value) {
+  if (!c || (n && (!hashes || !hit || !policy || !value))) return cfail(AZMI_ERR_INVALID, "azmi_debug_cache_find_group: null argument");
+  if (group_lanes != 8u && group_lanes != 64u)
+    return cfail(AZMI_ERR_INVALID, "azmi_debug_cache_find_group: group_lanes %u is not a lane group of the engines (8 or 64)", group_lanes);
+  if (n == 0) return AZMI_OK;
+  if (!wave_layout(c->c))
+    return cfail(AZMI_ERR_INVALID, "azmi_debug_cache_find_group: not a cache of 64-entry wave shards (max_size / shards = %u, ghost_size / shards = %u)",
+                 c->c.cap, c->c.ghost_cap);
+  return find_many(c, group_lanes, hashes, n, hit, policy, value);
+}
+
+int azmi_debug_cache_insert_locked(azmi_cache* c, const uint64_t* hashes, const float* policy, const float* value, uint32_t n, uint32_t waves,
+                                   uint32_t* failed_out) {
+  if (!c || !failed_out || (n && (!hashes || !policy || !value))) return cfail(AZMI_ERR_INVALID, "azmi_debug_cache_insert_locked: null argument");
+  if (waves == 0u || waves > 8192u) return cfail(AZMI_ERR_INVALID, "azmi_debug_cache_insert_locked: waves must be 1 .. 8192");
+  *failed_out = 0;
+  if (n == 0) return AZMI_OK;
+  if (!wave_layout(c->c))
+    return cfail(AZMI_ERR_INVALID, "azmi_debug_cache_insert_locked: not a cache of 64-entry wave shards (max_size / shards = %u, ghost_size / shards = %u)",
+                 c->c.cap, c->c.ghost_cap);
+  if (c->c.np > 64u || c->c.nv > 64u)
+    return cfail(AZMI_ERR_INVALID, "azmi_debug_cache_insert_locked: a lane carries one entry of each row: num_policy and num_value must be <= 64 (%u, %u)",
+                 c->c.np, c->c.nv);
   (void)hipSetDevice(c->device);
-  uint64_t* dh = nullptr; uint8_t* dhit = nullptr; float *dp = nullptr, *dv = nullptr;
+  const size_t np = c->c.np, nv = c->c.nv;
+  uint64_t* dh = nullptr; float *dp = nullptr, *dv = nullptr; uint32_t* dl = nullptr;      // dl: [shards] lock words, then the failure count
   hipError_t e = hipMalloc(&dh, n * 8ULL);
-  if (e == hipSuccess) e = hipMalloc(&dhit, n);
-  if (e == hipSuccess) e = hipMalloc(&dp, static_cast<size_t>(n) * c->c.np * 4);
-  if (e == hipSuccess) e = hipMalloc(&dv, static_cast<size_t>(n) * c->c.nv * 4);
+  if (e == hipSuccess) e = hipMalloc(&dp, n * np * 4);
+  if (e == hipSuccess) e = hipMalloc(&dv, n * nv * 4);
+  if (e == hipSuccess) e = hipMalloc(&dl, (static_cast<size_t>(c->c.shards) + 1) * 4);
   if (e == hipSuccess) e = hipMemcpy(dh, hashes, n * 8ULL, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dp, 0, static_cast<size_t>(n) * c->c.np * 4);
-  if (e == hipSuccess) e = hipMemset(dv, 0, static_cast<size_t>(n) * c->c.nv * 4);
+  if (e == hipSuccess) e = hipMemcpy(dp, policy, n * np * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv, value, n * nv * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dl, 0, (static_cast<size_t>(c->c.shards) + 1) * 4);
   if (e == hipSuccess) {
-    if (c->c.cap == kWaveCap) k_cache_find_wave<<<(n * 8 + 255) / 256, 256>>>(c->c, dh, n, dhit, dp, dv);
-    else k_cache_find_many<<<(n + 255) / 256, 256>>>(c->c, dh, n, dhit, dp, dv);
+    if (waves == 1u) k_debug_insert_locked<<<1, 64>>>(c->c, dl, dh, dp, dv, n, waves, dl + c->c.shards);
+    else k_debug_insert_locked<<<(waves + 3) / 4, 256>>>(c->c, dl, dh, dp, dv, n, waves, dl + c->c.shards);
     e = hipDeviceSynchronize();
   }
-  if (e == hipSuccess) e = hipMemcpy(hit, dhit, n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(policy, dp, static_cast<size_t>(n) * c->c.np * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(value, dv, static_cast<size_t>(n) * c->c.nv * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(dh); (void)hipFree(dhit); (void)hipFree(dp); (void)hipFree(dv);
-  return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "cache find: %s", hipGetErrorString(e));
+  if (e == hipSuccess) e = hipMemcpy(failed_out, dl + c->c.shards, 4, hipMemcpyDeviceToHost);
+  (void)hipFree(dh); (void)hipFree(dp); (void)hipFree(dv); (void)hipFree(dl);
+  return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "azmi_debug_cache_insert_locked: %s", hipGetErrorString(e));
 }
 
 int azmi_cache_stats(azmi_cache* c, uint64_t out[6]) {

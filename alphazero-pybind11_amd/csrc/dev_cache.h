@@ -5,6 +5,9 @@
 // indices, a Ghost ring of evicted keys, a 2-bit frequency per slot (s3fifo_cache.h:41-59, 82-150).
 // shard = key % shards, exactly as the reference.  absl's flat_hash_{map,set} become two
 // open-addressing tables per shard (linear probing, backward-shift deletion, key 0 = empty).
+// Key 0 therefore cannot be stored as itself: cache_key() maps hash 0 onto 0x9E3779B97F4A7C15, while the shard is still taken
+// from the hash (0 % shards).  Hash 0 and hash 0x9E3779B97F4A7C15 share ONE entry when they fall into the same shard (always with
+// shards == 1); the reference keeps them apart.  Known, accepted (one position key in 2^64), and not tested.
 //
 // Concurrency model on the GPU:
 //   * find()  — many lane-groups probe concurrently (read-only on the tables; the frequency bump
@@ -187,11 +190,19 @@ struct ShardCtx {
 // in the set" bit — so S3FIFOCache::find / insert_locked / evict_one / ghost_add (s3fifo_cache.h:41-194)
 // run as v_readlane / v_writelane / ballot sequences instead of dependent HBM accesses.  The hash map
 // and the ghost set become ballots over the 64 lanes.  Semantics are exactly the generic path's
-// (same rings, same counters); parity with the oracle is tested at shards = max_size / 64.
+// (same rings, same counters).  A lane holds ONE ghost-ring entry, so the layout needs ghost_cap <= 64 as well
+// (wave_layout below): a cache with 64-entry shards and a longer ghost ring runs on the generic kernels and is refused by the
+// engines.  Parity with the oracle is tested op by op (tests/test_gpu_cache.py at shards = max_size / 64 with batches of up
+// to 12 keys; tests/test_gpu_cache_edges.py for cache_apply_batch at 1 .. 2 * kApplyMax + 1 elements with chosen shard
+// patterns and duplicates, rows of 1 .. 2662 floats, key words that share or lack a 32-bit half, hash 0, repeated keys
+// inside one find batch, ghost rings longer than a shard, wave_shard_find<8> and <64>, and wave_shard_insert_locked<false>
+// serial and contended).
 // =====================================================================================================
 namespace azmi {
 
 constexpr uint32_t kWaveCap = 64;
+// does this cache have the wave-resident layout (the one the engines probe)?
+__host__ __device__ __forceinline__ bool wave_layout(const CacheView& c) { return c.cap == kWaveCap && c.ghost_cap <= kWaveCap; }
 
 __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) { return __builtin_amdgcn_readlane(v, lane); }
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -433,7 +444,8 @@ __device__ inline void wave_shard_find_account(const CacheView& c, uint64_t hash
 // Batch insert for wave shards.  One wavefront per batch element; the wave whose element is the FIRST
 // of its shard in the batch becomes that shard's owner and applies all of the shard's elements in
 // batch order (ShardedS3FIFOCache::insert_many, s3fifo_cache.h:259-286); every other wave exits.
-// `keys[j] == 0` marks an element that is not to be inserted.  Rows j of `policy` / `value`
+// `keys[j] == 0` marks an element that is not to be inserted (the engines' convention; ZERO_IS_KEY = true, the stand-alone
+// cache: hash 0 is a key like any other, as in the reference).  Rows j of `policy` / `value`
 // (row strides np / nv floats) are the payload.  Launch: <<<ceil(n / 4), 256>>>, n <= kApplyMax.
 constexpr uint32_t kApplyMax = 8192;
 // dst[0..n) = src[0..n) by one wavefront with U loads in flight per lane: a plain `dst[e] = src[e]` loop waits for every
@@ -449,6 +461,7 @@ __device__ __forceinline__ void wave_copy_row(float* __restrict__ dst, const flo
     for (uint32_t u = 0; u < U; ++u) { const uint32_t e = e0 + u * 64 + lane; if (e < n) dst[e] = t[u]; }
   }
 }
+template <bool ZERO_IS_KEY = false>
 __device__ __forceinline__ void cache_apply_batch(const CacheView& c, const uint64_t* keys, const float* policy,
                                                    const float* value, uint32_t n, uint32_t* s_sid,
                                                    const uint8_t* groups = nullptr, uint32_t group = 0) {
@@ -462,8 +475,9 @@ __device__ __forceinline__ void cache_apply_batch(const CacheView& c, const uint
   const float own_p = (i < n && own_rows && lane < c.np) ? policy[static_cast<size_t>(i) * c.np + lane] : 0.0f;
   const float own_v = (i < n && own_rows && lane < c.nv) ? value[static_cast<size_t>(i) * c.nv + lane] : 0.0f;
   for (uint32_t j = tid; j < n; j += blockDim.x) {
-    const uint64_t k = (groups && groups[j] != group) ? 0 : keys[j];   // elements of another model group are not ours
-    s_sid[j] = k ? static_cast<uint32_t>(k % c.shards) : 0xFFFFFFFFu;
+    const bool ours = !(groups && groups[j] != group);                 // elements of another model group are not ours
+    const uint64_t k = keys[j];
+    s_sid[j] = (ours && (ZERO_IS_KEY || k)) ? static_cast<uint32_t>(k % c.shards) : 0xFFFFFFFFu;
   }
   __syncthreads();
   if (i >= n) return;

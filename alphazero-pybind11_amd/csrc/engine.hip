@@ -516,6 +516,11 @@ int pm_create_impl(int game, const azmi_play_params* params, const azmi_engine_o
         return azmi_host_fail(AZMI_ERR_INVALID, "caches[%u]: the engine probes 64-entry shards; create the cache with shards = max_size / 64 "
                     "(ShardedS3FIFOCache.for_engine)", g);
       }
+      if (!wave_layout(c->c)) {      // a lane of a wave shard holds one ghost-ring entry (dev_cache.h)
+        delete pm;
+        return azmi_host_fail(AZMI_ERR_INVALID, "caches[%u]: ghost_size / shards = %u, but a 64-entry wave shard keeps at most 64 ghost keys; create the "
+                    "cache with ghost_size <= max_size (ShardedS3FIFOCache.for_engine)", g, c->c.ghost_cap);
+      }
     }
   }
   ep.cache_on = use_ext ? any_ext : params->max_cache_size > 0;

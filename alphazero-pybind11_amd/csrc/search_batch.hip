@@ -249,6 +249,9 @@ int search_args(azmi_search* s, const char* what, int eval_type, azmi_net* net, 
     if (cache->c.cap != kWaveCap)
       return SB_FAIL(AZMI_ERR_INVALID, "cache: the engine probes 64-entry shards; create the cache with shards = max_size / 64 "
                      "(ShardedS3FIFOCache.for_engine)");
+    if (!wave_layout(cache->c))      // a lane of a wave shard holds one ghost-ring entry (dev_cache.h)
+      return SB_FAIL(AZMI_ERR_INVALID, "cache: ghost_size / shards = %u, but a 64-entry wave shard keeps at most 64 ghost keys; create the cache "
+                     "with ghost_size <= max_size (ShardedS3FIFOCache.for_engine)", cache->c.ghost_cap);
     out->ep.cache_on = 1; out->ep.num_groups = 1;
     out->ar.cache = cache->c; out->ar.cache_keys = s->d_keys;
   }

@@ -661,6 +661,17 @@ int azmi_debug_pipe_log_dupes(azmi_pm* pm, uint64_t* out);
 int azmi_debug_group_select(int device, uint32_t rows, const uint32_t* k8, const uint32_t* n64, const float* q64, const float* p64,
                             const float* v_parent8, const uint32_t* n_parent8, const float* fpu8, const float* cpuct8, const uint64_t* pred,
                             float* sum64, uint32_t* best64, uint32_t* all64);
+/* diagnostics: azmi_cache_find_many on a cache of 64-entry wave shards, probing with wave_shard_find<group_lanes> - the lane groups the
+ * engines probe with (GM::GROUP: 8 and 64); the stand-alone call always uses 8.  Same accounting, same outputs.  Other values of
+ * group_lanes and caches in another layout are errors (azmi_cache_last_error).  tests/test_gpu_cache_edges.py */
+int azmi_debug_cache_find_group(azmi_cache* cache, uint32_t group_lanes, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy,
+                                float* value);
+/* diagnostics: the pipeline's cache insert (one wavefront per entry under the shard's insert lock, wave_shard_insert_locked) on host
+ * arrays: ONE kernel in which `waves` wavefronts (1 .. 8192) stride over the n entries, with a zeroed lock word per shard allocated
+ * for the call.  waves = 1 inserts in batch order.  *failed_out = the entries whose lock was not had (0 unless something is wrong).
+ * Needs 64-entry wave shards and num_policy, num_value <= 64 (azmi_cache_last_error otherwise). */
+int azmi_debug_cache_insert_locked(azmi_cache* cache, const uint64_t* hashes, const float* policy, const float* value, uint32_t n,
+                                   uint32_t waves, uint32_t* failed_out);
 /* 1 when azmi_run_pipeline can drive this engine with this net (net may be NULL for an engine whose seats all use
  * EvalType::RANDOM: the tree kernel alone), 0 otherwise (then azmi_run_rounds is the driver) */
 int azmi_pipeline_supported(azmi_pm* pm, azmi_net* net);
