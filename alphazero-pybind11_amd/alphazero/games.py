@@ -672,17 +672,43 @@ def hash_game_state(gs):
     return int(gs._state()["key"][0])
 
 
-def game_replay(game_cls, moves, device=0):
-    """Batched rules replay on the device (azmi_game_replay): moves [n, len] int32, -1 padded."""
+def _init_rows(init, n):
+    """start images of game_replay as one [n, stride] uint8 array: a list of bytes is zero-padded to the longest image"""
+    if isinstance(init, np.ndarray):
+        rows = np.ascontiguousarray(init, dtype=np.uint8)
+        if rows.ndim != 2:
+            raise RuntimeError(f"game_replay: init must be a list of bytes or a [n, stride] uint8 array, got shape {rows.shape}")
+    else:
+        images = [bytes(b) for b in init]
+        rows = np.zeros((len(images), max((len(b) for b in images), default=0)), np.uint8)
+        for i, b in enumerate(images):
+            rows[i, :len(b)] = np.frombuffer(b, np.uint8)
+    if rows.shape[0] != n:
+        raise RuntimeError(f"game_replay: {rows.shape[0]} start positions for {n} move rows")
+    return rows
+
+
+def game_replay(game_cls, moves, init=None, device=0):
+    """Batched rules replay on the device: moves [n, len] int32, -1 padded.  `init` = one start position per row
+    (azmi_game_replay_from) as a list of bytes or a [n, stride] uint8 array of zero-padded rows: Connect4GS.to_bytes() images
+    (89 bytes), _TaflBoardGS._image / to_bytes images; None = every row starts from the game's initial position
+    (azmi_game_replay).  Moves are checked: a row with an illegal move gets status -1 and stops before it."""
     moves = np.ascontiguousarray(moves, dtype=np.int32)
     n, ln = moves.shape
+    rows = None if init is None else _init_rows(init, n)
     P, M, chw = game_cls._info()
     out = dict(
         valid=np.zeros((n, M), np.uint8), scores=np.zeros((n, P + 1), np.float32),
         canonical=np.zeros((n,) + tuple(chw), np.float32), player=np.zeros(n, np.uint32),
         turn=np.zeros(n, np.uint32), key=np.zeros(n, np.uint64), status=np.zeros(n, np.int32),
     )
-    check(lib.azmi_game_replay(game_cls.GAME_ID, device, moves.ctypes.data, n, ln, out["valid"].ctypes.data,
-                               out["scores"].ctypes.data, out["canonical"].ctypes.data, out["player"].ctypes.data,
-                               out["turn"].ctypes.data, out["key"].ctypes.data, out["status"].ctypes.data))
+    if rows is None:
+        check(lib.azmi_game_replay(game_cls.GAME_ID, device, moves.ctypes.data, n, ln, out["valid"].ctypes.data,
+                                   out["scores"].ctypes.data, out["canonical"].ctypes.data, out["player"].ctypes.data,
+                                   out["turn"].ctypes.data, out["key"].ctypes.data, out["status"].ctypes.data))
+    else:
+        check(lib.azmi_game_replay_from(game_cls.GAME_ID, device, rows.ctypes.data, rows.shape[1], moves.ctypes.data, n, ln,
+                                        out["valid"].ctypes.data, out["scores"].ctypes.data, out["canonical"].ctypes.data,
+                                        out["player"].ctypes.data, out["turn"].ctypes.data, out["key"].ctypes.data,
+                                        out["status"].ctypes.data))
     return out

@@ -86,6 +86,7 @@ void* orc_c4_from_board(const int8_t* board, int8_t player, int32_t turn) {
 void* orc_tafl_from_board(int game_id, const int8_t* board, int8_t player, uint32_t turn, uint32_t max_turns) {
   try {
     switch (game_id) {
+      case 1: return new Tawlbwrdd(board, player, static_cast<uint16_t>(turn), static_cast<uint16_t>(max_turns));
       case 2: return new Brandubh(board, player, static_cast<uint16_t>(turn), static_cast<uint16_t>(max_turns));
       case 3: return new OpenTafl(board, player, static_cast<uint16_t>(turn), static_cast<uint16_t>(max_turns));
       default: return nullptr;

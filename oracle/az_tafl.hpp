@@ -42,6 +42,11 @@ struct Tawlbwrdd final : Game {
                                     {4,0},{5,0},{6,0},{4,1},{5,1},{6,1},{4,9},{5,9},{6,9},{4,10},{5,10},{6,10}};
     for (auto& a : atks) at(ATK, a[0], a[1]) = 1;
   }
+  // a given board with an empty repetition map and count 1 (the full constructor, tawlbwrdd_gs.h:136-148, called the way
+  // the Brandubh / OpenTafl test helper MakeGS calls theirs)
+  Tawlbwrdd(const int8_t* b, int8_t p, uint16_t t, uint16_t mt) : turn(t), max_turns(mt), player(p) {
+    std::memcpy(board.data(), b, board.size());
+  }
 
   std::unique_ptr<Game> copy() const override { return std::make_unique<Tawlbwrdd>(*this); }
   uint8_t current_player() const override { return static_cast<uint8_t>(player); }
