@@ -12,6 +12,9 @@
 // RANDOM, cache hit): the *_dl kernels; a search then needs fewer steps than visits, and reads one word back to know how many.
 // azmi_search_run_to searches every tree to its own root_n target and snapshots the read-outs at checkpoints on the way
 // (mcts_analysis.py:884-972): the steps above, plus the checkpoint kernel at the steps the host knows something can happen at.
+// azmi_search_set_capture / capture_roots / captured, azmi_pool_unique and azmi_search_net_metrics are frozen_eval.py's capture
+// loop and metric extraction (csrc/search_pool_kernels.h): root records before every move's search, first-occurrence dedup of
+// keys, the net's raw forward of the roots against their searches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +26,7 @@
 #include "cache_host.h"
 #include "engine_host.h"
 #include "search_batch_kernels.h"
+#include "search_pool_kernels.h"
 
 using namespace azmi;
 
@@ -73,6 +77,12 @@ struct azmi_search {
   SbDlArrays dl{};                    // todo [N], todo_max [2]
   uint32_t dl_parity = 0;             // parity of the next step of the running search: the todo_max word it raises
   uint64_t host_reads = 0;            // 4-byte reads of todo_max since creation
+  // root capture (azmi_search_set_capture): allocated by the first call that turns it on
+  bool capture = false;
+  SbCaptureArrays cp{};
+  // net versus search (azmi_search_net_metrics): allocated by the first call
+  double* d_nm_out = nullptr;         // [N, 3]
+  uint8_t* d_nm_valid = nullptr;      // [N]
 };
 
 namespace {
@@ -138,6 +148,8 @@ void launch_todo_set(azmi_search* s, uint32_t visits, hipStream_t st);
 void launch_find_dl(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, uint32_t eval_random, uint32_t root_noise,
                     hipStream_t st);
 void launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, hipStream_t st);
+// root capture (also at the end of the file): the record of every live tree's root at its current ply
+void launch_capture(azmi_search* s, hipStream_t st);
 
 // ---- K > 1: the same steps over K descents of every tree; the launch counts do not depend on N or K ---------------------------
 EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine arrays with the step-sized [K * N] row buffers in place
@@ -570,6 +582,7 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
     if (e == hipSuccess) e = hipMemsetAsync(s->pl.move, 0xFF, static_cast<size_t>(n) * 4, st);      // (-1: nothing picked yet)
     if (e == hipSuccess) e = hipMemcpyAsync(s->ro.seeds, roll.data(), static_cast<size_t>(n) * 8, hipMemcpyHostToDevice, st);      // (st is synchronised below)
     if (e == hipSuccess) e = hipMemsetAsync(s->ro.count, 0, static_cast<size_t>(n) * 4, st);
+    if (e == hipSuccess && s->cp.len) e = hipMemsetAsync(s->cp.len, 0, static_cast<size_t>(n) * 4, st);      // the captured roots were the old positions'
     if (e == hipSuccess && pm->ep.half_nodes) e = hipMemsetAsync(pm->ar.compact_flag, 0, static_cast<size_t>(n) * pm->gi.P * 4, st);
     if (e == hipSuccess && s->k_leaves > 1)     // the in-flight mark of every root (node 0 of its tree); every other node gets its mark cleared when it is created
       e = hipMemset2DAsync(s->wu.wu.nif, static_cast<size_t>(pm->gi.P) * pm->ep.cap * 4, 0, 4, n, st);
@@ -762,6 +775,7 @@ int azmi_search_play_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cac
   hipStream_t st = pm->pick(stream);
   const uint32_t rn = root_noise ? 1u : 0u, rt = s->root_temp != 1.0f ? 1u : 0u;
   for (uint32_t m = 0; m < max_moves; ++m) {
+    if (s->capture) launch_capture(s, st);
     rc = enqueue_search(s, a, visits, rn, st); if (rc) return rc;
     launch_pick(s, temp, st);
     launch_update_root(s, s->pl.move, st);
@@ -1001,3 +1015,127 @@ void launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const Engine
 }
 
 }  // namespace
+
+// ---- frozen-set capture, first-occurrence dedup, net versus search: the kernels of search_pool_kernels.h, behind everything else ---
+namespace {
+
+void launch_capture(azmi_search* s, hipStream_t st) {
+  SB_LAUNCH(s, st, k_sb_capture, k_sb_big_capture, s->pm->ep, s->pm->ar, s->sb, s->pl, s->cp, s->n);
+}
+
+}  // namespace
+
+extern "C" {
+
+int azmi_search_set_capture(azmi_search* s, int on) {
+  if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
+  if (on && !s->cp.key) {
+    azmi_pm* pm = s->pm;
+    SB_TRY(hipSetDevice(pm->device));
+    const size_t rows = static_cast<size_t>(s->n) * s->pl.log_cap;
+    SbCaptureArrays cp{};
+    int rc = pm->alloc(cp.key, rows, true);
+    if (rc == AZMI_OK) rc = pm->alloc(cp.player, rows, true);
+    if (rc == AZMI_OK) rc = pm->alloc(cp.variant, rows, true);
+    if (rc == AZMI_OK) rc = pm->alloc(cp.len, s->n, true);
+    if (rc != AZMI_OK) return rc;      // (what was allocated stays with the engine and is freed with it)
+    s->cp = cp;
+  }
+  s->capture = on != 0;
+  return AZMI_OK;
+}
+
+int azmi_search_capture_roots(azmi_search* s, void* stream) {
+  int rc = begin_move(s, "capture_roots"); if (rc) return rc;
+  if (!s->capture) return SB_FAIL(AZMI_ERR_STATE, "capture_roots: capture is off; call set_capture(true) first");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  launch_capture(s, pm->pick(stream));
+  SB_TRY(hipGetLastError());
+  return AZMI_OK;
+}
+
+int azmi_search_captured(azmi_search* s, uint64_t* key, uint8_t* player, int8_t* variant, uint32_t* len) {
+  int rc = begin_read(s, "captured"); if (rc) return rc;
+  if (!s->cp.key) return SB_FAIL(AZMI_ERR_STATE, "captured: capture was never on for this batch; call set_capture(true) before playing");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  rc = check_device(s, pm->last); if (rc) return rc;      // (synchronises)
+  const size_t rows = static_cast<size_t>(s->n) * s->pl.log_cap;
+  if (key) SB_TRY(hipMemcpy(key, s->cp.key, rows * 8, hipMemcpyDeviceToHost));
+  if (player) SB_TRY(hipMemcpy(player, s->cp.player, rows, hipMemcpyDeviceToHost));
+  if (variant) SB_TRY(hipMemcpy(variant, s->cp.variant, rows, hipMemcpyDeviceToHost));
+  if (len) SB_TRY(hipMemcpy(len, s->cp.len, static_cast<size_t>(s->n) * 4, hipMemcpyDeviceToHost));
+  return AZMI_OK;
+}
+
+int azmi_search_net_metrics(azmi_search* s, azmi_net* net, double* out, float* raw_v, float* raw_pi, uint8_t* valid, void* stream) {
+  int rc = begin_move(s, "net_vs_search"); if (rc) return rc;
+  if (!net) return SB_FAIL(AZMI_ERR_INVALID, "net_vs_search: needs a net");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  if (!s->d_nm_out) {
+    rc = pm->alloc(s->d_nm_valid, s->n, true); if (rc) return rc;
+    rc = pm->alloc(s->d_nm_out, static_cast<size_t>(s->n) * 3, true); if (rc) return rc;
+  }
+  hipStream_t st = pm->pick(stream);
+  const size_t N = s->n, V = pm->gi.P + 1, M = pm->gi.M;
+  // the step API's staging buffers are free (no step is pending): the roots' planes, the net's raw rows
+  SB_LAUNCH(s, st, k_sb_root_canon, k_sb_big_root_canon, pm->ep, pm->ar, s->sb, s->n, s->d_batch, s->d_nm_valid);
+  rc = azmi_net_forward(net, s->d_batch, s->d_vrows, s->d_pirows, s->n, st);
+  if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
+  s->net_calls += 1;
+  SB_LAUNCH(s, st, k_sb_net_metrics, k_sb_big_net_metrics, pm->ep, pm->ar, s->n, s->d_nm_valid, s->d_vrows, s->d_pirows, s->d_nm_out, s->d_qf,
+            s->vec_f, s->d_qu, s->vec_u);
+  SB_TRY(hipGetLastError());
+  if (out) SB_TRY(hipMemcpyAsync(out, s->d_nm_out, N * 3 * 8, hipMemcpyDeviceToHost, st));
+  if (raw_v) SB_TRY(hipMemcpyAsync(raw_v, s->d_vrows, N * V * 4, hipMemcpyDeviceToHost, st));
+  if (raw_pi) SB_TRY(hipMemcpyAsync(raw_pi, s->d_pirows, N * M * 4, hipMemcpyDeviceToHost, st));
+  if (valid) SB_TRY(hipMemcpyAsync(valid, s->d_nm_valid, N, hipMemcpyDeviceToHost, st));
+  return check_device(s, st);      // the one synchronisation
+}
+
+int azmi_pool_unique(const uint64_t* keys, const uint8_t* valid, uint32_t n, uint32_t* first_index_out, uint32_t* n_unique, uint32_t* n_duplicates,
+                     int device, void* stream) {
+  if (n > kPoolMaxRecords)
+    return SB_FAIL(AZMI_ERR_INVALID, "azmi_pool_unique: n = %u records: the table takes a power of two of at least 2 n slots indexed by 32 bits, "
+                   "at most %u records", n, kPoolMaxRecords);
+  if (!n_unique || !n_duplicates || (n && (!keys || !first_index_out))) return SB_FAIL(AZMI_ERR_INVALID, "azmi_pool_unique: null argument");
+  *n_unique = 0; *n_duplicates = 0;
+  if (n == 0) return AZMI_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SB_FAIL(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  if (device < 0 || device >= ndev) return SB_FAIL(AZMI_ERR_INVALID, "device %d out of range", device);
+  SB_TRY(hipSetDevice(device));
+  hipStream_t st = stream == AZMI_STREAM_ENGINE ? nullptr : static_cast<hipStream_t>(stream);
+  uint32_t slots = 64;
+  while (slots < 2u * n) slots <<= 1;
+  DevTemps tmp;
+  uint64_t* d_keys = nullptr; uint8_t* d_valid = nullptr; uint32_t *d_owner = nullptr, *d_first = nullptr, *d_slot_of = nullptr, *d_out = nullptr, *d_counts = nullptr;
+  std::vector<uint8_t> all;
+  if (!valid) { all.assign(n, 1); valid = all.data(); }
+  AZMI_HIP_TRY_NODEV(tmp.upload_async(d_keys, keys, n, st));
+  hipError_t e = tmp.upload_async(d_valid, valid, n, st);
+  if (e == hipSuccess) e = tmp.alloc(d_owner, slots);
+  if (e == hipSuccess) e = tmp.alloc(d_first, slots);
+  if (e == hipSuccess) e = tmp.alloc(d_slot_of, n);
+  if (e == hipSuccess) e = tmp.alloc(d_out, n);
+  if (e == hipSuccess) e = tmp.alloc(d_counts, 2);
+  if (e == hipSuccess) e = hipMemsetAsync(d_owner, 0xFF, static_cast<size_t>(slots) * 4, st);      // kPoolEmpty
+  if (e == hipSuccess) e = hipMemsetAsync(d_first, 0xFF, static_cast<size_t>(slots) * 4, st);
+  if (e == hipSuccess) {
+    k_pool_claim<<<(n + 255u) / 256u, 256, 0, st>>>(d_keys, d_valid, n, slots - 1u, d_owner, d_first, d_slot_of);
+    k_pool_compact<<<1, 1024, 0, st>>>(d_valid, n, d_first, d_slot_of, d_out, d_counts);
+    e = hipGetLastError();
+  }
+  uint32_t counts[2] = {0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(first_index_out, d_out, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);      // always: what was queued reads the buffers tmp is about to free
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return SB_FAIL(e == hipErrorOutOfMemory ? AZMI_ERR_OOM : AZMI_ERR_NO_DEVICE, "azmi_pool_unique: %s", hipGetErrorString(e));
+  *n_unique = counts[0]; *n_duplicates = counts[1];
+  return AZMI_OK;
+}
+
+}  // extern "C"

@@ -518,6 +518,35 @@ int azmi_search_run_to(azmi_search* s, int eval_type, azmi_net* net, azmi_cache*
                        uint32_t n_checkpoints, float temp, int pruned, int root_noise_enabled, void* stream);
 int azmi_search_checkpoints(azmi_search* s, uint32_t* taken_mask, uint32_t* root_n, uint32_t* counts, float* probs, float* root_values,
                             float* root_q);
+/* ---- a frozen evaluation set on the device: the two parts of frozen_eval.py around its search loop.  _burst_capture_one_variant
+ * (frozen_eval.py:330-413) plays whole games and keeps every position it has not seen yet; the metric extraction
+ * (frozen_eval.py:573-575, 649-672) compares every searched root with one raw forward of the net.
+ *   set_capture   on != 0: every play_eval move records the root of every live tree (status == 0) BEFORE that move's search, one
+ *                 launch per move: at [tree][ply], ply = the tree's move-log length, the engine key of the root state (what
+ *                 azmi_game_replay returns as `key`), the player to move and the variant (-1 except StarGambit).  Capturing a ply
+ *                 twice stores the same values.  The arrays ([n_trees, max_turns + 8] each) are allocated by the first call that
+ *                 turns capture on; with capture off nothing is allocated or launched.  reset clears the captured lengths.
+ *   capture_roots the same launch for a caller that walks run / pick_moves / update_roots itself.  AZMI_ERR_STATE with capture off.
+ *   captured      the records into HOST buffers, any of them NULL: key / player / variant [n_trees, max_turns + 8], len [n_trees]
+ *                 (entries at ply >= len[tree] are unspecified).  Synchronises.  AZMI_ERR_STATE if capture was never on.
+ *   net_metrics   for every tree that is live and whose root is not terminal: the net's raw (v, pi) of the root's canonical planes
+ *                 and, in float64, out[tree] = { KL(counts / total || raw_pi + 1e-10), mean |raw_v - root_value|, 1.0 if the
+ *                 arg-maxes of counts and raw_pi agree (first index wins) } - counts / total is uniform 1 / M for a root without
+ *                 visits.  Three launches (root planes, the net over all n_trees rows, the comparison) and one synchronisation.
+ *                 HOST buffers, any of them NULL: out [n_trees, 3] f64, raw_v [n_trees, P + 1], raw_pi [n_trees, M], valid
+ *                 [n_trees] u8.  A tree that takes no part has valid = 0 and NaN in every row.  AZMI_ERR_STATE while a find_leaves
+ *                 step is pending.
+ * azmi_pool_unique is the `seen_keys` set of the capture loop as one call on HOST arrays: of the n records with valid[i] != 0
+ * (valid NULL = all), first_index_out[0 .. *n_unique) are, ascending, the indices i for which no valid j < i has keys[j] ==
+ * keys[i]; *n_duplicates = the valid records left out.  Every 64-bit value is a key, 0 included.  The result does not depend on
+ * scheduling.  n == 0 is legal and touches no device; n > 2^30 is AZMI_ERR_INVALID (the table of at least 2 n slots is indexed
+ * by 32 bits).  `stream`: a HIP stream or NULL; the call synchronises it. */
+int azmi_search_set_capture(azmi_search* s, int on);
+int azmi_search_capture_roots(azmi_search* s, void* stream);
+int azmi_search_captured(azmi_search* s, uint64_t* key, uint8_t* player, int8_t* variant, uint32_t* len);
+int azmi_search_net_metrics(azmi_search* s, azmi_net* net, double* out, float* raw_v, float* raw_pi, uint8_t* valid, void* stream);
+int azmi_pool_unique(const uint64_t* keys, const uint8_t* valid, uint32_t n, uint32_t* first_index_out, uint32_t* n_unique,
+                     uint32_t* n_duplicates, int device, void* stream);
 
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
  *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------
