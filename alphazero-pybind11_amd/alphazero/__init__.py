@@ -10,7 +10,7 @@ reference lacks (`PlayManager.round`, `io_tensors`).
 Put the directory that contains this package on sys.path:
     sys.path.insert(0, "<repo>/alphazero-pybind11_amd"); import alphazero
 
-This file only re-exports; the code lives in the sibling modules (params, games, mcts, search_batch, evaluators, cache,
+This file only re-exports; the code lives in the sibling modules (params, games, mcts, search_batch, opening_tree, evaluators, cache,
 play_manager, drivers), whose imports follow that order and never form a cycle.
 """
 from . import _capi
@@ -22,6 +22,7 @@ from .games import (GameState, Connect4GS, _TaflBoardGS, TawlbwrddGS, BrandubhGS
                     _c4_from_bytes, _tafl_from_bytes, _sg_from_bytes, hash_game_state, game_replay, symmetries_batch, tafl_symmetries)
 from .mcts import MCTS, Query, _ENGINE_STREAM
 from .search_batch import MCTSBatch, pool_unique
+from .opening_tree import build_opening_tree, OpeningTree, OpeningNode, temperature_at_depth, node_seed
 from .evaluators import dumb_eval, playout_eval_batch, playout_eval
 from .cache import ShardedS3FIFOCache, S3FIFOCache
 from .play_manager import GameData, PlayManager, _f32

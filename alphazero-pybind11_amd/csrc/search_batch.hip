@@ -15,9 +15,13 @@
 // azmi_search_set_capture / capture_roots / captured, azmi_pool_unique and azmi_search_net_metrics are frozen_eval.py's capture
 // loop and metric extraction (csrc/search_pool_kernels.h): root records before every move's search, first-occurrence dedup of
 // keys, the net's raw forward of the roots against their searches.
+// azmi_search_expand / azmi_search_frontier are the step between two levels of opening_analysis.py's build_tree
+// (csrc/search_frontier_kernels.h): the sampling distribution of every searched root, the moves kept by reach probability and the
+// rules applied to every kept child, three launches whatever N is.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -27,6 +31,7 @@
 #include "engine_host.h"
 #include "search_batch_kernels.h"
 #include "search_pool_kernels.h"
+#include "search_frontier_kernels.h"
 
 using namespace azmi;
 
@@ -83,6 +88,14 @@ struct azmi_search {
   // net versus search (azmi_search_net_metrics): allocated by the first call
   double* d_nm_out = nullptr;         // [N, 3]
   uint8_t* d_nm_valid = nullptr;      // [N]
+  // opening-tree frontier (azmi_search_expand): allocated by the first call, the records regrown when max_children grows
+  SbFrontierArrays fr{};
+  void* fr_trees = nullptr;           // one allocation behind every per-tree pointer of fr
+  void* fr_records = nullptr;         // one behind the per-record pointers
+  uint32_t fr_cap = 0;                // records fr_records has room for
+  double* fr_host = nullptr;          // pinned [2 N]: reach | temp of the last call, the host side of its upload
+  hipEvent_t fr_uploaded = nullptr;   // behind that upload
+  bool fr_valid = false;              // an expand call has defined the frontier
 };
 
 namespace {
@@ -474,6 +487,10 @@ void azmi_search_destroy(azmi_search* s) {
   (void)hipSetDevice(s->pm->device);
   wu_free(s);        // (hipFree waits for the device)
   if (s->sw_block) (void)hipFree(s->sw_block);
+  if (s->fr_trees) (void)hipFree(s->fr_trees);
+  if (s->fr_records) (void)hipFree(s->fr_records);
+  if (s->fr_host) (void)hipHostFree(s->fr_host);
+  if (s->fr_uploaded) (void)hipEventDestroy(s->fr_uploaded);
   azmi_pm_destroy(s->pm);
   delete s;
 }
@@ -1135,6 +1152,129 @@ int azmi_pool_unique(const uint64_t* keys, const uint8_t* valid, uint32_t n, uin
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return SB_FAIL(e == hipErrorOutOfMemory ? AZMI_ERR_OOM : AZMI_ERR_NO_DEVICE, "azmi_pool_unique: %s", hipGetErrorString(e));
   *n_unique = counts[0]; *n_duplicates = counts[1];
+  return AZMI_OK;
+}
+
+}  // extern "C"
+
+// ---- opening-tree frontier: the kernels of search_frontier_kernels.h, behind everything else -------------------------------------
+namespace {
+
+// the per-tree block (first call) and room for `cap` records (first call, and whenever a call asks for more)
+int frontier_reserve(azmi_search* s, uint32_t cap) {
+  const size_t N = s->n, M = s->pm->gi.M, V = s->pm->gi.P + 1;
+  if (!s->fr_trees) {
+    void* q = nullptr;
+    const size_t bytes = 8 * (2 * N + 2 * N * M + N + 3 * N + N) + 4 * (N + (N + 1) + 1) + (N + N * M);
+    SB_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->fr_host), 2 * N * sizeof(double), hipHostMallocDefault));
+    SB_TRY(hipEventCreateWithFlags(&s->fr_uploaded, hipEventDisableTiming));
+    SB_TRY(hipMalloc(&q, bytes));
+    s->fr_trees = q;
+    double* d = static_cast<double*>(q);
+    s->fr.reach = d; d += N;
+    s->fr.temp = d; d += N;
+    s->fr.raw_pi = d; d += N * M;
+    s->fr.samp_pi = d; d += N * M;
+    s->fr.entropy = d; d += N;
+    s->fr.value = d; d += 3 * N;
+    s->fr.key = reinterpret_cast<uint64_t*>(d); d += N;
+    uint32_t* w = reinterpret_cast<uint32_t*>(d);
+    s->fr.kept = w; w += N;
+    s->fr.first_child = w; w += N + 1;
+    s->fr.total = w; w += 1;
+    uint8_t* b = reinterpret_cast<uint8_t*>(w);
+    s->fr.kind = b; b += N;
+    s->fr.keep = b;
+  }
+  if (!s->fr_records || cap > s->fr_cap) {
+    void* q = nullptr;
+    const size_t C = cap;
+    SB_TRY(hipMalloc(&q, C * (8 + 8 + 4 + 4 + 4 * V + 3)));
+    if (s->fr_records) (void)hipFree(s->fr_records);      // (waits for the device)
+    s->fr_records = q; s->fr_cap = cap;
+    double* d = static_cast<double*>(q);
+    s->fr.child_reach = d; d += C;
+    s->fr.child_key = reinterpret_cast<uint64_t*>(d); d += C;
+    uint32_t* w = reinterpret_cast<uint32_t*>(d);
+    s->fr.parent = w; w += C;
+    s->fr.action = w; w += C;
+    s->fr.child_scores = reinterpret_cast<float*>(w); w += C * V;
+    uint8_t* b = reinterpret_cast<uint8_t*>(w);
+    s->fr.child_player = b; b += C;
+    s->fr.child_variant = reinterpret_cast<int8_t*>(b); b += C;
+    s->fr.child_terminal = b;
+  }
+  return AZMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int azmi_search_expand(azmi_search* s, const double* reach, const double* temp, double min_reach, uint32_t max_children, void* stream) {
+  int rc = begin_move(s, "expand_frontier"); if (rc) return rc;
+  if (!reach || !temp) return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: null argument");
+  if (!(min_reach > 0.0) || !std::isfinite(min_reach)) return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: min_reach must be positive and finite, got %g", min_reach);
+  if (max_children == 0) return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: max_children must be > 0");
+  for (uint32_t i = 0; i < s->n; ++i) {
+    if (!(reach[i] >= 0.0) || !std::isfinite(reach[i]))
+      return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: tree %u: reach must be finite and not negative, got %g", i, reach[i]);
+    if (!(temp[i] >= 0.0) || !std::isfinite(temp[i]))
+      return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: tree %u: temp must be finite and not negative, got %g", i, temp[i]);
+  }
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  const bool first = s->fr_host == nullptr;
+  rc = frontier_reserve(s, max_children); if (rc) return rc;
+  hipStream_t st = pm->pick(stream);
+  const size_t N = s->n;
+  if (!first) SB_TRY(hipEventSynchronize(s->fr_uploaded));      // the previous call's upload may still read fr_host
+  std::memcpy(s->fr_host, reach, N * sizeof(double));
+  std::memcpy(s->fr_host + N, temp, N * sizeof(double));
+  SB_TRY(hipMemcpyAsync(const_cast<double*>(s->fr.reach), s->fr_host, 2 * N * sizeof(double), hipMemcpyHostToDevice, st));      // (reach | temp are neighbours)
+  SB_TRY(hipEventRecord(s->fr_uploaded, st));
+  s->fr.max_children = max_children;
+  s->fr_valid = true;
+  SB_LAUNCH(s, st, k_sb_frontier_policy, k_sb_big_frontier_policy, pm->ep, pm->ar, s->sb, s->fr, s->n, min_reach, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
+  k_frontier_scan<1024><<<1, 1024, 0, st>>>(s->fr.kept, s->n, s->fr.first_child, s->fr.total);
+  s->launches += 1;
+  SB_LAUNCH(s, st, k_sb_frontier_emit, k_sb_big_frontier_emit, pm->ep, pm->ar, s->fr, s->n);
+  SB_TRY(hipGetLastError());
+  return AZMI_OK;
+}
+
+int azmi_search_frontier(azmi_search* s, uint8_t* kind, uint64_t* key, double* raw_pi, double* sampling_pi, double* entropy, double* value,
+                         uint32_t* first_child, uint32_t* parent, uint32_t* action, double* child_reach, uint64_t* child_key, uint8_t* child_player,
+                         int8_t* child_variant, uint8_t* child_terminal, float* child_scores) {
+  int rc = begin_read(s, "frontier"); if (rc) return rc;
+  if (!s->fr_valid) return SB_FAIL(AZMI_ERR_STATE, "frontier: no expand_frontier call has been made on this batch");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t st = pm->last;
+  uint32_t total = 0;
+  SB_TRY(hipMemcpyAsync(&total, s->fr.total, 4, hipMemcpyDeviceToHost, st));
+  rc = check_device(s, st); if (rc) return rc;      // the one synchronisation
+  const size_t N = s->n, M = pm->gi.M, V = pm->gi.P + 1;
+  if (kind) SB_TRY(hipMemcpy(kind, s->fr.kind, N, hipMemcpyDeviceToHost));
+  if (key) SB_TRY(hipMemcpy(key, s->fr.key, N * 8, hipMemcpyDeviceToHost));
+  if (raw_pi) SB_TRY(hipMemcpy(raw_pi, s->fr.raw_pi, N * M * 8, hipMemcpyDeviceToHost));
+  if (sampling_pi) SB_TRY(hipMemcpy(sampling_pi, s->fr.samp_pi, N * M * 8, hipMemcpyDeviceToHost));
+  if (entropy) SB_TRY(hipMemcpy(entropy, s->fr.entropy, N * 8, hipMemcpyDeviceToHost));
+  if (value) SB_TRY(hipMemcpy(value, s->fr.value, N * 3 * 8, hipMemcpyDeviceToHost));
+  if (first_child) SB_TRY(hipMemcpy(first_child, s->fr.first_child, (N + 1) * 4, hipMemcpyDeviceToHost));
+  if (total > s->fr.max_children)
+    return SB_FAIL(AZMI_ERR_OVERFLOW, "frontier: the trees keep %u children, max_children = %u: the first %u records were written; expand again "
+                   "with room for all of them", total, s->fr.max_children, s->fr.max_children);
+  const size_t T = total;
+  if (!T) return AZMI_OK;
+  if (parent) SB_TRY(hipMemcpy(parent, s->fr.parent, T * 4, hipMemcpyDeviceToHost));
+  if (action) SB_TRY(hipMemcpy(action, s->fr.action, T * 4, hipMemcpyDeviceToHost));
+  if (child_reach) SB_TRY(hipMemcpy(child_reach, s->fr.child_reach, T * 8, hipMemcpyDeviceToHost));
+  if (child_key) SB_TRY(hipMemcpy(child_key, s->fr.child_key, T * 8, hipMemcpyDeviceToHost));
+  if (child_player) SB_TRY(hipMemcpy(child_player, s->fr.child_player, T, hipMemcpyDeviceToHost));
+  if (child_variant) SB_TRY(hipMemcpy(child_variant, s->fr.child_variant, T, hipMemcpyDeviceToHost));
+  if (child_terminal) SB_TRY(hipMemcpy(child_terminal, s->fr.child_terminal, T, hipMemcpyDeviceToHost));
+  if (child_scores) SB_TRY(hipMemcpy(child_scores, s->fr.child_scores, T * V * 4, hipMemcpyDeviceToHost));
   return AZMI_OK;
 }
 

@@ -548,6 +548,38 @@ int azmi_search_net_metrics(azmi_search* s, azmi_net* net, double* out, float* r
 int azmi_pool_unique(const uint64_t* keys, const uint8_t* valid, uint32_t n, uint32_t* first_index_out, uint32_t* n_unique,
                      uint32_t* n_duplicates, int device, void* stream);
 
+/* ---- opening trees by reach probability (the reference's opening_analysis.py build_tree, :261-355): the step from n_trees
+ *      searched roots to the next level's frontier, on the device (csrc/search_frontier_kernels.h).  Everything in float64.
+ *   expand    `reach`, `temp`: HOST arrays [n_trees], the reach probability and the sampling temperature of every tree.  Per
+ *             tree: kind = 0 a searched live root, 1 a terminal root (value = its scores(), no policies, no children), 2 the
+ *             tree takes no part (finished, stopped, or reach == 0: zero rows).  For kind 0, expression for expression:
+ *             raw_pi = counts / total (evaluate_node, :233-257), uniform over the root's legal moves when total == 0, on a
+ *             Gumbel batch the improved policy over its float64 sum when that sum is positive; sampling_pi = apply_temperature
+ *             (play.py:256-266): one-hot at the first arg-max for temp == 0, raw_pi for temp == 1, else (raw_pi + 1e-10) **
+ *             (1 / temp) over its sum; entropy = -sum over p > 0 of p ln p; value = root_value(); key = the root's engine key.
+ *             Move a is kept when sampling_pi[a] > 0 and reach * sampling_pi[a] >= min_reach and a is legal at the root (the
+ *             reference would raise from play_move where the `+ 1e-10` gives an illegal move its tiny mass).  Every kept move
+ *             becomes one record, in (tree, action) order: parent, action, child_reach = reach * sampling_pi[a] and, from the
+ *             root state with the action played on a copy, the successor's engine key, player to move, variant (-1 except
+ *             StarGambit), terminal flag and scores() [P + 1] (zeros unless terminal).  A record at or beyond `max_children`
+ *             is not written; the total is still exact.  Exactly three launches, whatever n_trees is (policies, a scan of the
+ *             kept counts, records); asynchronous.  The buffers are allocated by the first call and regrown when max_children
+ *             grows; with no call nothing is allocated or launched.  No tree is changed.  min_reach <= 0, a negative or
+ *             non-finite reach or temp, or max_children == 0: AZMI_ERR_INVALID before any launch; AZMI_ERR_STATE while a
+ *             find_leaves step is pending.
+ *   frontier  the result of the last expand into HOST buffers, any of them NULL; synchronises once.  Per tree: kind [n_trees]
+ *             u8, key [n_trees], raw_pi / sampling_pi [n_trees, M] f64, entropy [n_trees], value [n_trees, 3], first_child
+ *             [n_trees + 1] (the records of tree i are first_child[i] .. first_child[i + 1]; first_child[n_trees] = the total).
+ *             Per record, `total` entries each (buffers with room for the expand's max_children always do): parent, action,
+ *             child_reach, child_key, child_player, child_variant, child_terminal, child_scores [total, P + 1].  A total above
+ *             max_children is AZMI_ERR_OVERFLOW with a message naming the total and the capacity; the per-tree buffers are
+ *             filled, the batch stays usable, and an expand with room gives the full answer.  AZMI_ERR_STATE before any expand.
+ *      A NULL handle is AZMI_ERR_NO_DEVICE without a device, AZMI_ERR_INVALID with one, as for the move entry points. */
+int azmi_search_expand(azmi_search* s, const double* reach, const double* temp, double min_reach, uint32_t max_children, void* stream);
+int azmi_search_frontier(azmi_search* s, uint8_t* kind, uint64_t* key, double* raw_pi, double* sampling_pi, double* entropy, double* value,
+                         uint32_t* first_child, uint32_t* parent, uint32_t* action, double* child_reach, uint64_t* child_key,
+                         uint8_t* child_player, int8_t* child_variant, uint8_t* child_terminal, float* child_scores);
+
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
  *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------
  * `blob` is the BatchNorm-folded, MFMA-fragment-ordered weight image produced by
