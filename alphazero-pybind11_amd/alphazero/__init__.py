@@ -21,7 +21,7 @@ from .games import (GameState, Connect4GS, _TaflBoardGS, TawlbwrddGS, BrandubhGS
                     _StarGambitPlainGS, StarGambitSkirmishGS, StarGambitShowdownGS, StarGambitClashGS, StarGambitBattleGS, StarGambitGS,
                     _c4_from_bytes, _tafl_from_bytes, _sg_from_bytes, hash_game_state, game_replay, symmetries_batch, tafl_symmetries)
 from .mcts import MCTS, Query, _ENGINE_STREAM
-from .search_batch import MCTSBatch, pool_unique
+from .search_batch import MCTSBatch, pool_unique, policy_divergences, POLICY_COLUMNS, SWEEP_COLUMNS
 from .opening_tree import build_opening_tree, OpeningTree, OpeningNode, temperature_at_depth, node_seed
 from .evaluators import dumb_eval, playout_eval_batch, playout_eval
 from .cache import ShardedS3FIFOCache, S3FIFOCache

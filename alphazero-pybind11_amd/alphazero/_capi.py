@@ -223,6 +223,8 @@ SYMBOLS = {
     "azmi_search_captured": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "azmi_search_net_metrics": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "azmi_pool_unique": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _PP(C.c_uint32), _PP(C.c_uint32), C.c_int, _VP]),
+    "azmi_search_sweep_metrics": (C.c_int, [_VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "azmi_policy_divergences": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP, C.c_int, _VP]),
     "azmi_search_expand": (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_uint32, _VP]),
     "azmi_search_frontier": (C.c_int, [_VP] * 16),
     "azmi_game_replay_ex": (C.c_int, [C.c_int, C.c_int, _VP, C.c_uint32, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32]),

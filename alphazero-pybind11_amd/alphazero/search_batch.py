@@ -31,6 +31,42 @@ def pool_unique(keys, valid=None, device=0):
     return out[: nu.value].copy(), int(nd.value)
 
 
+POLICY_COLUMNS = ("jsd", "tv", "hellinger", "top1", "top3", "top9")
+SWEEP_COLUMNS = POLICY_COLUMNS + ("reward", "regret", "pressure", "benefit", "entropy", "value_gap", "abs_err", "closer_than_anchor",
+                                  "closer_than_raw")      # the column order of azmi_search_sweep_metrics
+
+
+def policy_divergences(p, q, device=0):
+    """The six policy figures of policy_metrics.py for every row of two [rows, M] policy arrays, on the device
+    (azmi_policy_divergences), in float64 from the float32 inputs: jsd, tv, hellinger and top1 / top3 / top9 =
+    |top_k(p) & top_k(q)| / k.  top_k(x) is np.argsort(x, kind="stable")[-k:] - among equal values the higher index ranks
+    higher; with M < k every index is in both sets and the divisor stays k.  A pair of one-dimensional arrays is one row.
+    -> dict of six float64 [rows] arrays.  rows == 0 touches no device."""
+    try:
+        a = np.asarray(p, dtype=np.float32)
+        b = np.asarray(q, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise RuntimeError("policy_divergences: p and q must be arrays of numbers") from None
+    if a.ndim == 1 and b.ndim == 1:
+        a, b = a[None, :], b[None, :]
+    if a.ndim != 2 or b.ndim != 2:
+        raise RuntimeError(f"policy_divergences: p and q must be [rows, M] arrays, got shapes {a.shape} and {b.shape}")
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape:
+        raise RuntimeError(f"policy_divergences: p and q must have one shape, got {a.shape} and {b.shape}")
+    rows, M = a.shape
+    if M < 1 or M > 1 << 20:
+        raise RuntimeError(f"policy_divergences: M must be in [1, 2^20], got {M}")
+    if rows > 1 << 30:
+        raise RuntimeError(f"policy_divergences: at most 2^30 rows, got {rows}")
+    if isinstance(device, bool) or not isinstance(device, (int, np.integer)) or device < 0:
+        raise RuntimeError(f"policy_divergences: device must be a device index, got {device!r}")
+    out = np.zeros((rows, len(POLICY_COLUMNS)), np.float64)
+    check(lib.azmi_policy_divergences(a.ctypes.data if rows else None, b.ctypes.data if rows else None, rows, M,
+                                      out.ctypes.data if rows else None, int(device), None))
+    return {k: out[:, c].copy() for c, k in enumerate(POLICY_COLUMNS)}
+
+
 class MCTSBatch:
     """N independent search trees on N positions of one game, advanced together on the device (azmi_search_*): the job of the
     reference's evaluation tools, which hold a list of MCTS objects, step them in lock step and batch the leaves into one net
@@ -113,7 +149,9 @@ class MCTSBatch:
 
     A visit sweep (mcts_analysis.py:884-972): search_to(targets, ..., checkpoints=(c0, c1, ...)) searches tree i until
     root_n(i) >= targets[i] and records counts / probs / root_values / root_q_values on the device the first time root_n(i)
-    reaches each checkpoint; checkpoints() returns the snapshots.  See search_to().
+    reaches each checkpoint; checkpoints() returns the snapshots.  See search_to().  sweep_metrics(anchor, raw, reference,
+    outcomes) scores every snapshot against the anchor one on the device (:1150-1400): divergences, top-k agreement, expected
+    reward and regret, the signal figures against the one-visit policy, the value gaps, and their per-checkpoint means.
 
     A frozen evaluation set (frozen_eval.py:330-413, 541-672): with `capture=True` (set_capture(), play(..., capture=)) every
     move of play() records the root of every live tree before its search, one launch more per move and none with capture off;
@@ -342,6 +380,87 @@ class MCTSBatch:
         check(lib.azmi_search_checkpoints(self._h, mask.ctypes.data, out["root_n"].ctypes.data, out["counts"].ctypes.data,
                                           out["probs"].ctypes.data, out["root_values"].ctypes.data, out["root_q_values"].ctypes.data))
         out["taken"] = ((mask[:, None] >> np.arange(J, dtype=np.uint32)[None, :]) & 1).astype(bool)
+        return out
+
+    @staticmethod
+    def _sweep_index(what, x, J):
+        """-> x as a checkpoint index of a set of J, negative values counting from its end"""
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise RuntimeError(f"sweep_metrics: {what} must be a checkpoint index (an integer), got {x!r}")
+        if not -J <= x < J:
+            raise RuntimeError(f"sweep_metrics: {what} = {x} out of range: the reference set has {J} checkpoints")
+        return int(x) % J
+
+    def _sweep_args(self, anchor, raw, reference, outcomes):
+        """-> (reference batch, anchor, raw or -1, outcomes float64 [n] or None); every argument error before any device call"""
+        J = getattr(self, "_sweep_j", None)
+        if J is None:
+            raise RuntimeError("sweep_metrics: no search_to call has been made on this batch")
+        if getattr(self, "_rows", None) is not None:
+            raise RuntimeError("sweep_metrics: a find_leaves step is pending; call process_results first")
+        ref = self if reference is None else reference
+        if not isinstance(ref, MCTSBatch):
+            raise RuntimeError(f"sweep_metrics: reference must be an MCTSBatch or None, got {type(reference).__name__}")
+        if ref is not self:
+            if getattr(ref._game, "GAME_ID", None) != getattr(self._game, "GAME_ID", None):
+                raise RuntimeError(f"sweep_metrics: the reference batch holds another game ({ref._game.__name__}, "
+                                   f"this batch {self._game.__name__})")
+            if ref._n != self._n:
+                raise RuntimeError(f"sweep_metrics: the reference batch holds {ref._n} trees, this batch {self._n}")
+            if ref._device != self._device:
+                raise RuntimeError(f"sweep_metrics: the reference batch is on device {ref._device}, this batch on {self._device}")
+            if getattr(ref, "_sweep_j", None) is None:
+                raise RuntimeError("sweep_metrics: no search_to call has been made on the reference batch")
+            if getattr(ref, "_rows", None) is not None:
+                raise RuntimeError("sweep_metrics: a find_leaves step is pending on the reference batch; call process_results first")
+        Jr = ref._sweep_j
+        if Jr == 0:
+            raise RuntimeError("sweep_metrics: the reference set has no checkpoints: nothing to anchor on")
+        a = self._sweep_index("anchor", anchor, Jr)
+        r = -1 if raw is None else self._sweep_index("raw", raw, Jr)
+        o = None
+        if outcomes is not None:
+            try:
+                o = np.ascontiguousarray(outcomes, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise RuntimeError(f"sweep_metrics: outcomes must be {self._n} numbers, got {outcomes!r}") from None
+            if o.shape != (self._n,):
+                raise RuntimeError(f"sweep_metrics: outcomes: one per tree ({self._n}), got shape {o.shape}")
+        return ref, a, r, o
+
+    def sweep_metrics(self, anchor=-1, raw=None, reference=None, outcomes=None):
+        """Score every snapshot of the last search_to() against the anchor snapshot of the same tree, on the device
+        (azmi_search_sweep_metrics): what mcts_analysis.run_analysis does with its sweep once the search is over
+        (mcts_analysis.py:1150-1400), without copying the [n, J, M] snapshots out.  `reference`: the batch whose snapshot set
+        supplies the anchor row, the raw row and root_q_values (default: this batch; the reference's `base_ref` tree when the
+        swept trees search with root noise) - same game, n and device.  `anchor`, `raw`: checkpoint indices into the
+        reference's set, negative ones counting from its end; raw (None: none) is the one-visit checkpoint the "signal"
+        figures compare against.  `outcomes`: None or n game outcomes.
+        With p the anchor policy, q the policy of row (i, j), r the raw policy, Q the anchor's root_q_values and v =
+        root_values[..., 0], all float32 snapshots computed with in float64:
+          jsd, tv, hellinger, top1, top3, top9    policy_divergences(p, q)
+          reward = sum q Q, regret = reward(anchor row) - reward
+          pressure = KL(q || r + 1e-10), benefit = reward - sum r Q, entropy = -sum q ln q         (pressure, benefit: need raw)
+          value_gap = |v_j - v_anchor|
+          abs_err = |v_j - outcome|, closer_than_anchor, closer_than_raw (1.0 / 0.0)               (need outcomes; the last, raw)
+          ceiling[i] = KL(p || r + 1e-10)                                                          (needs raw)
+        A row is valid when snapshot j of tree i and the reference's anchor snapshot of tree i were both taken; an invalid row
+        is NaN everywhere, and what needs a raw row or outcomes that are not there is NaN.
+        -> dict: one float64 [n, J] array per name above, ceiling [n], valid bool [n, J], and mean / count: dicts of [J] arrays,
+        per column the mean over the trees that are not NaN there and their number.  Two launches and one synchronisation
+        whatever n and J are; the sums run in a fixed order, so two calls give the same bits.  Correlations and calibration
+        bins (mcts_analysis.py:1289-1353) are a few numpy lines over the returned arrays."""
+        ref, a, r, o = self._sweep_args(anchor, raw, reference, outcomes)
+        n, J, C_ = self._n, self._sweep_j, len(SWEEP_COLUMNS)
+        rows = np.zeros((n, J, C_), np.float64); ceiling = np.zeros(n, np.float64)
+        mean = np.zeros((J, C_), np.float64); count = np.zeros((J, C_), np.uint32); valid = np.zeros((n, J), np.uint8)
+        check(lib.azmi_search_sweep_metrics(self._h, None if ref is self else ref._h, a, r, None if o is None else o.ctypes.data,
+                                            rows.ctypes.data, ceiling.ctypes.data, mean.ctypes.data, count.ctypes.data,
+                                            valid.ctypes.data, _ENGINE_STREAM))
+        out = {k: rows[:, :, c].copy() for c, k in enumerate(SWEEP_COLUMNS)}
+        out.update(ceiling=ceiling, valid=valid.astype(bool),
+                   mean={k: mean[:, c].copy() for c, k in enumerate(SWEEP_COLUMNS)},
+                   count={k: count[:, c].astype(np.int64) for c, k in enumerate(SWEEP_COLUMNS)})
         return out
 
     def synchronize(self):

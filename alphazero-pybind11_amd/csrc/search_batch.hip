@@ -18,6 +18,9 @@
 // azmi_search_expand / azmi_search_frontier are the step between two levels of opening_analysis.py's build_tree
 // (csrc/search_frontier_kernels.h): the sampling distribution of every searched root, the moves kept by reach probability and the
 // rules applied to every kept child, three launches whatever N is.
+// azmi_search_sweep_metrics scores the snapshot set of a run_to against its anchor checkpoint, the second half of
+// mcts_analysis.py:run_analysis (csrc/search_sweep_metrics_kernels.h): one launch over the (tree, checkpoint) rows, one for the
+// per-checkpoint means; azmi_policy_divergences is the same row function over any [rows, M] pair of HOST policies.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +35,7 @@
 #include "search_batch_kernels.h"
 #include "search_pool_kernels.h"
 #include "search_frontier_kernels.h"
+#include "search_sweep_metrics_kernels.h"
 
 using namespace azmi;
 
@@ -96,6 +100,9 @@ struct azmi_search {
   double* fr_host = nullptr;          // pinned [2 N]: reach | temp of the last call, the host side of its upload
   hipEvent_t fr_uploaded = nullptr;   // behind that upload
   bool fr_valid = false;              // an expand call has defined the frontier
+  // sweep metrics (azmi_search_sweep_metrics): allocated by the first call, regrown when a sweep brings more checkpoints
+  void* sm_block = nullptr;           // rows [N, J, 15] | ceiling [N] | mean [J, 15] | outcomes [N] f64, count [J, 15] u32, valid [N, J] u8
+  uint32_t sm_cap = 0;                // checkpoints the block has room for
 };
 
 namespace {
@@ -487,6 +494,7 @@ void azmi_search_destroy(azmi_search* s) {
   (void)hipSetDevice(s->pm->device);
   wu_free(s);        // (hipFree waits for the device)
   if (s->sw_block) (void)hipFree(s->sw_block);
+  if (s->sm_block) (void)hipFree(s->sm_block);
   if (s->fr_trees) (void)hipFree(s->fr_trees);
   if (s->fr_records) (void)hipFree(s->fr_records);
   if (s->fr_host) (void)hipHostFree(s->fr_host);
@@ -1275,6 +1283,111 @@ int azmi_search_frontier(azmi_search* s, uint8_t* kind, uint64_t* key, double* r
   if (child_variant) SB_TRY(hipMemcpy(child_variant, s->fr.child_variant, T, hipMemcpyDeviceToHost));
   if (child_terminal) SB_TRY(hipMemcpy(child_terminal, s->fr.child_terminal, T, hipMemcpyDeviceToHost));
   if (child_scores) SB_TRY(hipMemcpy(child_scores, s->fr.child_scores, T * V * 4, hipMemcpyDeviceToHost));
+  return AZMI_OK;
+}
+
+}  // extern "C"
+
+// ---- sweep metrics: the kernels of search_sweep_metrics_kernels.h, behind everything else ------------------------------------------
+namespace {
+
+// the output block of azmi_search_sweep_metrics for the J checkpoints of the current snapshot set
+struct SweepMetricsOut {
+  double *rows, *ceiling, *mean, *outcomes;
+  uint32_t* count;
+  uint8_t* valid;
+};
+
+int sweep_metrics_reserve(azmi_search* s, uint32_t j, SweepMetricsOut* o) {
+  const size_t N = s->n;
+  if (!s->sm_block || j > s->sm_cap) {
+    const size_t cap = std::max<uint32_t>(j, 1u);
+    void* q = nullptr;
+    SB_TRY(hipMalloc(&q, 8 * (N * cap * kSweepCols + 2 * N + cap * kSweepCols) + 4 * cap * kSweepCols + N * cap));
+    if (s->sm_block) (void)hipFree(s->sm_block);      // (waits for the device)
+    s->sm_block = q; s->sm_cap = static_cast<uint32_t>(cap);
+  }
+  const size_t cap = s->sm_cap;
+  double* d = static_cast<double*>(s->sm_block);
+  o->rows = d; d += N * cap * kSweepCols;
+  o->ceiling = d; d += N;
+  o->mean = d; d += cap * kSweepCols;
+  o->outcomes = d; d += N;
+  o->count = reinterpret_cast<uint32_t*>(d);
+  o->valid = reinterpret_cast<uint8_t*>(o->count + cap * kSweepCols);
+  return AZMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int azmi_search_sweep_metrics(azmi_search* s, azmi_search* ref, uint32_t anchor, int32_t raw, const double* outcomes, double* out_rows,
+                              double* out_tree, double* out_mean, uint32_t* out_count, uint8_t* valid, void* stream) {
+  int rc = begin_move(s, "sweep_metrics"); if (rc) return rc;
+  if (!ref) ref = s;
+  if (!s->sw_valid) return SB_FAIL(AZMI_ERR_STATE, "sweep_metrics: no search_to call has been made on this batch");
+  if (!ref->sw_valid) return SB_FAIL(AZMI_ERR_STATE, "sweep_metrics: no search_to call has been made on the reference batch");
+  if (ref->step_pending) return SB_FAIL(AZMI_ERR_STATE, "sweep_metrics: a find_leaves step is pending on the reference batch; call process_results first");
+  if (ref->pm->game != s->pm->game || ref->n != s->n || ref->pm->device != s->pm->device)
+    return SB_FAIL(AZMI_ERR_INVALID, "sweep_metrics: the reference batch must hold the same game, tree count and device (game %d, %u trees, "
+                   "device %d against game %d, %u trees, device %d)", ref->pm->game, ref->n, ref->pm->device, s->pm->game, s->n, s->pm->device);
+  const uint32_t J = s->sw.n_cp, Jr = ref->sw.n_cp;
+  if (anchor >= Jr) return SB_FAIL(AZMI_ERR_INVALID, "sweep_metrics: anchor %u out of range: the reference set has %u checkpoints", anchor, Jr);
+  if (raw < -1 || (raw >= 0 && static_cast<uint32_t>(raw) >= Jr))
+    return SB_FAIL(AZMI_ERR_INVALID, "sweep_metrics: raw %d out of range: -1 for none, or one of the reference set's %u checkpoints", raw, Jr);
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  hipStream_t prev = pm->last;
+  hipStream_t st = pm->pick(stream);
+  if (prev != st) SB_TRY(hipStreamSynchronize(prev));                              // the snapshots may still be on their way
+  if (ref != s && ref->pm->last != st) SB_TRY(hipStreamSynchronize(ref->pm->last));
+  SweepMetricsOut o;
+  rc = sweep_metrics_reserve(s, J, &o); if (rc) return rc;
+  const size_t N = s->n;
+  if (outcomes) SB_TRY(hipMemcpyAsync(o.outcomes, outcomes, N * 8, hipMemcpyHostToDevice, st));
+  SB_LAUNCH(s, st, k_sb_sweep_metrics, k_sb_big_sweep_metrics, s->sw, ref->sw, s->n, anchor, raw, outcomes ? o.outcomes : nullptr, o.rows, o.ceiling,
+            o.valid);
+  k_sb_sweep_mean<<<std::max(J, 1u), kSweepMeanThreads, 0, st>>>(o.rows, s->n, J, o.mean, o.count);
+  s->launches += 1;
+  SB_TRY(hipGetLastError());
+  if (out_tree) SB_TRY(hipMemcpyAsync(out_tree, o.ceiling, N * 8, hipMemcpyDeviceToHost, st));
+  if (J) {
+    if (out_rows) SB_TRY(hipMemcpyAsync(out_rows, o.rows, N * J * kSweepCols * 8, hipMemcpyDeviceToHost, st));
+    if (out_mean) SB_TRY(hipMemcpyAsync(out_mean, o.mean, static_cast<size_t>(J) * kSweepCols * 8, hipMemcpyDeviceToHost, st));
+    if (out_count) SB_TRY(hipMemcpyAsync(out_count, o.count, static_cast<size_t>(J) * kSweepCols * 4, hipMemcpyDeviceToHost, st));
+    if (valid) SB_TRY(hipMemcpyAsync(valid, o.valid, N * J, hipMemcpyDeviceToHost, st));
+  }
+  return check_device(s, st);      // the one synchronisation
+}
+
+int azmi_policy_divergences(const float* p, const float* q, uint32_t rows, uint32_t M, double* out, int device, void* stream) {
+  constexpr uint32_t kMaxRows = 1u << 30, kMaxMoves = 1u << 20;
+  if (rows > kMaxRows || M == 0 || M > kMaxMoves)
+    return SB_FAIL(AZMI_ERR_INVALID, "azmi_policy_divergences: rows = %u, M = %u: at most %u rows of 1 to %u moves", rows, M, kMaxRows, kMaxMoves);
+  if (rows && (!p || !q || !out)) return SB_FAIL(AZMI_ERR_INVALID, "azmi_policy_divergences: null argument");
+  if (rows == 0) return AZMI_OK;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SB_FAIL(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  if (device < 0 || device >= ndev) return SB_FAIL(AZMI_ERR_INVALID, "device %d out of range", device);
+  SB_TRY(hipSetDevice(device));
+  hipStream_t st = stream == AZMI_STREAM_ENGINE ? nullptr : static_cast<hipStream_t>(stream);
+  const size_t cells = static_cast<size_t>(rows) * M;
+  DevTemps tmp;
+  float *d_p = nullptr, *d_q = nullptr;
+  double* d_out = nullptr;
+  AZMI_HIP_TRY_NODEV(tmp.upload_async(d_p, p, cells, st));
+  hipError_t e = tmp.upload_async(d_q, q, cells, st);
+  if (e == hipSuccess) e = tmp.alloc(d_out, static_cast<size_t>(rows) * kPolicyCols);
+  if (e == hipSuccess) {
+    if (M <= 8) k_policy_divergences<8><<<(rows + 31u) / 32u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
+    else k_policy_divergences<64><<<(rows + 3u) / 4u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, static_cast<size_t>(rows) * kPolicyCols * 8, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);      // always: what was queued reads the buffers tmp is about to free
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return SB_FAIL(e == hipErrorOutOfMemory ? AZMI_ERR_OOM : AZMI_ERR_NO_DEVICE, "azmi_policy_divergences: %s", hipGetErrorString(e));
   return AZMI_OK;
 }
 

@@ -518,6 +518,44 @@ int azmi_search_run_to(azmi_search* s, int eval_type, azmi_net* net, azmi_cache*
                        uint32_t n_checkpoints, float temp, int pruned, int root_noise_enabled, void* stream);
 int azmi_search_checkpoints(azmi_search* s, uint32_t* taken_mask, uint32_t* root_n, uint32_t* counts, float* probs, float* root_values,
                             float* root_q);
+/* ---- scoring a visit sweep against its anchor: the second half of mcts_analysis.py:run_analysis (:1150-1400), on the snapshot
+ *      set run_to left on the device (csrc/search_sweep_metrics_kernels.h).  Everything in float64, the float32 snapshot values
+ *      converted exactly; the reference computes in float32 numpy, which nothing can be matched bit for bit against.
+ *   sweep_metrics  `ref`: another azmi_search of the same game, tree count and device, or NULL for `s` itself; its snapshot set
+ *                 supplies the anchor row, the raw row and root_q (the reference's `base_ref` tree when the swept trees are
+ *                 self-play-mode ones).  `anchor`, `raw`: checkpoint indices into ref's set, raw = -1 for none.  `outcomes`: HOST
+ *                 array [n_trees] of game outcomes, or NULL.  With p = ref.probs[i, anchor], r = ref.probs[i, raw], Q =
+ *                 ref.root_q[i, anchor], v = root_values[..., 0] and row (i, j): q = probs[i, j], the 15 columns of out_rows are,
+ *                 policy_metrics.py and mcts_analysis.py:1196-1258 expression for expression,
+ *                   0 jsd        0.5 sum_{p>0} p ln(p / m) + 0.5 sum_{q>0} q ln(q / m), m = 0.5 (p + q)
+ *                   1 tv         0.5 sum |p - q|
+ *                   2 hellinger  sqrt(0.5 sum (sqrt p - sqrt q)^2)
+ *                   3 top1, 4 top3, 5 top9   |top_k(p) & top_k(q)| / k.  top_k(x) = the last k indices of x ordered ascending by
+ *                                (value, index), np.argsort(x, kind="stable")[-k:]: among equal values the higher index ranks
+ *                                higher.  This rule is the project's definition (the reference's default argsort is not stable
+ *                                for every M and numpy build).  With M < k every index is in both sets and the divisor stays k.
+ *                   6 reward     sum q Q            7 regret   reward of the anchor row - reward
+ *                   8 pressure   sum_{q>0} q ln(q / (r + 1e-10))        9 benefit  reward - sum r Q
+ *                  10 entropy    -sum_{q>0} q ln q                     11 value_gap  |v_j - v_anchor|
+ *                  12 abs_err    |v_j - outcome|   13 closer_than_anchor  1.0 if |v_j - o| < |v_anchor - o| else 0.0
+ *                  14 closer_than_raw  1.0 if |v_j - o| < |v_raw - o| else 0.0
+ *                 and out_tree[i] = the ceiling KL(p || r + 1e-10).  Row (i, j) is valid when snapshot j of tree i and ref's
+ *                 anchor snapshot of tree i were both taken; an invalid row is NaN in every column.  Columns 8, 9, 14 and
+ *                 out_tree are NaN when raw is -1 or ref's raw snapshot of the tree was not taken; columns 12-14 are NaN without
+ *                 outcomes.  out_mean[j, c] / out_count[j, c]: the mean over, and the number of, the trees whose row (i, j) is
+ *                 not NaN in column c (NaN for a count of 0), summed in a fixed order: the bits do not depend on scheduling.
+ *                 Two launches (rows, means) whatever n_trees and J are, and one synchronisation (a `ref` or a snapshot set last
+ *                 used on another stream is waited for first).  HOST buffers, any of them NULL: out_rows [n_trees, J, 15] f64,
+ *                 out_tree [n_trees] f64, out_mean [J, 15] f64, out_count [J, 15] u32, valid [n_trees, J] u8.  The output block is
+ *                 allocated by the first call; no tree and no snapshot is changed.  AZMI_ERR_STATE before any run_to on s or ref,
+ *                 or while a find_leaves step is pending; AZMI_ERR_INVALID for an index out of range or a ref of another game,
+ *                 tree count or device; the object stays usable.
+ * azmi_policy_divergences is columns 0-5 as one call on HOST float32 arrays p, q [rows, M] -> out [rows, 6] f64, by the same row
+ * function (the batch_* functions of policy_metrics.py, per row).  rows == 0 is legal and touches no device; M == 0, M > 2^20 or
+ * rows > 2^30 is AZMI_ERR_INVALID.  `stream`: a HIP stream or NULL; the call synchronises it. */
+int azmi_search_sweep_metrics(azmi_search* s, azmi_search* ref, uint32_t anchor, int32_t raw, const double* outcomes, double* out_rows,
+                              double* out_tree, double* out_mean, uint32_t* out_count, uint8_t* valid, void* stream);
+int azmi_policy_divergences(const float* p, const float* q, uint32_t rows, uint32_t M, double* out, int device, void* stream);
 /* ---- a frozen evaluation set on the device: the two parts of frozen_eval.py around its search loop.  _burst_capture_one_variant
  * (frozen_eval.py:330-413) plays whole games and keeps every position it has not seen yet; the metric extraction
  * (frozen_eval.py:573-575, 649-672) compares every searched root with one raw forward of the net.
