@@ -11,7 +11,7 @@ Put the directory that contains this package on sys.path:
     sys.path.insert(0, "<repo>/alphazero-pybind11_amd"); import alphazero
 
 This file only re-exports; the code lives in the sibling modules (params, games, mcts, search_batch, opening_tree, evaluators, cache,
-play_manager, drivers), whose imports follow that order and never form a cycle.
+play_manager, drivers, samples), whose imports follow that order and never form a cycle.
 """
 from . import _capi
 from ._capi import lib, check
@@ -29,6 +29,8 @@ from .play_manager import GameData, PlayManager, _f32
 from .drivers import (run_rounds, run_rounds_groups, pipeline_supported, pipeline_supported_groups, run_pipeline, run_pipeline_groups,
                       _pipe_stats, _PIPE_KEYS, pipeline_log_duplicates, cache_find_group, cache_insert_locked, rng_probe, tracy_is_enabled, tracy_frame_mark,
                       _tracy_zone_begin, _tracy_zone_end, _tracy_set_thread_name)
+from . import samples
+from .samples import sample_loss, resample_plan, resample_rows, resample_by_surprise, iteration_losses
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use

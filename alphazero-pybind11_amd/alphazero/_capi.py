@@ -106,6 +106,10 @@ class EngineOptsC(C.Structure):
     ]
 
 
+class ResampleRecordC(C.Structure):      # azmi_resample_record
+    _fields_ = [("total_loss", C.c_double), ("rows_out", C.c_uint64), ("nonfinite", C.c_uint32), ("first_nonfinite", C.c_uint32)]
+
+
 # every symbol include/azmi.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _PP = C.POINTER
@@ -176,6 +180,10 @@ SYMBOLS = {
     "azmi_symmetries": (C.c_int, [C.c_int, C.c_int, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, _VP]),
     "azmi_tafl_symmetries": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, _VP]),
     "azmi_symmetries_last_error": (C.c_char_p, []),
+    "azmi_sample_loss": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_double, _VP, C.c_int, _VP]),
+    "azmi_resample_plan": (C.c_int, [_VP, C.c_uint32, C.c_uint64, _VP, _VP, _PP(ResampleRecordC), C.c_int, _VP]),
+    "azmi_resample_gather": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _PP(_VP), _PP(_VP), _PP(C.c_uint32), C.c_int, _VP]),
+    "azmi_samples_last_error": (C.c_char_p, []),
     "azmi_pm_net_forward": (C.c_int, [_VP, _VP, _VP]),
     "azmi_pm_net_forward_group": (C.c_int, [_VP, C.c_uint32, _VP, _VP]),
     "azmi_pm_groups": (C.c_int, [_VP, _PP(C.c_uint32), _PP(C.c_uint32)]),

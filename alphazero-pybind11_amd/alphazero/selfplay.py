@@ -191,6 +191,20 @@ def self_play(game, params, net=None, engines=None, seed=20240601, device=0, str
     return res, samples
 
 
+def process_samples(game, samples, net, seed, **kwargs):
+    """The two stages between self_play and training (game_runner.py:4234-4239): exploit_symmetries (symmetries_batch, when the
+    game has more than one symmetry), then resample_by_surprise with `net` and `seed`; the keywords are resample_by_surprise's.
+    -> ((canonical, v, pi) resampled, loss), loss holding one entry per symmetry-expanded sample."""
+    from .games import symmetries_batch
+    from .samples import resample_by_surprise, _check_samples, _check_seed
+    cls = game if isinstance(game, type) else type(game)
+    _check_samples("process_samples", samples, kwargs.get("batch_rows", 65536))      # the named errors, before symmetries_batch's own
+    _check_seed("process_samples", seed)
+    if cls.NUM_SYMMETRIES() > 1 and int(samples[0].shape[0]) > 0:
+        samples = symmetries_batch(cls, *samples)
+    return resample_by_surprise(samples, net, seed, **kwargs)
+
+
 def _pipeline_step(call, state, driver, what):
     """One call of the asynchronous pipeline under the error contract of include/azmi.h: a "pipeline error mask" error (a spin that hit
     the stall cap: the host was held up between the launches, another tenant took CUs) leaves the engine whole and the call is simply

@@ -1,0 +1,179 @@
+// Per-row surprise loss, resample plan and row gather on the device: the host side of samples_kernels.h.
+// azmi_sample_loss / azmi_resample_plan / azmi_resample_gather take DEVICE pointers and a stream; only the plan synchronises,
+// once, to hand back its record (the caller needs rows_out to size the gather's outputs).
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <mutex>
+#include <string>
+
+#include "../../include/azmi.h"
+#include "samples_kernels.h"
+
+namespace {
+using namespace azmi;
+
+static_assert(sizeof(ResampleRecord) == sizeof(azmi_resample_record), "azmi_resample_record is the device record");
+
+thread_local std::string g_samples_err;
+
+int sfail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_samples_err = buf;
+  return code;
+}
+
+int hip_fail(const char* what, hipError_t e) {
+  return sfail(e == hipErrorOutOfMemory ? AZMI_ERR_OOM : AZMI_ERR_NO_DEVICE, "%s: %s", what, hipGetErrorString(e));
+}
+
+// selects `device` for one call and puts the thread's current device back when the call ends
+struct DeviceScope {
+  int prev = -1;
+  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+  int enter(const char* what, int device) {
+    int ndev = 0, cur = -1;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return sfail(AZMI_ERR_NO_DEVICE, "%s: no HIP device: libazmi has no CPU path", what);
+    if (device < 0 || device >= ndev) return sfail(AZMI_ERR_INVALID, "%s: device %d out of range", what, device);
+    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+    if (cur == device) return AZMI_OK;
+    const hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return hip_fail(what, e);
+    prev = cur;
+    return AZMI_OK;
+  }
+};
+
+// The plan's scratch block, one per device, kept between calls and grown when a call needs more.  A call holds the mutex up to
+// its synchronisation, so two calls never use a block at once, and in the steady state no call allocates or frees (hipFree waits
+// for the whole device, not for the call's stream).
+constexpr int kPlanMaxDevices = 64;
+struct PlanScratch { void* block; size_t bytes; };
+std::mutex g_plan_mutex;
+PlanScratch g_plan_scratch[kPlanMaxDevices];
+
+uint32_t tiles_of(uint32_t n) { return (n + kPlanBlock - 1) / kPlanBlock; }
+
+}  // namespace
+
+extern "C" {
+
+const char* azmi_samples_last_error(void) { return g_samples_err.c_str(); }
+
+int azmi_sample_loss(const float* dev_target, const float* dev_p, uint32_t n, uint32_t M, double scale, double* dev_loss_out, int device,
+                     void* stream) {
+  if (n > kPlanMaxRows || M == 0 || M > (1u << 20))
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_loss: n = %u, M = %u: at most %u rows of 1 to %u entries", n, M, kPlanMaxRows, 1u << 20);
+  if (n == 0) return AZMI_OK;
+  if (!dev_target || !dev_p || !dev_loss_out) return sfail(AZMI_ERR_INVALID, "azmi_sample_loss: null argument");
+  DeviceScope scope;
+  int rc = scope.enter("azmi_sample_loss", device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // the lane group of a row: 8 lanes for M <= 8, then 16, 32, and one wavefront striding m from M = 33 on
+  if (M <= 8) k_sample_loss<8><<<(n + 31u) / 32u, kLossThreads, 0, st>>>(dev_target, dev_p, n, M, scale, dev_loss_out);
+  else if (M <= 16) k_sample_loss<16><<<(n + 15u) / 16u, kLossThreads, 0, st>>>(dev_target, dev_p, n, M, scale, dev_loss_out);
+  else if (M <= 32) k_sample_loss<32><<<(n + 7u) / 8u, kLossThreads, 0, st>>>(dev_target, dev_p, n, M, scale, dev_loss_out);
+  else k_sample_loss<64><<<(n + 3u) / 4u, kLossThreads, 0, st>>>(dev_target, dev_p, n, M, scale, dev_loss_out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : hip_fail("k_sample_loss", e);
+}
+
+int azmi_resample_plan(const double* dev_loss, uint32_t n, uint64_t seed, uint32_t* dev_copies, uint64_t* dev_offsets,
+                       azmi_resample_record* host_record_out, int device, void* stream) {
+  if (!host_record_out) return sfail(AZMI_ERR_INVALID, "azmi_resample_plan: null argument");
+  *host_record_out = azmi_resample_record{0.0, 0, 0, kPlanNone};
+  if (n > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "azmi_resample_plan: n = %u: at most %u rows", n, kPlanMaxRows);
+  if (n == 0) return AZMI_OK;
+  if (!dev_loss || (dev_copies == nullptr) != (dev_offsets == nullptr))
+    return sfail(AZMI_ERR_INVALID, "azmi_resample_plan: null argument (dev_copies and dev_offsets: both, or neither for the sums alone)");
+  if (device >= kPlanMaxDevices) return sfail(AZMI_ERR_INVALID, "azmi_resample_plan: device %d: at most %d devices", device, kPlanMaxDevices);
+  DeviceScope scope;
+  int rc = scope.enter("azmi_resample_plan", device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // one block: the record | the tile sums of the three levels (f64) | the tile totals of the scan's upper levels (u64)
+  const uint32_t t0 = tiles_of(n), t1 = tiles_of(t0);      // t1 <= 1024: the level above it is one tile
+  const size_t words = 4 + 2 * (size_t(t0) + t1);
+  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  PlanScratch& sc = g_plan_scratch[device];
+  hipError_t e = hipSuccess;
+  if (sc.bytes < words * 8) {      // first call on this device, or a larger n than any before
+    if (sc.block) (void)hipFree(sc.block);
+    sc.block = nullptr; sc.bytes = 0;
+    e = hipMalloc(&sc.block, words * 8);
+    if (e != hipSuccess) { sc.block = nullptr; return hip_fail("azmi_resample_plan", e); }
+    sc.bytes = words * 8;
+  }
+  void* block = sc.block;
+  ResampleRecord* rec = static_cast<ResampleRecord*>(block);
+  double* sum0 = static_cast<double*>(block) + 4;
+  double* sum1 = sum0 + t0;
+  uint64_t* tot0 = reinterpret_cast<uint64_t*>(sum1 + t1);
+  uint64_t* tot1 = tot0 + t0;
+  e = hipMemsetAsync(rec, 0, sizeof *rec, st);
+  if (e == hipSuccess) e = hipMemsetAsync(&rec->first_nonfinite, 0xFF, 4, st);
+  if (e == hipSuccess) {
+    // the total: a tree over tiles of kPlanBlock, whose top writes the record
+    k_plan_sum<true><<<t0, kPlanBlock, 0, st>>>(dev_loss, n, t0 == 1 ? &rec->total_loss : sum0, rec);
+    if (t0 > 1) k_plan_sum<false><<<t1, kPlanBlock, 0, st>>>(sum0, t0, t1 == 1 ? &rec->total_loss : sum1, rec);
+    if (t1 > 1) k_plan_sum<false><<<1, kPlanBlock, 0, st>>>(sum1, t1, &rec->total_loss, rec);
+    if (dev_copies) {
+      // the counts and their scan inside a tile, the tile totals scanned level by level, the bases handed down again
+      k_plan_copies<<<t0, kPlanBlock, 0, st>>>(dev_loss, n, seed, &rec->total_loss, dev_copies, dev_offsets, t0 == 1 ? &rec->rows_out : tot0);
+      if (t0 > 1) k_plan_scan<<<t1, kPlanBlock, 0, st>>>(tot0, t0, t1 == 1 ? &rec->rows_out : tot1);
+      if (t1 > 1) {
+        k_plan_scan<<<1, kPlanBlock, 0, st>>>(tot1, t1, &rec->rows_out);
+        k_plan_add<<<t1, kPlanBlock, 0, st>>>(tot0, t0, tot1);
+      }
+      if (t0 > 1) k_plan_add<<<t0, kPlanBlock, 0, st>>>(dev_offsets, n, tot0);
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_record_out, rec, sizeof *rec, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);      // the one synchronisation; always: what was queued uses the block the next call reuses
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail("azmi_resample_plan", e);
+  return AZMI_OK;
+}
+
+int azmi_resample_gather(const uint32_t* dev_copies, const uint64_t* dev_offsets, uint32_t n, uint32_t n_arrays, const void* const* dev_in,
+                         void* const* dev_out, const uint32_t* row_bytes, int device, void* stream) {
+  if (n > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "azmi_resample_gather: n = %u: at most %u rows", n, kPlanMaxRows);
+  if (n_arrays > kGatherMaxArrays) return sfail(AZMI_ERR_INVALID, "azmi_resample_gather: %u arrays: at most %u per call", n_arrays, kGatherMaxArrays);
+  if (n_arrays && (!dev_in || !dev_out || !row_bytes)) return sfail(AZMI_ERR_INVALID, "azmi_resample_gather: null argument");
+  GatherArrays a{};
+  for (uint32_t k = 0; k < n_arrays; ++k) {
+    const uint32_t rb = row_bytes[k];
+    if (rb == 0 || rb % 4u) return sfail(AZMI_ERR_INVALID, "azmi_resample_gather: array %u: a row of %u bytes: rows are whole dwords", k, rb);
+    if (n && (!dev_in[k] || !dev_out[k])) return sfail(AZMI_ERR_INVALID, "azmi_resample_gather: array %u: null argument", k);
+    if (reinterpret_cast<uintptr_t>(dev_in[k]) % 4u || reinterpret_cast<uintptr_t>(dev_out[k]) % 4u)
+      return sfail(AZMI_ERR_INVALID, "azmi_resample_gather: array %u: the arrays are dword-aligned", k);
+    // the 16-byte path needs every row of both arrays on a 16-byte boundary
+    const bool vec = rb % 16u == 0 && reinterpret_cast<uintptr_t>(dev_in[k]) % 16u == 0 && reinterpret_cast<uintptr_t>(dev_out[k]) % 16u == 0;
+    a.in[k] = dev_in[k]; a.out[k] = dev_out[k];
+    a.vec[k] = vec ? 1 : 0;
+    a.units[k] = vec ? rb / 16u : rb / 4u;
+    uint32_t lanes = 1;
+    while (lanes < 64u && lanes < a.units[k]) lanes <<= 1;
+    a.lanes[k] = lanes;
+  }
+  if (n == 0 || n_arrays == 0) return AZMI_OK;
+  if (!dev_copies || !dev_offsets) return sfail(AZMI_ERR_INVALID, "azmi_resample_gather: null argument");
+  DeviceScope scope;
+  int rc = scope.enter("azmi_resample_gather", device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // grid.x covers the array with the widest groups (the fewest rows per workgroup); the others leave early
+  uint32_t max_lanes = 1;
+  for (uint32_t k = 0; k < n_arrays; ++k) max_lanes = a.lanes[k] > max_lanes ? a.lanes[k] : max_lanes;
+  const uint32_t rows_per_wg = kGatherThreads / max_lanes;
+  k_resample_gather<<<dim3((n + rows_per_wg - 1) / rows_per_wg, n_arrays), kGatherThreads, 0, st>>>(a, n, dev_copies, dev_offsets);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : hip_fail("k_resample_gather", e);
+}
+
+}  // extern "C"

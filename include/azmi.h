@@ -307,6 +307,44 @@ int azmi_tafl_symmetries(uint32_t board, uint32_t channels, uint32_t num_values,
                          float* out_pi, int host_buffers, void* stream);
 const char* azmi_symmetries_last_error(void);
 
+/* ---- per-row surprise loss and resample_by_surprise on the device (game_runner.py:1148-1255; sample_loss / sample_loss_pi /
+ *      sample_loss_v, neural_net.py:664-676, 875-879; csrc/samples_kernels.h).  Everything in float64 on the float32
+ *      inputs.  `dev_*` are DEVICE pointers; `stream` is a HIP stream or NULL; the message of a failed call is in
+ *      azmi_samples_last_error().  n == 0 is legal everywhere and touches no device; n > 2^30 is AZMI_ERR_INVALID.
+ *   sample_loss      dev_loss_out[i] = -scale * sum over m with target[i,m] > 0, of target[i,m] * log(max(p[i,m], FLT_MIN)), for two
+ *                    [n, M] float32 arrays, p holding PROBABILITIES (what azmi_net_forward writes; the reference's outputs are
+ *                    log-probabilities): sample_loss_pi at scale = 1, sample_loss_v at scale = cv.  A zero target contributes
+ *                    exactly 0 whatever p is; a negative target makes the row NaN.  A row's bits do not depend on n.  One launch,
+ *                    asynchronous.  M == 0 or M > 2^20 is AZMI_ERR_INVALID.
+ *   resample_plan    from dev_loss [n] f64: total_loss (a tree sum whose order is fixed by n alone: the same bits on every run and
+ *                    stream), nonfinite / first_nonfinite (the number of rows that are NaN or +-inf and the first of them,
+ *                    0xFFFFFFFF for none), and - unless dev_copies and dev_offsets are both NULL, which leaves the sums alone -
+ *                    dev_copies [n] u32, dev_offsets [n] u64 = the exclusive prefix sum of the copies, rows_out = their sum.
+ *                    total_loss <= 0: every count is 1.  Otherwise, every operation in float64 in this order:
+ *                      w = 0.5 + (loss[i] / total_loss) * 0.5 * n,  k = floor(w),  copies[i] = k + (u_i < w - k)
+ *                      u_i = (mix64(seed + 0x9E3779B97F4A7C15 * (i + 1)) >> 11) * 2^-53      (mix64: csrc/dev_rng.h; mod 2^64)
+ *                    (the weights and the rounding rule of game_runner.py:1189-1193; the draw is ours: the reference's comes from
+ *                    the global numpy state).  With nonfinite > 0 the counts are unspecified (each is a valid u32, their sum is
+ *                    rows_out).  Synchronises `stream` once, to hand back the record; the scratch block is kept per device between
+ *                    calls (no allocation in the steady state).  The thread's current device is left as it was (all three).
+ *   resample_gather  out[offsets[i] + c] = in[i] for c < copies[i], for the n_arrays <= 8 row arrays dev_in[k] -> dev_out[k] with
+ *                    rows of row_bytes[k] bytes (whole dwords; dev_in, dev_out, row_bytes are HOST arrays of n_arrays entries):
+ *                    x[np.repeat(np.arange(n), copies)].  dev_out[k] has room for rows_out rows.  Rows whose size and both base
+ *                    addresses are multiples of 16 move as 16-byte accesses, the others as dwords.  One launch, asynchronous. */
+typedef struct azmi_resample_record {
+  double total_loss;
+  uint64_t rows_out;
+  uint32_t nonfinite;
+  uint32_t first_nonfinite;
+} azmi_resample_record;
+int azmi_sample_loss(const float* dev_target, const float* dev_p, uint32_t n, uint32_t M, double scale, double* dev_loss_out, int device,
+                     void* stream);
+int azmi_resample_plan(const double* dev_loss, uint32_t n, uint64_t seed, uint32_t* dev_copies, uint64_t* dev_offsets,
+                       azmi_resample_record* host_record_out, int device, void* stream);
+int azmi_resample_gather(const uint32_t* dev_copies, const uint64_t* dev_offsets, uint32_t n, uint32_t n_arrays, const void* const* dev_in,
+                         void* const* dev_out, const uint32_t* row_bytes, int device, void* stream);
+const char* azmi_samples_last_error(void);
+
 /* ---- the stand-alone MCTS class (py_wrapper.cc:192-220, mcts.h:50-200): one search tree driven call by call.
  * All five games.  A GameState argument is passed as start position (`init`, NULL = initial position, else the
  * game's serialized image as in azmi_game_replay_from) + the moves played from it.  The object owns one pcg32
