@@ -30,7 +30,8 @@ from .drivers import (run_rounds, run_rounds_groups, pipeline_supported, pipelin
                       _pipe_stats, _PIPE_KEYS, pipeline_log_duplicates, cache_find_group, cache_insert_locked, rng_probe, tracy_is_enabled, tracy_frame_mark,
                       _tracy_zone_begin, _tracy_zone_end, _tracy_set_thread_name)
 from . import samples
-from .samples import sample_loss, resample_plan, resample_rows, resample_by_surprise, iteration_losses
+from .samples import (sample_loss, resample_plan, resample_rows, resample_by_surprise, iteration_losses, sample_metrics, plane_argmax,
+                      eval_metrics, analyze_samples)
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use

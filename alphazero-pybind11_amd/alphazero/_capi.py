@@ -110,6 +110,16 @@ class ResampleRecordC(C.Structure):      # azmi_resample_record
     _fields_ = [("total_loss", C.c_double), ("rows_out", C.c_uint64), ("nonfinite", C.c_uint32), ("first_nonfinite", C.c_uint32)]
 
 
+SAMPLE_METRIC_COLUMNS = 13      # AZMI_SAMPLE_METRIC_COLUMNS
+SAMPLE_METRIC_MAX_BUCKETS = 8   # AZMI_SAMPLE_METRIC_MAX_BUCKETS
+
+
+class SampleMetricsRecordC(C.Structure):      # azmi_sample_metrics_record
+    _fields_ = [("sum", C.c_double * SAMPLE_METRIC_COLUMNS * SAMPLE_METRIC_MAX_BUCKETS), ("total", C.c_double * SAMPLE_METRIC_COLUMNS),
+                ("count", C.c_uint32 * SAMPLE_METRIC_MAX_BUCKETS), ("nonfinite", C.c_uint32), ("first_nonfinite", C.c_uint32),
+                ("invalid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # every symbol include/azmi.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _PP = C.POINTER
@@ -184,6 +194,10 @@ SYMBOLS = {
     "azmi_resample_plan": (C.c_int, [_VP, C.c_uint32, C.c_uint64, _VP, _VP, _PP(ResampleRecordC), C.c_int, _VP]),
     "azmi_resample_gather": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _PP(_VP), _PP(_VP), _PP(C.c_uint32), C.c_int, _VP]),
     "azmi_samples_last_error": (C.c_char_p, []),
+    "azmi_sample_metrics": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _VP, C.c_uint64, _VP, _VP, C.c_int, _VP]),
+    "azmi_sample_plane_argmax": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           _VP, C.c_int, _VP]),
+    "azmi_sample_metrics_reduce": (C.c_int, [_VP, C.c_uint64, C.c_uint32, _VP, C.c_uint32, _PP(SampleMetricsRecordC), C.c_int, _VP]),
     "azmi_pm_net_forward": (C.c_int, [_VP, _VP, _VP]),
     "azmi_pm_net_forward_group": (C.c_int, [_VP, C.c_uint32, _VP, _VP]),
     "azmi_pm_groups": (C.c_int, [_VP, _PP(C.c_uint32), _PP(C.c_uint32)]),

@@ -5,15 +5,48 @@ behind it (NNWrapper.sample_loss, NNWrapper.losses, neural_net.py:644-676, 875-8
 Every function takes numpy arrays (staged through the device) or CUDA tensors (in place, nothing leaves the device but the plan's
 record) and answers in the kind it was given.  Argument errors are RuntimeErrors raised before any device call; inputs are
 contiguous float32 (the losses: float64) and are never converted silently.  torch is imported inside the functions: importing
-the package does not import it."""
+the package does not import it.
+
+Second half (azmi_sample_metrics / azmi_sample_plane_argmax / azmi_sample_metrics_reduce, csrc/sample_metrics_kernels.h): the
+per-row policy and value diagnostics of a net against the samples - sample_metrics, plane_argmax - and the two consumers the
+reference has for them: eval_metrics (network_pareto.eval_loss, network_pareto.py:652-738) and analyze_samples
+(game_runner._analyze_iteration_variants, game_runner.py:2509-2627)."""
 import ctypes as C
+import enum
 
 import numpy as np
 
-from ._capi import lib, ResampleRecordC
+from ._capi import lib, ResampleRecordC, SampleMetricsRecordC
 
 MAX_ROWS = 1 << 30
 MAX_ENTRIES = 1 << 20
+MAX_BUCKETS = 8
+MAX_PLANES = 16
+
+
+class Metric(enum.IntEnum):
+    """the float64 columns of sample_metrics: enum SampleMetric of csrc/sample_metrics_kernels.h"""
+    PI_LOSS = 0
+    V_LOSS = 1
+    TARGET_ENTROPY = 2
+    ENTROPY = 3
+    KL = 4
+    TOP1 = 5
+    NET_TOP1 = 6
+    NET_AT_MCTS = 7
+    TOP1_GAP = 8
+    TOP1_AGREE = 9
+    TOP3_OVERLAP = 10
+    V_PRED = 11
+    V_ACTUAL = 12
+
+
+METRIC_COLUMNS = tuple(m.name.lower() for m in Metric)
+INDEX_COLUMNS = ("mcts_argmax", "net_argmax")
+# the ten per-sample arrays of _analyze_iteration_variants (game_runner.py:2602-2613)
+ANALYSIS_KEYS = ("pi_loss", "v_loss", "entropy", "top1", "net_top1", "net_at_mcts", "top1_gap", "top1_agree", "v_pred", "v_actual")
+# the keys of network_pareto.eval_loss, and the row count
+EVAL_KEYS = ("v_loss", "v_loss_raw", "pi_loss", "total_loss", "top1_agree", "top3_agree", "kl_div", "target_entropy", "kl_gap", "count")
 
 
 def _call(rc):
@@ -358,3 +391,290 @@ def iteration_losses(samples, net, cv=1.0, batch_rows=65536, device=0, stream=No
                                "a NaN from the net, or a negative target")
         means.append(float(rec.total_loss) / n)
     return means[0], means[1]
+
+
+# ---- per-row diagnostics: sample_metrics, plane_argmax, eval_metrics, analyze_samples ------------------------------------------
+def _check_cv(what, cv):
+    try:
+        cv = float(cv)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{what}: cv must be a number, got {cv!r}") from None
+    if not np.isfinite(cv):
+        raise RuntimeError(f"{what}: cv must be finite, got {cv!r}")
+    return cv
+
+
+def _check_index(what, name, x):
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 0:
+        raise RuntimeError(f"{what}: {name} must be an integer >= 0, got {x!r}")
+    return int(x)
+
+
+def _launch_metrics(t_pi, p_pi, t_v, p_v, n, cv, cols, lo, mcts, net, stream):
+    """k_sample_metrics over n rows into the rows lo .. lo + n of the [13, N] float64 tensor `cols` and of the two index tensors"""
+    _call(lib.azmi_sample_metrics(t_pi.data_ptr(), p_pi.data_ptr(), t_v.data_ptr(), p_v.data_ptr(), n, int(t_pi.shape[1]), int(t_v.shape[1]),
+                                  cv, cols.data_ptr() + 8 * lo, int(cols.shape[1]), mcts.data_ptr() + 4 * lo, net.data_ptr() + 4 * lo,
+                                  cols.device.index, _stream_of(cols.device, stream)))
+
+
+def _metric_tensors(n, dev, stream):
+    import torch
+    return (_empty((len(Metric), n), torch.float64, dev, stream), _empty(n, torch.int32, dev, stream), _empty(n, torch.int32, dev, stream))
+
+
+def sample_metrics(pi_target, pi_p, v_target, v_p, cv=1.0, device=0, stream=None):
+    """The per-row diagnostics of a net's answers (pi_p [n, M], v_p [n, V]: PROBABILITIES, what HipLeafNet writes) against the samples'
+    targets (pi_target [n, M], v_target [n, V]), one launch that reads every element once (azmi_sample_metrics), float64 on the
+    float32 inputs.  -> {column: array [n]}: the thirteen float64 columns of Metric (METRIC_COLUMNS)
+
+        pi_loss         -sum over t > 0 of t * log(max(p, FLT_MIN))       sample_loss(pi_target, pi_p), bit for bit
+        v_loss          the same on the value rows at scale cv            sample_loss(v_target, v_p, scale=cv), bit for bit
+        target_entropy  -sum over t > 0 of t * log(t)                     (network_pareto.py:716)
+        entropy         -sum over all m of t * log(t + 1e-9)              (game_runner.py:2562)
+        kl              sum over t > 0 of t * log(t / (p + 1e-10))        (network_pareto.py:713)
+        top1, net_top1  max t, max p            net_at_mcts  p[mcts_argmax]            top1_gap  top1 - net_at_mcts
+        top1_agree      1.0 when net_argmax == mcts_argmax, else 0.0
+        top3_overlap    |top3(p) & top3(t)|, 0..3 (M < 3: the sets have M members)
+        v_pred, v_actual  v_p[:, 0], v_target[:, 0]
+
+    and the uint32 columns mcts_argmax and net_argmax (CUDA tensors: int32 with the same bits).  Ties in every argmax and top-3
+    go to the LOWER index (np.argmax; the first three of np.argsort(-x, kind="stable"); pib.max(dim=1) on the reference's CPU path) -
+    unlike policy_divergences and sweep_metrics, where the higher index wins as in policy_metrics.py.  A negative target is NOT
+    an error here, on either path: it makes the sums of its row NaN (pi_loss, target_entropy, entropy, kl; v_loss for a value
+    target); a NaN probability makes NaN what reads it (pi_loss and kl under a positive target, net_top1, net_at_mcts and top1_gap at
+    the target's argmax); the index columns of such a row are unspecified but < M.  numpy arrays are staged on `device`; CUDA
+    tensors are used in place on `stream` with no synchronisation (the columns are the rows of one [13, n] tensor).  n == 0 touches
+    no device."""
+    what = "sample_metrics"
+    named = (("pi_target", pi_target), ("pi_p", pi_p), ("v_target", v_target), ("v_p", v_p))
+    kind = _kind(what, named)
+    shapes = [tuple(x.shape) for _, x in named]
+    if any(len(s) != 2 for s in shapes):
+        raise RuntimeError(f"{what}: pi_target and pi_p must be [n, M] arrays, v_target and v_p [n, V] arrays, got shapes "
+                           + ", ".join(str(s) for s in shapes))
+    if shapes[0] != shapes[1]:
+        raise RuntimeError(f"{what}: pi_target and pi_p must have one shape, got {shapes[0]} and {shapes[1]}")
+    if shapes[2] != shapes[3]:
+        raise RuntimeError(f"{what}: v_target and v_p must have one shape, got {shapes[2]} and {shapes[3]}")
+    if shapes[0][0] != shapes[2][0]:
+        raise RuntimeError(f"{what}: the policy and the value arrays must hold one row per sample, got {shapes[0][0]} and {shapes[2][0]} rows")
+    (n, M), V = shapes[0], shapes[2][1]
+    if not 1 <= M <= MAX_ENTRIES or not 1 <= V <= MAX_ENTRIES:
+        raise RuntimeError(f"{what}: M and V must be in [1, 2^20], got M = {M} and V = {V}")
+    _check_rows(what, n)
+    for name, x in named:
+        _check_dtype(what, name, x, "float32")
+    cv = _check_cv(what, cv)
+    if kind == "numpy":
+        device = _check_device(what, device)
+        if n == 0:
+            out = {name: np.zeros(0, np.float64) for name in METRIC_COLUMNS}
+            out.update({name: np.zeros(0, np.uint32) for name in INDEX_COLUMNS})
+            return out
+        pi_target, pi_p, v_target, v_p = (_stage(x, device) for _, x in named)
+    cols, mcts, net = _metric_tensors(n, pi_target.device, stream)
+    if n:
+        _launch_metrics(pi_target, pi_p, v_target, v_p, n, cv, cols, 0, mcts, net, stream)
+    if kind == "numpy":
+        host = cols.cpu().numpy()
+        out = {name: host[k] for k, name in enumerate(METRIC_COLUMNS)}
+        out["mcts_argmax"], out["net_argmax"] = mcts.cpu().numpy().view(np.uint32), net.cpu().numpy().view(np.uint32)
+        return out
+    out = {name: cols[k] for k, name in enumerate(METRIC_COLUMNS)}
+    out["mcts_argmax"], out["net_argmax"] = mcts, net
+    return out
+
+
+def plane_argmax(canonical, first_plane, n_planes, row, col, device=0, stream=None):
+    """The lower-index argmax over the planes first_plane .. first_plane + n_planes - 1 (1 to 16 planes) of canonical [n, C, H, W] at
+    the cell (row, col) (azmi_sample_plane_argmax): canonical[:, first_plane:first_plane + n_planes, row, col].argmax(1).
+    -> uint8 [n], numpy for numpy (staged on `device`), a CUDA tensor for a CUDA tensor (on `stream`, no synchronisation).
+    [n, NS, C, H, W] is read as n * NS rows.  plane_argmax(canonical, 32, 4, 6, 6) is the variant id of the unified StarGambit
+    encoding (game_runner.py:2535)."""
+    what = "plane_argmax"
+    kind = _kind(what, (("canonical", canonical),))
+    shape = tuple(canonical.shape)
+    if len(shape) < 4:
+        raise RuntimeError(f"{what}: canonical must be an [n, C, H, W] array, got shape {shape}")
+    n = int(np.prod(shape[:-3], dtype=np.int64))
+    Cn, H, W = shape[-3:]
+    _check_rows(what, n)
+    if min(Cn, H, W) < 1 or Cn * H * W >= 1 << 30:
+        raise RuntimeError(f"{what}: canonical: a row of {Cn} x {H} x {W}: rows hold 1 to 2^30 - 1 float32")
+    _check_dtype(what, "canonical", canonical, "float32")
+    first_plane, n_planes = _check_index(what, "first_plane", first_plane), _check_index(what, "n_planes", n_planes)
+    row, col = _check_index(what, "row", row), _check_index(what, "col", col)
+    if not 1 <= n_planes <= MAX_PLANES:
+        raise RuntimeError(f"{what}: n_planes must be in [1, {MAX_PLANES}], got {n_planes}")
+    if first_plane + n_planes > Cn:
+        raise RuntimeError(f"{what}: the planes {first_plane} .. {first_plane + n_planes - 1} are outside the {Cn} planes of canonical")
+    if row >= H or col >= W:
+        raise RuntimeError(f"{what}: the cell ({row}, {col}) is outside the {H} x {W} board")
+    if kind == "numpy":
+        device = _check_device(what, device)
+        if n == 0:
+            return np.zeros(0, np.uint8)
+        canonical = _stage(canonical, device)
+    import torch
+    out = _empty(n, torch.uint8, canonical.device, stream)
+    if n:
+        _call(lib.azmi_sample_plane_argmax(canonical.data_ptr(), n, Cn, H, W, first_plane, n_planes, row, col, out.data_ptr(),
+                                           canonical.device.index, _stream_of(canonical.device, stream)))
+    return out.cpu().numpy() if kind == "numpy" else out
+
+
+def _check_buckets(what, sample_arrays, n, buckets, n_buckets, names):
+    """-> (n_buckets or None without buckets, names)"""
+    if buckets is None:
+        if n_buckets is not None or names is not None:
+            raise RuntimeError(f"{what}: n_buckets and names go with buckets, which is None")
+        return None, None
+    _kind(what, tuple(sample_arrays) + (("buckets", buckets),))
+    if len(buckets.shape) != 1 or int(buckets.shape[0]) != n:
+        raise RuntimeError(f"{what}: buckets must hold one id per sample ({n}), got shape {tuple(buckets.shape)}")
+    _check_dtype(what, "buckets", buckets, "uint8")
+    if names is not None:
+        names = list(names)
+        if any(not isinstance(x, str) for x in names) or len(set(names)) != len(names) or "overall" in names:
+            raise RuntimeError(f'{what}: names must be distinct strings other than "overall", got {names!r}')
+    if n_buckets is None:
+        if names is None:
+            raise RuntimeError(f"{what}: with buckets, give n_buckets or names")
+        n_buckets = len(names)
+    if isinstance(n_buckets, bool) or not isinstance(n_buckets, (int, np.integer)) or not 1 <= n_buckets <= MAX_BUCKETS:
+        raise RuntimeError(f"{what}: n_buckets must be an integer in [1, {MAX_BUCKETS}], got {n_buckets!r}")
+    n_buckets = int(n_buckets)
+    if names is None:
+        names = [str(b) for b in range(n_buckets)]
+    if len(names) != n_buckets:
+        raise RuntimeError(f"{what}: {len(names)} names for {n_buckets} buckets")
+    return n_buckets, names
+
+
+def _net_metrics(net, c, v, pi, n, batch_rows, cv, stream):
+    """the net over the samples in chunks of batch_rows into one reused scratch (as _net_losses), one k_sample_metrics launch per chunk
+    -> (columns [13, n] float64, mcts_argmax [n], net_argmax [n] int32), CUDA tensors"""
+    import torch
+    B = max(1, min(int(batch_rows), n))
+    v_s = _empty((B, v.shape[1]), torch.float32, c.device, stream)
+    pi_s = _empty((B, pi.shape[1]), torch.float32, c.device, stream)
+    st = torch.cuda.current_stream(c.device).cuda_stream if stream is None else int(stream)
+    cols, mcts, net_idx = _metric_tensors(n, c.device, stream)
+    for lo in range(0, n, B):
+        hi = min(n, lo + B)
+        net.forward(c[lo:hi], v_s[:hi - lo], pi_s[:hi - lo], stream=st)
+        _launch_metrics(pi[lo:hi], pi_s[:hi - lo], v[lo:hi], v_s[:hi - lo], hi - lo, cv, cols, lo, mcts, net_idx, st)
+    return cols, mcts, net_idx
+
+
+def _reduce(cols, n, buckets_t, n_buckets, stream):
+    """azmi_sample_metrics_reduce on the [13, N] columns -> the record"""
+    rec = SampleMetricsRecordC()
+    _call(lib.azmi_sample_metrics_reduce(cols.data_ptr(), int(cols.shape[1]), n, None if buckets_t is None else buckets_t.data_ptr(),
+                                         1 if buckets_t is None else n_buckets, C.byref(rec), cols.device.index, _stream_of(cols.device, stream)))
+    return rec
+
+
+def _eval_dict(sums, count, cv):
+    """the figures of network_pareto.eval_loss (network_pareto.py:720-738) from the column sums of `count` rows"""
+    if count == 0:
+        return dict({k: float("nan") for k in EVAL_KEYS}, count=0)
+    mean = lambda m: float(sums[m]) / count
+    v_loss, pi_loss, target_entropy = mean(Metric.V_LOSS), mean(Metric.PI_LOSS), mean(Metric.TARGET_ENTROPY)
+    return {"v_loss": v_loss, "v_loss_raw": v_loss / cv if cv else float("nan"), "pi_loss": pi_loss, "total_loss": v_loss + pi_loss,
+            "top1_agree": mean(Metric.TOP1_AGREE), "top3_agree": float(sums[Metric.TOP3_OVERLAP]) / (3 * count), "kl_div": mean(Metric.KL),
+            "target_entropy": target_entropy, "kl_gap": pi_loss - target_entropy, "count": int(count)}
+
+
+def eval_metrics(samples, net, cv=1.0, batch_rows=65536, buckets=None, n_buckets=None, names=None, device=0, stream=None):
+    """network_pareto.eval_loss (network_pareto.py:652-738) on the device: the held-out metric set of `net` (a HipLeafNet) over
+    `samples` (the (canonical, v, pi) triple of self_play() or of symmetries_batch()).  The net runs over chunks of `batch_rows` rows
+    into one reused scratch, one k_sample_metrics launch per chunk writes the [13, n] columns, one bucketed reduction sums them.
+    -> {"v_loss", "v_loss_raw" (= v_loss / cv), "pi_loss", "total_loss", "top1_agree", "top3_agree" (= sum of top3_overlap / (3 n)),
+    "kl_div", "target_entropy", "kl_gap" (= pi_loss - target_entropy), "count"}.  With `buckets` (uint8 [n], ids below `n_buckets`
+    <= 8, default len(names); `names` default "0", "1", ...): {name: that dict} over the non-empty buckets, and "overall".
+    The means are float64 per-sample means; the reference takes the mean of float32 batch means, the same figure when all batches
+    have one size.  No AMP: the net's own precision tier decides.  One host synchronisation, the reduction's record.  Raises
+    RuntimeError naming the first row whose loss, entropy or kl is NaN or infinite, and when a bucket id is >= n_buckets.  No samples:
+    every figure is NaN and count is 0."""
+    what = "eval_metrics"
+    kind, n, c, v, pi = _check_samples(what, samples, batch_rows)
+    cv = _check_cv(what, cv)
+    if not hasattr(net, "forward"):
+        raise RuntimeError(f"{what}: net must be a HipLeafNet, got {type(net).__name__}")
+    B, names = _check_buckets(what, (("canonical", c), ("v", v), ("pi", pi)), n, buckets, n_buckets, names)
+    if kind == "numpy":
+        device = _check_device(what, device)
+    if n == 0:
+        return _eval_dict(None, 0, cv) if B is None else {"overall": _eval_dict(None, 0, cv)}
+    if kind == "numpy":
+        c, v, pi = _stage(c, device), _stage(v, device), _stage(pi, device)
+        buckets = None if B is None else _stage(buckets, device)
+    cols, _, _ = _net_metrics(net, c, v, pi, n, batch_rows, cv, stream)
+    rec = _reduce(cols, n, buckets, B, stream)
+    if rec.nonfinite:
+        raise RuntimeError(f"{what}: {rec.nonfinite} of {n} samples have a loss, entropy or kl that is not finite, the first at row "
+                           f"{rec.first_nonfinite} (first_nonfinite): a NaN from the net, or a negative target")
+    if rec.invalid:
+        raise RuntimeError(f"{what}: {rec.invalid} of {n} bucket ids are >= n_buckets = {B}")
+    overall = _eval_dict(rec.total, n, cv)
+    if B is None:
+        return overall
+    out = {names[b]: _eval_dict(rec.sum[b], rec.count[b], cv) for b in range(B) if rec.count[b]}
+    out["overall"] = overall
+    return out
+
+
+def analyze_samples(samples, net, cv=1.0, batch_rows=65536, buckets=None, names=None, device=0, stream=None):
+    """game_runner._analyze_iteration_variants (game_runner.py:2509-2627) on the device: the per-sample arrays "pi_loss", "v_loss",
+    "entropy", "top1", "net_top1", "net_at_mcts", "top1_gap", "top1_agree", "v_pred", "v_actual" of `net` over `samples` (float64 columns
+    of sample_metrics), split by bucket.  -> {"overall": {key: array [n]}} without `buckets`; with `buckets` (uint8 [n]) and `names`
+    (default "0", "1", ... up to the largest id) {name: {key: array of the bucket's rows}} over the non-empty buckets, as the
+    reference returns per variant.  numpy samples give numpy arrays, CUDA tensors give CUDA tensors.  The split is boolean-mask
+    indexing (it synchronises); the reference's sample loading and checkpoint loading stay with the caller."""
+    what = "analyze_samples"
+    kind, n, c, v, pi = _check_samples(what, samples, batch_rows)
+    cv = _check_cv(what, cv)
+    if not hasattr(net, "forward"):
+        raise RuntimeError(f"{what}: net must be a HipLeafNet, got {type(net).__name__}")
+    if buckets is None and names is not None:
+        raise RuntimeError(f"{what}: names go with buckets, which is None")
+    if buckets is not None:
+        _kind(what, (("canonical", c), ("v", v), ("pi", pi), ("buckets", buckets)))
+        if len(buckets.shape) != 1 or int(buckets.shape[0]) != n:
+            raise RuntimeError(f"{what}: buckets must hold one id per sample ({n}), got shape {tuple(buckets.shape)}")
+        _check_dtype(what, "buckets", buckets, "uint8")
+        if names is not None:
+            names = list(names)
+            if any(not isinstance(x, str) for x in names) or len(set(names)) != len(names):
+                raise RuntimeError(f"{what}: names must be distinct strings, got {names!r}")
+    if kind == "numpy":
+        device = _check_device(what, device)
+    if n == 0:
+        empty = {k: np.zeros(0, np.float64) for k in ANALYSIS_KEYS} if kind == "numpy" else None
+        if empty is None:
+            import torch
+            empty = {k: torch.empty(0, dtype=torch.float64, device=c.device) for k in ANALYSIS_KEYS}
+        return {"overall": empty} if buckets is None else {}
+    if kind == "numpy":
+        c, v, pi = _stage(c, device), _stage(v, device), _stage(pi, device)
+    cols, _, _ = _net_metrics(net, c, v, pi, n, batch_rows, cv, stream)
+    if stream is not None:
+        import torch
+        torch.cuda.ExternalStream(int(stream), device=cols.device).synchronize()      # the indexing below runs on the current stream
+    if kind == "numpy":
+        cols = cols.cpu().numpy()
+    if buckets is None:
+        return {"overall": {k: cols[Metric[k.upper()]] for k in ANALYSIS_KEYS}}
+    top = int(buckets.max()) + 1
+    if names is None:
+        names = [str(b) for b in range(top)]
+    if top > len(names):
+        raise RuntimeError(f"{what}: a bucket id {top - 1} with {len(names)} names")
+    out = {}
+    for b, name in enumerate(names):
+        mask = buckets == b
+        if not bool(mask.any()):
+            continue
+        out[name] = {k: cols[Metric[k.upper()]][mask] for k in ANALYSIS_KEYS}
+    return out

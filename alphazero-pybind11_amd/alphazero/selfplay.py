@@ -205,6 +205,32 @@ def process_samples(game, samples, net, seed, **kwargs):
     return resample_by_surprise(samples, net, seed, **kwargs)
 
 
+UNIFIED_VARIANT_NAMES = ("skirmish", "showdown", "clash", "battle")      # game_runner.py:37
+
+
+def variant_buckets(game, canonical, **kwargs):
+    """The variant of every sample of a unified StarGambit game, read from its canonical planes: (ids, names) with ids =
+    plane_argmax(canonical, 32, 4, 6, 6) (uint8 [n]: the one-hot planes 32..35 at the centre cell, star_gambit_gs.cc:2604-2610;
+    game_runner.py:2535) and the four variant names; None for every other game.  The keywords are plane_argmax's."""
+    from .games import StarGambitUnifiedGS
+    from .samples import plane_argmax
+    cls = game if isinstance(game, type) else type(game)
+    if not issubclass(cls, StarGambitUnifiedGS):
+        return None
+    return plane_argmax(canonical, 32, 4, 6, 6, **kwargs), UNIFIED_VARIANT_NAMES
+
+
+def analyze_iteration(game, samples, net, **kwargs):
+    """game_runner._analyze_iteration_variants on the samples where self_play leaves them: analyze_samples, split by variant for a
+    unified StarGambit game (variant_buckets) and one "overall" bucket for every other game; the keywords are analyze_samples'."""
+    from .samples import analyze_samples, _check_samples
+    _, n, canonical, _, _ = _check_samples("analyze_iteration", samples, kwargs.get("batch_rows", 65536))
+    split = variant_buckets(game, canonical, **{k: kwargs[k] for k in ("device", "stream") if k in kwargs}) if n else None
+    if split is None:
+        return analyze_samples(samples, net, **kwargs)
+    return analyze_samples(samples, net, buckets=split[0], names=split[1], **kwargs)
+
+
 def _pipeline_step(call, state, driver, what):
     """One call of the asynchronous pipeline under the error contract of include/azmi.h: a "pipeline error mask" error (a spin that hit
     the stall cap: the host was held up between the launches, another tenant took CUs) leaves the engine whole and the call is simply

@@ -1,6 +1,8 @@
 // Per-row surprise loss, resample plan and row gather on the device: the host side of samples_kernels.h.
 // azmi_sample_loss / azmi_resample_plan / azmi_resample_gather take DEVICE pointers and a stream; only the plan synchronises,
 // once, to hand back its record (the caller needs rows_out to size the gather's outputs).
+// Likewise the per-row diagnostics of sample_metrics_kernels.h: azmi_sample_metrics and azmi_sample_plane_argmax are one
+// asynchronous launch each, azmi_sample_metrics_reduce synchronises once for its record.
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -11,11 +13,14 @@
 
 #include "../../include/azmi.h"
 #include "samples_kernels.h"
+#include "sample_metrics_kernels.h"
 
 namespace {
 using namespace azmi;
 
 static_assert(sizeof(ResampleRecord) == sizeof(azmi_resample_record), "azmi_resample_record is the device record");
+static_assert(sizeof(SampleMetricsRecord) == sizeof(azmi_sample_metrics_record), "azmi_sample_metrics_record is the device record");
+static_assert(kSampleMetricColumns == AZMI_SAMPLE_METRIC_COLUMNS && kMetricMaxBuckets == AZMI_SAMPLE_METRIC_MAX_BUCKETS, "the header's sizes");
 
 thread_local std::string g_samples_err;
 
@@ -58,7 +63,12 @@ struct PlanScratch { void* block; size_t bytes; };
 std::mutex g_plan_mutex;
 PlanScratch g_plan_scratch[kPlanMaxDevices];
 
+PlanScratch g_metrics_scratch[kPlanMaxDevices];      // the same for azmi_sample_metrics_reduce, under the same mutex
+
 uint32_t tiles_of(uint32_t n) { return (n + kPlanBlock - 1) / kPlanBlock; }
+
+// the lane group k_sample_loss gives a row of `entries` entries
+int lanes_of(uint32_t entries) { return entries <= 8 ? 8 : entries <= 16 ? 16 : entries <= 32 ? 32 : 64; }
 
 }  // namespace
 
@@ -174,6 +184,110 @@ int azmi_resample_gather(const uint32_t* dev_copies, const uint64_t* dev_offsets
   k_resample_gather<<<dim3((n + rows_per_wg - 1) / rows_per_wg, n_arrays), kGatherThreads, 0, st>>>(a, n, dev_copies, dev_offsets);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? AZMI_OK : hip_fail("k_resample_gather", e);
+}
+
+int azmi_sample_metrics(const float* dev_target_pi, const float* dev_p_pi, const float* dev_target_v, const float* dev_p_v, uint32_t n,
+                        uint32_t M, uint32_t V, double cv, double* dev_cols_out, uint64_t col_stride, uint32_t* dev_mcts_argmax_out,
+                        uint32_t* dev_net_argmax_out, int device, void* stream) {
+  if (n > kPlanMaxRows || M == 0 || M > (1u << 20) || V == 0 || V > (1u << 20))
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics: n = %u, M = %u, V = %u: at most %u rows of 1 to %u entries", n, M, V, kPlanMaxRows,
+                 1u << 20);
+  if (col_stride < n)
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics: col_stride = %llu: a column holds at least n = %u rows",
+                 static_cast<unsigned long long>(col_stride), n);
+  if (n == 0) return AZMI_OK;
+  if (!dev_target_pi || !dev_p_pi || !dev_target_v || !dev_p_v || !dev_cols_out || !dev_mcts_argmax_out || !dev_net_argmax_out)
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics: null argument");
+  DeviceScope scope;
+  int rc = scope.enter("azmi_sample_metrics", device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // a row's group: the larger of the groups k_sample_loss gives the policy row and the value row
+  const int lm = lanes_of(M), lv = lanes_of(V), g = lm > lv ? lm : lv;
+#define AZMI_METRICS_LAUNCH(G)                                                                                                          \
+  k_sample_metrics<G><<<(n + kMetricThreads / G - 1) / (kMetricThreads / G), kMetricThreads, 0, st>>>(                                  \
+      dev_target_pi, dev_p_pi, dev_target_v, dev_p_v, n, M, V, lm, lv, cv, dev_cols_out, col_stride, dev_mcts_argmax_out, dev_net_argmax_out)
+  if (g == 8) AZMI_METRICS_LAUNCH(8);
+  else if (g == 16) AZMI_METRICS_LAUNCH(16);
+  else if (g == 32) AZMI_METRICS_LAUNCH(32);
+  else AZMI_METRICS_LAUNCH(64);
+#undef AZMI_METRICS_LAUNCH
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : hip_fail("k_sample_metrics", e);
+}
+
+int azmi_sample_plane_argmax(const float* dev_canonical, uint32_t n, uint32_t C, uint32_t H, uint32_t W, uint32_t first_plane,
+                             uint32_t n_planes, uint32_t row, uint32_t col, uint8_t* dev_out, int device, void* stream) {
+  if (n > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "azmi_sample_plane_argmax: n = %u: at most %u rows", n, kPlanMaxRows);
+  if (C == 0 || H == 0 || W == 0 || uint64_t(C) * H * W >= (1ull << 30))
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_plane_argmax: a row of %u x %u x %u: rows hold 1 to 2^30 - 1 float32", C, H, W);
+  if (n_planes == 0 || n_planes > 16 || first_plane >= C || n_planes > C - first_plane)
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_plane_argmax: planes %u .. %u + %u of %u: 1 to 16 planes inside the row", first_plane,
+                 first_plane, n_planes, C);
+  if (row >= H || col >= W) return sfail(AZMI_ERR_INVALID, "azmi_sample_plane_argmax: cell (%u, %u) outside the %u x %u board", row, col, H, W);
+  if (n == 0) return AZMI_OK;
+  if (!dev_canonical || !dev_out) return sfail(AZMI_ERR_INVALID, "azmi_sample_plane_argmax: null argument");
+  DeviceScope scope;
+  int rc = scope.enter("azmi_sample_plane_argmax", device); if (rc) return rc;
+  const uint64_t plane = uint64_t(H) * W;
+  k_sample_plane_argmax<<<(n + kMetricThreads - 1) / kMetricThreads, kMetricThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      dev_canonical, n, plane * C, plane, plane * first_plane + uint64_t(row) * W + col, n_planes, dev_out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : hip_fail("k_sample_plane_argmax", e);
+}
+
+int azmi_sample_metrics_reduce(const double* dev_cols, uint64_t col_stride, uint32_t n, const uint8_t* dev_bucket, uint32_t n_buckets,
+                               azmi_sample_metrics_record* host_record_out, int device, void* stream) {
+  if (!host_record_out) return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics_reduce: null argument");
+  *host_record_out = azmi_sample_metrics_record{};
+  host_record_out->first_nonfinite = kPlanNone;
+  if (n > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics_reduce: n = %u: at most %u rows", n, kPlanMaxRows);
+  if (n_buckets == 0 || n_buckets > kMetricMaxBuckets)
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics_reduce: n_buckets = %u: 1 to %u buckets", n_buckets, kMetricMaxBuckets);
+  if (!dev_bucket && n_buckets != 1)
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics_reduce: n_buckets = %u without a bucket array: every row is in bucket 0", n_buckets);
+  if (col_stride < n)
+    return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics_reduce: col_stride = %llu: a column holds at least n = %u rows",
+                 static_cast<unsigned long long>(col_stride), n);
+  if (n == 0) return AZMI_OK;
+  if (!dev_cols) return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics_reduce: null argument");
+  if (device >= kPlanMaxDevices) return sfail(AZMI_ERR_INVALID, "azmi_sample_metrics_reduce: device %d: at most %d devices", device, kPlanMaxDevices);
+  DeviceScope scope;
+  int rc = scope.enter("azmi_sample_metrics_reduce", device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // one block: the record | per (bucket, column) pair the tile sums of the first and of the second level
+  const bool has_all = dev_bucket != nullptr;
+  const uint32_t pairs = (n_buckets + (has_all ? 1u : 0u)) * kSampleMetricColumns;
+  const uint32_t t0 = tiles_of(n), t1 = tiles_of(t0);      // t1 <= 1024: the level above it is one tile
+  const size_t bytes = sizeof(SampleMetricsRecord) + 8 * size_t(pairs) * (size_t(t0) + t1);
+  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  PlanScratch& sc = g_metrics_scratch[device];
+  hipError_t e = hipSuccess;
+  if (sc.bytes < bytes) {      // first call on this device, or a larger one than any before
+    if (sc.block) (void)hipFree(sc.block);
+    sc.block = nullptr; sc.bytes = 0;
+    e = hipMalloc(&sc.block, bytes);
+    if (e != hipSuccess) { sc.block = nullptr; return hip_fail("azmi_sample_metrics_reduce", e); }
+    sc.bytes = bytes;
+  }
+  SampleMetricsRecord* rec = static_cast<SampleMetricsRecord*>(sc.block);
+  double* sum0 = reinterpret_cast<double*>(rec + 1);
+  double* sum1 = sum0 + size_t(pairs) * t0;
+  e = hipMemsetAsync(rec, 0, sizeof *rec, st);
+  if (e == hipSuccess) e = hipMemsetAsync(&rec->first_nonfinite, 0xFF, 4, st);
+  if (e == hipSuccess) {
+    k_metrics_sum<<<dim3(t0, pairs), kPlanBlock, 0, st>>>(dev_cols, col_stride, n, dev_bucket, n_buckets, sum0, rec);
+    if (t0 > 1) k_metrics_sum_up<<<dim3(t1, pairs), kPlanBlock, 0, st>>>(sum0, t0, n_buckets, has_all, sum1, rec);
+    if (t1 > 1) k_metrics_sum_up<<<dim3(1, pairs), kPlanBlock, 0, st>>>(sum1, t1, n_buckets, has_all, nullptr, rec);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_record_out, rec, sizeof *rec, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);      // the one synchronisation; always: what was queued uses the block the next call reuses
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail("azmi_sample_metrics_reduce", e);
+  if (!has_all) {      // one bucket of every row: it is the overall figure too
+    for (uint32_t c = 0; c < kSampleMetricColumns; ++c) host_record_out->total[c] = host_record_out->sum[0][c];
+  }
+  return AZMI_OK;
 }
 
 }  // extern "C"

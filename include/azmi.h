@@ -345,6 +345,58 @@ int azmi_resample_gather(const uint32_t* dev_copies, const uint64_t* dev_offsets
                          void* const* dev_out, const uint32_t* row_bytes, int device, void* stream);
 const char* azmi_samples_last_error(void);
 
+/* ---- per-row policy and value diagnostics of a net against the samples, and their bucketed sums (network_pareto.eval_loss,
+ *      network_pareto.py:652-738; _analyze_iteration_variants, game_runner.py:2509-2627; csrc/sample_metrics_kernels.h, DESIGN.md
+ *      §8.5).  The conventions of the block above: float64 on the float32 inputs, DEVICE pointers, `stream` a HIP stream or NULL,
+ *      the message of a failed call in azmi_samples_last_error(), argument errors are AZMI_ERR_INVALID before any device call,
+ *      n == 0 is legal and touches no device, n <= 2^30, 1 <= M, V <= 2^20, the thread's current device is left as it was.
+ *   sample_metrics   one launch over target_pi / p_pi [n, M] and target_v / p_v [n, V] (p: PROBABILITIES), every element read
+ *                    once.  Per row i it writes the 13 float64 columns dev_cols_out[c * col_stride + i] (col_stride >= n; c:
+ *                    SampleMetric of csrc/sample_metrics_kernels.h = alphazero.samples.Metric) and two u32:
+ *                       0 pi_loss         -sum over t > 0 of t * log(max(p, FLT_MIN))      = azmi_sample_loss at scale 1, bit for bit
+ *                       1 v_loss          the same on the value rows, times cv             = azmi_sample_loss at scale cv, bit for bit
+ *                       2 target_entropy  -sum over t > 0 of t * log(t)
+ *                       3 entropy         -sum over all m of t * log(t + 1e-9)
+ *                       4 kl              sum over t > 0 of t * log(t / (p + 1e-10))
+ *                       5 top1            max_m t            6 net_top1     max_m p        7 net_at_mcts  p[mcts_argmax]
+ *                       8 top1_gap        top1 - net_at_mcts 9 top1_agree   1.0 when net_argmax == mcts_argmax, else 0.0
+ *                      10 top3_overlap    |top3(p) & top3(t)|, 0..3 (M < 3: the sets have M members)
+ *                      11 v_pred          p_v[i, 0]         12 v_actual     target_v[i, 0]
+ *                      dev_mcts_argmax_out[i], dev_net_argmax_out[i]: the argmax of the target and of the net's row.
+ *                    Ties in every argmax and top-3 go to the LOWER index (np.argmax, a stable argsort of -x) - NOT the rule of
+ *                    azmi_policy_divergences / sweep_metrics, where the higher index wins.  A negative target makes the sums of
+ *                    its row NaN (policy: columns 0, 2, 3, 4; value: column 1); a NaN probability makes NaN what reads it
+ *                    (pi_loss and kl under a positive target, net_top1 anywhere in the row, net_at_mcts and top1_gap at the
+ *                    target's argmax); the index columns of such a row are unspecified but < M.  A row's bits do not depend on n.
+ *   sample_plane_argmax  dev_out[i] (u8) = the lower-index argmax over the planes first_plane .. first_plane + n_planes - 1
+ *                    (1 <= n_planes <= 16, inside C) of dev_canonical [n, C, H, W] at cell (row, col): the variant id of the
+ *                    unified StarGambit encoding is (32, 4, 6, 6).  One launch, asynchronous.
+ *   sample_metrics_reduce  sum[b][c] = the float64 sum of column c over the rows with dev_bucket[i] == b (u8 [n]; NULL with
+ *                    n_buckets == 1: every row is in bucket 0), 1 <= n_buckets <= 8, count[b] the rows of bucket b, total[c] the sum
+ *                    over every row.  The tile tree of resample_plan (tiles of 1024, a row outside the bucket enters as +0.0): the
+ *                    bits of a sum depend on n and on which rows belong, on nothing else.  nonfinite / first_nonfinite: the rows
+ *                    with a NaN or +-inf in one of the columns 0..4 and the first of them (0xFFFFFFFF for none); invalid: the rows
+ *                    whose id is >= n_buckets, which belong to no bucket (total[] holds them).  One launch per level (at most
+ *                    three); synchronises `stream` once, to hand back the record; the scratch block is kept per device. */
+#define AZMI_SAMPLE_METRIC_COLUMNS 13
+#define AZMI_SAMPLE_METRIC_MAX_BUCKETS 8
+typedef struct azmi_sample_metrics_record {
+  double sum[AZMI_SAMPLE_METRIC_MAX_BUCKETS][AZMI_SAMPLE_METRIC_COLUMNS];
+  double total[AZMI_SAMPLE_METRIC_COLUMNS];
+  uint32_t count[AZMI_SAMPLE_METRIC_MAX_BUCKETS];
+  uint32_t nonfinite;
+  uint32_t first_nonfinite;
+  uint32_t invalid;
+  uint32_t reserved;
+} azmi_sample_metrics_record;
+int azmi_sample_metrics(const float* dev_target_pi, const float* dev_p_pi, const float* dev_target_v, const float* dev_p_v, uint32_t n,
+                        uint32_t M, uint32_t V, double cv, double* dev_cols_out, uint64_t col_stride, uint32_t* dev_mcts_argmax_out,
+                        uint32_t* dev_net_argmax_out, int device, void* stream);
+int azmi_sample_plane_argmax(const float* dev_canonical, uint32_t n, uint32_t C, uint32_t H, uint32_t W, uint32_t first_plane,
+                             uint32_t n_planes, uint32_t row, uint32_t col, uint8_t* dev_out, int device, void* stream);
+int azmi_sample_metrics_reduce(const double* dev_cols, uint64_t col_stride, uint32_t n, const uint8_t* dev_bucket, uint32_t n_buckets,
+                               azmi_sample_metrics_record* host_record_out, int device, void* stream);
+
 /* ---- the stand-alone MCTS class (py_wrapper.cc:192-220, mcts.h:50-200): one search tree driven call by call.
  * All five games.  A GameState argument is passed as start position (`init`, NULL = initial position, else the
  * game's serialized image as in azmi_game_replay_from) + the moves played from it.  The object owns one pcg32
