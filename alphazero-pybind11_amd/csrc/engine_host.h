@@ -6,7 +6,12 @@
 //   mcts_object.hip   the stand-alone MCTS object (azmi_mcts_*) on a one-slot engine; host code only
 //   replay.hip        rules replay, playout evaluation, StarGambit images and the RNG probe; host code only
 //   pipeline.hip      the asynchronous tree / net pipeline
-//   search_batch.hip  the batched position search (azmi_search_*)
+//   search_batch.hip  the batched position search (azmi_search_*): the one device module of the four search_*_kernels.h, every
+//                     launch of them, and the core entry points.  search_batch_sweep.hip, search_batch_pool.hip and
+//                     search_batch_frontier.hip hold the entry points of those three families; host code only, they launch
+//                     through search_batch.hip (search_batch_host.h)
+//   samples.hip       per-row losses, resample plan and metrics (azmi_sample_*, azmi_resample_*); DevBlock only
+// DevTemps are the device buffers of one call, DevBlock one that is kept between calls and grown.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,6 +75,22 @@ struct DevTemps {
  private:
   size_t min_bytes_;
   std::vector<void*> bufs_;
+};
+
+// A device block that outlives the call: kept by its owner between calls, grown when a call needs more, never shrunk.  What
+// the old block held is gone after a growth (the layouts of block_cut.h are cut again on the new one); the owner frees `p`.
+struct DevBlock {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipError_t reserve(size_t need) {
+    if (p && need <= bytes) return hipSuccess;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, need);
+    if (e != hipSuccess) return e;      // (the old block stays)
+    if (p) (void)hipFree(p);            // (waits for the device)
+    p = q; bytes = need;
+    return hipSuccess;
+  }
 };
 
 namespace azmi {

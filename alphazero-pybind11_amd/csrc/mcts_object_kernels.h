@@ -3,17 +3,9 @@
 // the PlayManager round kernel uses, on a one-slot engine (seat 0's tree).  Connect4 (lane-group engine).
 #pragma once
 #include "engine_kernels.h"
+#include "search_batch_types.h"      // WuArrays: the WU-UCT batched API state (mcts.cc:752-851)
 
 namespace azmi {
-
-// WU-UCT batched API state (mcts.cc:752-851): Node::n_in_flight per arena node + the in_flight_ list.  Every kernel of the
-// object that can create nodes clears the marks of the nodes it created, so the array always describes live nodes.
-struct WuArrays {
-  uint32_t* nif;        // [trees * cap] Node::n_in_flight
-  uint32_t* ifl_path;   // [ifl_cap][max_depth] InFlightLeaf::path
-  uint32_t* ifl_plen;   // [ifl_cap]
-  uint32_t* ifl_cur;    // [ifl_cap] InFlightLeaf::leaf
-};
 
 // the root GameState of a call = start position (optional serialized state) + move list
 template <class GM>

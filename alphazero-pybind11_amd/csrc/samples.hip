@@ -12,8 +12,10 @@
 #include <string>
 
 #include "../../include/azmi.h"
+#include "engine_host.h"
 #include "samples_kernels.h"
 #include "sample_metrics_kernels.h"
+#include "samples_layout.h"
 
 namespace {
 using namespace azmi;
@@ -59,11 +61,10 @@ struct DeviceScope {
 // its synchronisation, so two calls never use a block at once, and in the steady state no call allocates or frees (hipFree waits
 // for the whole device, not for the call's stream).
 constexpr int kPlanMaxDevices = 64;
-struct PlanScratch { void* block; size_t bytes; };
 std::mutex g_plan_mutex;
-PlanScratch g_plan_scratch[kPlanMaxDevices];
+DevBlock g_plan_scratch[kPlanMaxDevices];
 
-PlanScratch g_metrics_scratch[kPlanMaxDevices];      // the same for azmi_sample_metrics_reduce, under the same mutex
+DevBlock g_metrics_scratch[kPlanMaxDevices];      // the same for azmi_sample_metrics_reduce, under the same mutex
 
 uint32_t tiles_of(uint32_t n) { return (n + kPlanBlock - 1) / kPlanBlock; }
 
@@ -108,23 +109,18 @@ int azmi_resample_plan(const double* dev_loss, uint32_t n, uint64_t seed, uint32
   hipStream_t st = static_cast<hipStream_t>(stream);
   // one block: the record | the tile sums of the three levels (f64) | the tile totals of the scan's upper levels (u64)
   const uint32_t t0 = tiles_of(n), t1 = tiles_of(t0);      // t1 <= 1024: the level above it is one tile
-  const size_t words = 4 + 2 * (size_t(t0) + t1);
+  PlanScratch<ResampleRecord> ps;
+  BlockCut size;
+  cut_plan_scratch(size, ps, t0, t1);
   std::lock_guard<std::mutex> lock(g_plan_mutex);
-  PlanScratch& sc = g_plan_scratch[device];
-  hipError_t e = hipSuccess;
-  if (sc.bytes < words * 8) {      // first call on this device, or a larger n than any before
-    if (sc.block) (void)hipFree(sc.block);
-    sc.block = nullptr; sc.bytes = 0;
-    e = hipMalloc(&sc.block, words * 8);
-    if (e != hipSuccess) { sc.block = nullptr; return hip_fail("azmi_resample_plan", e); }
-    sc.bytes = words * 8;
-  }
-  void* block = sc.block;
-  ResampleRecord* rec = static_cast<ResampleRecord*>(block);
-  double* sum0 = static_cast<double*>(block) + 4;
-  double* sum1 = sum0 + t0;
-  uint64_t* tot0 = reinterpret_cast<uint64_t*>(sum1 + t1);
-  uint64_t* tot1 = tot0 + t0;
+  DevBlock& sc = g_plan_scratch[device];
+  hipError_t e = sc.reserve(size.off);      // allocates on the first call on this device, or for a larger n than any before
+  if (e != hipSuccess) return hip_fail("azmi_resample_plan", e);
+  BlockCut cut(sc.p);
+  cut_plan_scratch(cut, ps, t0, t1);
+  ResampleRecord* rec = ps.rec;
+  double *sum0 = ps.sum0, *sum1 = ps.sum1;
+  uint64_t *tot0 = ps.tot0, *tot1 = ps.tot1;
   e = hipMemsetAsync(rec, 0, sizeof *rec, st);
   if (e == hipSuccess) e = hipMemsetAsync(&rec->first_nonfinite, 0xFF, 4, st);
   if (e == hipSuccess) {
@@ -258,20 +254,17 @@ int azmi_sample_metrics_reduce(const double* dev_cols, uint64_t col_stride, uint
   const bool has_all = dev_bucket != nullptr;
   const uint32_t pairs = (n_buckets + (has_all ? 1u : 0u)) * kSampleMetricColumns;
   const uint32_t t0 = tiles_of(n), t1 = tiles_of(t0);      // t1 <= 1024: the level above it is one tile
-  const size_t bytes = sizeof(SampleMetricsRecord) + 8 * size_t(pairs) * (size_t(t0) + t1);
+  MetricsScratch<SampleMetricsRecord> ms;
+  BlockCut size;
+  cut_metrics_scratch(size, ms, pairs, t0, t1);
   std::lock_guard<std::mutex> lock(g_plan_mutex);
-  PlanScratch& sc = g_metrics_scratch[device];
-  hipError_t e = hipSuccess;
-  if (sc.bytes < bytes) {      // first call on this device, or a larger one than any before
-    if (sc.block) (void)hipFree(sc.block);
-    sc.block = nullptr; sc.bytes = 0;
-    e = hipMalloc(&sc.block, bytes);
-    if (e != hipSuccess) { sc.block = nullptr; return hip_fail("azmi_sample_metrics_reduce", e); }
-    sc.bytes = bytes;
-  }
-  SampleMetricsRecord* rec = static_cast<SampleMetricsRecord*>(sc.block);
-  double* sum0 = reinterpret_cast<double*>(rec + 1);
-  double* sum1 = sum0 + size_t(pairs) * t0;
+  DevBlock& sc = g_metrics_scratch[device];
+  hipError_t e = sc.reserve(size.off);      // allocates on the first call on this device, or for a larger one than any before
+  if (e != hipSuccess) return hip_fail("azmi_sample_metrics_reduce", e);
+  BlockCut cut(sc.p);
+  cut_metrics_scratch(cut, ms, pairs, t0, t1);
+  SampleMetricsRecord* rec = ms.rec;
+  double *sum0 = ms.sum0, *sum1 = ms.sum1;
   e = hipMemsetAsync(rec, 0, sizeof *rec, st);
   if (e == hipSuccess) e = hipMemsetAsync(&rec->first_nonfinite, 0xFF, 4, st);
   if (e == hipSuccess) {

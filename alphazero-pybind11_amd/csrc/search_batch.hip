@@ -10,17 +10,11 @@
 // no compaction, no net call, no cache insert, at most 3 launches a step.
 // azmi_search_set_descents_per_step(L > 1) lets a tree go on descending inside a step while its leaves need no evaluator (terminal,
 // RANDOM, cache hit): the *_dl kernels; a search then needs fewer steps than visits, and reads one word back to know how many.
-// azmi_search_run_to searches every tree to its own root_n target and snapshots the read-outs at checkpoints on the way
-// (mcts_analysis.py:884-972): the steps above, plus the checkpoint kernel at the steps the host knows something can happen at.
-// azmi_search_set_capture / capture_roots / captured, azmi_pool_unique and azmi_search_net_metrics are frozen_eval.py's capture
-// loop and metric extraction (csrc/search_pool_kernels.h): root records before every move's search, first-occurrence dedup of
-// keys, the net's raw forward of the roots against their searches.
-// azmi_search_expand / azmi_search_frontier are the step between two levels of opening_analysis.py's build_tree
-// (csrc/search_frontier_kernels.h): the sampling distribution of every searched root, the moves kept by reach probability and the
-// rules applied to every kept child, three launches whatever N is.
-// azmi_search_sweep_metrics scores the snapshot set of a run_to against its anchor checkpoint, the second half of
-// mcts_analysis.py:run_analysis (csrc/search_sweep_metrics_kernels.h): one launch over the (tree, checkpoint) rows, one for the
-// per-checkpoint means; azmi_policy_divergences is the same row function over any [rows, M] pair of HOST policies.
+// This file is also the ONE device module of the four search_*_kernels.h: a kernel header defines non-template kernels, and the
+// code of a kernel depends on the kernels it shares a module with and on the order they are instantiated in (DESIGN.md sections
+// 1 and 8.3).  So every launch lives here, one thin sb_launch_* function per kernel family (search_batch_host.h), in the order the
+// families were added; the entry points of the visit sweep, of capture / dedup / net metrics and of the opening-tree frontier are
+// host code only, in search_batch_sweep.hip, search_batch_pool.hip and search_batch_frontier.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,81 +23,14 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/azmi.h"
 #include "cache_host.h"
-#include "engine_host.h"
+#include "search_batch_host.h"
 #include "search_batch_kernels.h"
 #include "search_pool_kernels.h"
 #include "search_frontier_kernels.h"
 #include "search_sweep_metrics_kernels.h"
 
 using namespace azmi;
-
-#define SB_FAIL azmi_host_fail
-#define SB_TRY AZMI_HIP_TRY
-
-struct azmi_search {
-  azmi_pm* pm = nullptr;
-  uint32_t n = 0, max_sims = 0;
-  uint32_t sims_done = 0;      // descents that count against max_sims: since reset (Connect4), since the last update_roots (wide games)
-  bool flat_arena = false;     // Connect4: the arena never reclaims.  Wide games: two halves, compacted behind update_roots
-  float root_temp = 1.0f;
-  SbPlayArrays pl{};
-  int32_t* d_moves_in = nullptr;  // [N] a caller's moves for update_roots
-  uint32_t chw = 0, vec_f = 0, vec_u = 0;
-  bool ready = false;          // reset() has given every tree a position
-  bool step_pending = false;   // find_leaves() without its process_results()
-  bool gumbel = false;
-  uint32_t step_rows = 0;
-  SbArrays sb{};
-  uint64_t* d_keys = nullptr;     // [N] ar.cache_keys of a search with a cache attached
-  float* d_batch = nullptr;       // [N, C, H, W] compacted leaf batch of the step API
-  float* d_vrows = nullptr;       // [N, P+1] / [N, M]: host evaluator answers staged for the step API
-  float* d_pirows = nullptr;
-  float* d_qf = nullptr;          // [N, vec_f] / [N, vec_u] read-out buffers
-  uint32_t* d_qu = nullptr;
-  uint64_t launches = 0, net_calls = 0, steps = 0;
-  // several leaves in flight per tree and step (azmi_search_set_leaves_per_step): allocated only when K > 1
-  uint32_t k_leaves = 1;
-  uint32_t step_k = 0;            // descents of the pending find_leaves step
-  SbWuArrays wu{};
-  float* d_batch_wu = nullptr;    // [K * N, ...] the step API's buffers of a K > 1 step (d_batch, d_vrows, d_pirows hold N rows)
-  float* d_vrows_wu = nullptr;
-  float* d_pirows_wu = nullptr;
-  std::vector<void*> wu_allocs;
-  // EvalType::PLAYOUT: the rollout seed and rollout count of every tree, the parked leaf states of a Connect4 K == 1 step
-  SbRollArrays ro{};
-  std::vector<uint64_t> tree_seeds;   // seeds of the last reset: the default rollout seeds derive from them
-  // search to targets (azmi_search_run_to): allocated by the first call, regrown when it brings more checkpoints
-  SbSweepArrays sw{};
-  void* sw_block = nullptr;           // one allocation behind every sw pointer
-  size_t sw_clear_bytes = 0;          // its leading part that every call clears: taken masks and snapshot rows
-  uint32_t sw_cap = 0;                // checkpoints the block has room for
-  bool sw_valid = false;              // a run_to call has defined the snapshot set
-  std::vector<uint32_t> sw_upload;    // targets [N] + checkpoints [32]: the host side of the call's upload (kept until the next call)
-  // descents_per_step (azmi_search_set_descents_per_step): up to L descents of a tree per step while its leaves need no evaluator
-  uint32_t dl_L = 1;
-  SbDlArrays dl{};                    // todo [N], todo_max [2]
-  uint32_t dl_parity = 0;             // parity of the next step of the running search: the todo_max word it raises
-  uint64_t host_reads = 0;            // 4-byte reads of todo_max since creation
-  // root capture (azmi_search_set_capture): allocated by the first call that turns it on
-  bool capture = false;
-  SbCaptureArrays cp{};
-  // net versus search (azmi_search_net_metrics): allocated by the first call
-  double* d_nm_out = nullptr;         // [N, 3]
-  uint8_t* d_nm_valid = nullptr;      // [N]
-  // opening-tree frontier (azmi_search_expand): allocated by the first call, the records regrown when max_children grows
-  SbFrontierArrays fr{};
-  void* fr_trees = nullptr;           // one allocation behind every per-tree pointer of fr
-  void* fr_records = nullptr;         // one behind the per-record pointers
-  uint32_t fr_cap = 0;                // records fr_records has room for
-  double* fr_host = nullptr;          // pinned [2 N]: reach | temp of the last call, the host side of its upload
-  hipEvent_t fr_uploaded = nullptr;   // behind that upload
-  bool fr_valid = false;              // an expand call has defined the frontier
-  // sweep metrics (azmi_search_sweep_metrics): allocated by the first call, regrown when a sweep brings more checkpoints
-  void* sm_block = nullptr;           // rows [N, J, 15] | ceiling [N] | mean [J, 15] | outcomes [N] f64, count [J, 15] u32, valid [N, J] u8
-  uint32_t sm_cap = 0;                // checkpoints the block has room for
-};
 
 namespace {
 
@@ -131,25 +58,28 @@ void sb_for_game(int game, Small&& small, Big&& big) {
     (s)->launches += 1;                                                                                                                    \
   } while (0)
 
-void launch_find(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t eval_random, hipStream_t st) {
+}  // namespace
+
+void sb_launch_find(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t eval_random, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_find, k_sb_big_find, ep, ar, s->sb, s->n, eval_random);
   k_sb_compact<<<1, 1024, 0, st>>>(s->sb, s->n);
   s->launches += 1;
 }
 
-void launch_process(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, const float* v_rows, const float* pi_rows,
+void sb_launch_process(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, const float* v_rows, const float* pi_rows,
                     hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_process, k_sb_big_process, ep, ar, s->sb, s->n, root_noise, v_rows, pi_rows);
 }
 
-void launch_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, hipStream_t st) {
+void sb_launch_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_query, k_sb_big_query, s->pm->ep, s->pm->ar, s->n, kind, temp, arg, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
 }
+void sb_launch_query_scalars(azmi_search* s, hipStream_t st) { sb_launch_query(s, kQScalars, 0.0f, 0u, st); }
 
 // the answers of the step's net call go into the cache (PlayManager::update_inferences -> insert_many, play_manager.cc:631-640):
 // keys left by the find kernel in ar.cache_keys, (pi, v) rows indexed like them; `total` = N entries (K > 1: the kk * N of the
 // step, `ar` = wu_rows); ceil(total / kApplyMax) launches
-void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t total, hipStream_t st) {
+void sb_launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t total, hipStream_t st) {
   for (uint32_t off = 0; off < total; off += kApplyMax) {
     const uint32_t m = std::min<uint32_t>(kApplyMax, total - off);
     auto insert = [&](auto tag) { using GM = decltype(tag); k_cache_insert<GM><<<(m + 3) / 4, 256, 0, st>>>(ep, ar, ar.cache_keys, off, m, 0xFFFFFFFFu, 0u, 0u); };
@@ -158,37 +88,24 @@ void launch_cache_insert(azmi_search* s, const EngineParams& ep, const EngineArr
   }
 }
 
-// EvalType::PLAYOUT steps (defined at the end of the file: kernels that are instantiated last leave the code objects of the others where they were)
-void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, hipStream_t st);
-void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st);
-// the checkpoint kernel of azmi_search_run_to (also at the end of the file)
-void launch_checkpoint(azmi_search* s, float temp, uint32_t pruned, uint32_t resume, hipStream_t st);
-// descents_per_step > 1 (also at the end of the file): the counter launch of a search, the find launch(es) of a step
-void launch_todo_set(azmi_search* s, uint32_t visits, hipStream_t st);
-void launch_find_dl(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, uint32_t eval_random, uint32_t root_noise,
-                    hipStream_t st);
-void launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, hipStream_t st);
-// root capture (also at the end of the file): the record of every live tree's root at its current ply
-void launch_capture(azmi_search* s, hipStream_t st);
-
 // ---- K > 1: the same steps over K descents of every tree; the launch counts do not depend on N or K ---------------------------
-EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine arrays with the step-sized [K * N] row buffers in place
+static EngineArrays wu_rows(const azmi_search* s, EngineArrays ar) {     // the engine arrays with the step-sized [K * N] row buffers in place
   ar.canon = s->wu.canon; ar.v = s->wu.v; ar.pi = s->wu.pi; ar.cache_keys = s->wu.keys;
   return ar;
 }
 
-void launch_find_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t eval_random, uint32_t root_noise, hipStream_t st) {
+void sb_launch_find_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t eval_random, uint32_t root_noise, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_find_wu, k_sb_big_find_wu, ep, ar, s->sb, s->wu, s->n, kk, eval_random, root_noise);
   k_sb_compact_wu<<<1, 1024, 0, st>>>(s->sb, s->wu, s->n, kk);
   s->launches += 1;
 }
 
-void launch_process_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, const float* v_rows,
+void sb_launch_process_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, const float* v_rows,
                        const float* pi_rows, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_process_wu, k_sb_big_process_wu, ep, ar, s->wu, s->n, kk, root_noise, v_rows, pi_rows);
 }
 
-void wu_free(azmi_search* s) {
+static void wu_free(azmi_search* s) {
   for (void* q : s->wu_allocs) (void)hipFree(q);
   s->wu_allocs.clear();
   s->wu = SbWuArrays{};
@@ -198,7 +115,7 @@ void wu_free(azmi_search* s) {
 // why `more` descents do not fit (0: they do).  Connect4's flat arena never reclaims, so max_simulations counts every descent
 // since reset(), the searches between moves included; the wide games compact behind update_roots (the PlayManager engine's rule),
 // so it counts the descents since the last one.
-int check_budget(const azmi_search* s, const char* what, uint64_t more) {
+int sb_check_budget(const azmi_search* s, const char* what, uint64_t more) {
   if (more <= s->max_sims - s->sims_done) return AZMI_OK;
   if (s->flat_arena)
     return SB_FAIL(AZMI_ERR_OVERFLOW, "%s: %llu more simulations, %u of max_simulations = %u are already used: a Connect4 arena never "
@@ -212,7 +129,7 @@ int check_budget(const azmi_search* s, const char* what, uint64_t more) {
 // synchronises `st` and turns a stopped tree / a raised overflow bit into an error that names the tree.  A finished tree
 // (status > 0) is no error.  The two errors of a move (a move the root does not have, a root without visits) left their tree as
 // it was: the tree is named, its status and the engine's "unknown move" bit are cleared, and the object stays usable.
-int check_device(azmi_search* s, hipStream_t st) {
+int sb_check_device(azmi_search* s, hipStream_t st) {
   Control c;
   std::vector<int32_t> status(s->n);
   SB_TRY(hipMemcpyAsync(&c, s->pm->ar.ctl, sizeof(c), hipMemcpyDeviceToHost, st));
@@ -250,22 +167,15 @@ int check_device(azmi_search* s, hipStream_t st) {
   return AZMI_OK;
 }
 
-int begin_step(azmi_search* s, const char* what) {
+int sb_begin_step(azmi_search* s, const char* what) {
   if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   if (!s->ready) return SB_FAIL(AZMI_ERR_STATE, "%s: the trees have no positions; call reset first", what);
   return AZMI_OK;
 }
 
-// the engine parameters and arrays of a search() with this net and cache
-struct SearchArgs {
-  EngineParams ep;
-  EngineArrays ar;
-  azmi_net* net = nullptr;
-  bool playout = false;
-};
 // the evaluator of azmi_search_run_eval / play_eval: NN needs a net, RANDOM and PLAYOUT take none; PLAYOUT takes no cache either
 // (the reference's playout branch sits before the cache probe, play.py:306 / :320)
-int search_args(azmi_search* s, const char* what, int eval_type, azmi_net* net, azmi_cache* cache, SearchArgs* out) {
+int sb_search_args(azmi_search* s, const char* what, int eval_type, azmi_net* net, azmi_cache* cache, SbSearchArgs* out) {
   azmi_pm* pm = s->pm;
   if (eval_type != AZMI_EVAL_NN && eval_type != AZMI_EVAL_RANDOM && eval_type != AZMI_EVAL_PLAYOUT)
     return SB_FAIL(AZMI_ERR_INVALID, "%s: eval_type %d is none of NN, RANDOM, PLAYOUT", what, eval_type);
@@ -291,47 +201,47 @@ int search_args(azmi_search* s, const char* what, int eval_type, azmi_net* net, 
 }
 
 // one step of every live tree on `st`: `kk` descents each (1 unless leaves_per_step > 1), the evaluator, the back-up
-int enqueue_step(azmi_search* s, const SearchArgs& a, uint32_t kk, uint32_t rn, hipStream_t st) {
+int sb_enqueue_step(azmi_search* s, const SbSearchArgs& a, uint32_t kk, uint32_t rn, hipStream_t st) {
   const EngineParams& ep = a.ep;
   const EngineArrays& ar = a.ar;
   azmi_net* net = a.net;
   if (s->dl_L > 1) {      // up to L descents of every tree that still owes some; at most one row per tree, so the rest of the step is K == 1's
     const uint32_t parity = s->dl_parity;
     s->dl_parity ^= 1u;
-    if (a.playout) launch_find_dl_playout(s, ep, ar, parity, st);
+    if (a.playout) sb_launch_find_dl_playout(s, ep, ar, parity, st);
     else {
-      launch_find_dl(s, ep, ar, parity, net ? 0u : 1u, rn, st);
+      sb_launch_find_dl(s, ep, ar, parity, net ? 0u : 1u, rn, st);
       if (net) {
         const int rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
         if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
         s->net_calls += 1;
-        if (ep.cache_on) launch_cache_insert(s, ep, ar, s->n, st);
+        if (ep.cache_on) sb_launch_cache_insert(s, ep, ar, s->n, st);
       }
     }
     // RANDOM leaves nothing pending (every descent is backed up by the find kernel): no process launch
-    if (net || a.playout) launch_process(s, ep, ar, rn, nullptr, nullptr, st);
+    if (net || a.playout) sb_launch_process(s, ep, ar, rn, nullptr, nullptr, st);
   } else if (a.playout) {
-    if (s->k_leaves > 1) launch_step_playout_wu(s, ep, ar, kk, rn, st);
-    else launch_step_playout(s, ep, ar, rn, st);
+    if (s->k_leaves > 1) sb_launch_step_playout_wu(s, ep, ar, kk, rn, st);
+    else sb_launch_step_playout(s, ep, ar, rn, st);
   } else if (s->k_leaves > 1) {
     const EngineArrays aw = wu_rows(s, ar);
-    launch_find_wu(s, ep, ar, kk, net ? 0u : 1u, rn, st);
+    sb_launch_find_wu(s, ep, ar, kk, net ? 0u : 1u, rn, st);
     if (net) {
       const int rc = azmi_net_forward_rows(net, aw.canon, aw.v, aw.pi, s->wu.rows, s->sb.n_rows, s->n * kk, st);
       if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
       s->net_calls += 1;
-      if (ep.cache_on) launch_cache_insert(s, ep, aw, s->n * kk, st);
+      if (ep.cache_on) sb_launch_cache_insert(s, ep, aw, s->n * kk, st);
     }
-    launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
+    sb_launch_process_wu(s, ep, ar, kk, rn, nullptr, nullptr, st);
   } else {
-    launch_find(s, ep, ar, net ? 0u : 1u, st);
+    sb_launch_find(s, ep, ar, net ? 0u : 1u, st);
     if (net) {
       const int rc = azmi_net_forward_rows(net, ar.canon, ar.v, ar.pi, s->sb.rows, s->sb.n_rows, s->n, st);
       if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
       s->net_calls += 1;
-      if (ep.cache_on) launch_cache_insert(s, ep, ar, s->n, st);
+      if (ep.cache_on) sb_launch_cache_insert(s, ep, ar, s->n, st);
     }
-    launch_process(s, ep, ar, rn, nullptr, nullptr, st);
+    sb_launch_process(s, ep, ar, rn, nullptr, nullptr, st);
   }
   s->steps += 1;
   return AZMI_OK;
@@ -346,15 +256,15 @@ int enqueue_step(azmi_search* s, const SearchArgs& a, uint32_t kk, uint32_t rn, 
 // is capped at r: the search is complete behind round ceil(log2(visits)) at the latest, after at most 1 + ceil(log2(visits)) reads.
 // (Halving r instead - max(1, ceil(r / 2)) steps per read - takes 1 + visits / 2 steps where the leaves are all immediate and 2 do.)
 // The call returns behind the read of 0: only the last step's back-up may still be running
-int enqueue_search_dl(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
+static int enqueue_search_dl(azmi_search* s, const SbSearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
   if (!visits) return AZMI_OK;
-  launch_todo_set(s, visits, st);
+  sb_launch_todo_set(s, visits, st);
   s->dl_parity = 0;
   const bool blind = !a.net && !a.playout;
   uint32_t more = (visits + s->dl_L - 1) / s->dl_L;
   for (uint32_t reads = 0;; ++reads) {      // round `reads` of `more` steps
     for (uint32_t i = 0; i < more; ++i) {
-      const int rc = enqueue_step(s, a, 1, rn, st);
+      const int rc = sb_enqueue_step(s, a, 1, rn, st);
       if (rc != AZMI_OK) return rc;
     }
     SB_TRY(hipGetLastError());
@@ -374,12 +284,12 @@ int enqueue_search_dl(azmi_search* s, const SearchArgs& a, uint32_t visits, uint
 
 // the steps of search(visits) on `st`, nothing read back: azmi_search_run, and every move of azmi_search_play.  Enqueued back to
 // back: the row count of a step never leaves the device.  K > 1: visits / K steps of K descents and one of the remainder
-int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
-  if (s->gumbel && visits) launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
+int sb_enqueue_search(azmi_search* s, const SbSearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st) {
+  if (s->gumbel && visits) sb_launch_query(s, kQSetGumbelSims, 0.0f, visits, st);     // set_gumbel_num_sims(visits) on every tree
   if (s->dl_L > 1) return enqueue_search_dl(s, a, visits, rn, st);
   for (uint32_t left = visits; left;) {
     const uint32_t kk = std::min<uint32_t>(s->k_leaves, left);
-    const int rc = enqueue_step(s, a, kk, rn, st);
+    const int rc = sb_enqueue_step(s, a, kk, rn, st);
     if (rc != AZMI_OK) return rc;
     left -= kk;
   }
@@ -389,12 +299,12 @@ int enqueue_search(azmi_search* s, const SearchArgs& a, uint32_t visits, uint32_
 }
 
 // ---- a move: pick, update-root (+ compaction for the wide games), root prior; one launch each, whatever N is ------------------
-void launch_pick(azmi_search* s, float temp, hipStream_t st) {
+void sb_launch_pick(azmi_search* s, float temp, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_pick, k_sb_big_pick, s->pm->ep, s->pm->ar, s->sb, s->pl, s->n, temp, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
 }
 
 // `moves`: [N] on the device.  The wide games compact behind it (k_compact lives in engine.hip's device module)
-void launch_update_root(azmi_search* s, const int32_t* moves, hipStream_t st) {
+void sb_launch_update_root(azmi_search* s, const int32_t* moves, hipStream_t st) {
   uint32_t* nif = s->k_leaves > 1 ? s->wu.wu.nif : nullptr;
   SB_LAUNCH(s, st, k_sb_update_root, k_sb_big_update_root, s->pm->ep, s->pm->ar, s->sb, s->pl, s->n, moves, nif);
   if (s->pm->ep.half_nodes) {
@@ -403,27 +313,25 @@ void launch_update_root(azmi_search* s, const int32_t* moves, hipStream_t st) {
   }
 }
 
-void launch_root_prior(azmi_search* s, uint32_t apply_temp, uint32_t noise, hipStream_t st) {
+void sb_launch_root_prior(azmi_search* s, uint32_t apply_temp, uint32_t noise, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_root_prior, k_sb_big_root_prior, s->pm->ep, s->pm->ar, s->sb, s->n, apply_temp, noise, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
 }
 
 // A NULL handle is what a caller holds whose create failed.  On a machine without a device that failure was the no-device one, and
 // the move entry points repeat it (AZMI_ERR_NO_DEVICE); with a device a NULL handle is an invalid argument (include/azmi.h says so).
-int begin_read(azmi_search* s, const char* what) {
+int sb_begin_read(azmi_search* s, const char* what) {
   if (!s) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SB_FAIL(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
   }
-  return begin_step(s, what);
+  return sb_begin_step(s, what);
 }
 // the calls that change the trees: not while a find_leaves step is pending
-int begin_move(azmi_search* s, const char* what) {
-  int rc = begin_read(s, what); if (rc) return rc;
+int sb_begin_move(azmi_search* s, const char* what) {
+  int rc = sb_begin_read(s, what); if (rc) return rc;
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "%s: a find_leaves step is pending; call process_results first", what);
   return AZMI_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -493,10 +401,10 @@ void azmi_search_destroy(azmi_search* s) {
   if (!s) return;
   (void)hipSetDevice(s->pm->device);
   wu_free(s);        // (hipFree waits for the device)
-  if (s->sw_block) (void)hipFree(s->sw_block);
-  if (s->sm_block) (void)hipFree(s->sm_block);
+  if (s->sw_block.p) (void)hipFree(s->sw_block.p);
+  if (s->sm_block.p) (void)hipFree(s->sm_block.p);
   if (s->fr_trees) (void)hipFree(s->fr_trees);
-  if (s->fr_records) (void)hipFree(s->fr_records);
+  if (s->fr_records.p) (void)hipFree(s->fr_records.p);
   if (s->fr_host) (void)hipHostFree(s->fr_host);
   if (s->fr_uploaded) (void)hipEventDestroy(s->fr_uploaded);
   azmi_pm_destroy(s->pm);
@@ -621,39 +529,39 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
     return SB_FAIL(AZMI_ERR_NO_DEVICE, "azmi_search_reset: %s", hipGetErrorString(e));
   }
   pm->last = st;
-  const int rc = check_device(s, st);   // synchronises st: tmp is freed after it
+  const int rc = sb_check_device(s, st);   // synchronises st: tmp is freed after it
   if (rc != AZMI_OK) return rc;
   s->ready = true;
   return AZMI_OK;
 }
 
 int azmi_search_find_leaves(azmi_search* s, void* stream, float** dev_canonical, uint32_t** dev_tree_index, uint32_t* n_rows) {
-  int rc = begin_step(s, "find_leaves"); if (rc) return rc;
+  int rc = sb_begin_step(s, "find_leaves"); if (rc) return rc;
   if (!n_rows) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "find_leaves: the previous step's process_results has not been called");
   if (s->dl_L > 1)
     return SB_FAIL(AZMI_ERR_INVALID, "find_leaves with descents_per_step = %u: the step API's caller owns the evaluator and the step, one "
                    "descent of every tree each; use search / play, or descents_per_step = 1", s->dl_L);
-  rc = check_budget(s, "find_leaves", 1); if (rc) return rc;
+  rc = sb_check_budget(s, "find_leaves", 1); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
   const bool wu = s->k_leaves > 1;
   const uint32_t kk = std::min<uint32_t>(s->k_leaves, s->max_sims - s->sims_done);     // fewer than K left: the remainder only
   if (wu) {
-    launch_find_wu(s, pm->ep, pm->ar, kk, 0u, 0u, st);
+    sb_launch_find_wu(s, pm->ep, pm->ar, kk, 0u, 0u, st);
     SbArrays rows_of_step = s->sb;       // k_sb_gather over the step's kk * N entries
     rows_of_step.row_of = s->wu.row_of;
     k_sb_gather<<<s->n * kk, 256, 0, st>>>(rows_of_step, s->n * kk, s->wu.canon, s->chw, s->d_batch_wu);
   } else {
-    launch_find(s, pm->ep, pm->ar, 0u, st);
+    sb_launch_find(s, pm->ep, pm->ar, 0u, st);
     k_sb_gather<<<s->n, 256, 0, st>>>(s->sb, s->n, pm->ar.canon, s->chw, s->d_batch);
   }
   s->launches += 1;
   SB_TRY(hipGetLastError());
   uint32_t rows = 0;
   SB_TRY(hipMemcpyAsync(&rows, s->sb.n_rows, 4, hipMemcpyDeviceToHost, st));
-  rc = check_device(s, st); if (rc) return rc;
+  rc = sb_check_device(s, st); if (rc) return rc;
   s->step_pending = true; s->step_rows = rows; s->step_k = kk;
   if (dev_canonical) *dev_canonical = wu ? s->d_batch_wu : s->d_batch;
   if (dev_tree_index) *dev_tree_index = wu ? s->wu.tree_of : s->sb.rows;
@@ -676,7 +584,7 @@ int azmi_search_leaves_to_host(azmi_search* s, float* canonical, uint32_t* tree_
 }
 
 int azmi_search_process_results(azmi_search* s, const float* dev_v, const float* dev_pi, int root_noise_enabled, void* stream) {
-  int rc = begin_step(s, "process_results"); if (rc) return rc;
+  int rc = sb_begin_step(s, "process_results"); if (rc) return rc;
   if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "process_results: no leaf batch is pending; call find_leaves first");
   if (s->step_rows && (!dev_v || !dev_pi)) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   azmi_pm* pm = s->pm;
@@ -684,9 +592,9 @@ int azmi_search_process_results(azmi_search* s, const float* dev_v, const float*
   hipStream_t st = pm->pick(stream);
   // (with no rows the pointers are not read: every pending tree is a terminal leaf already backed up)
   if (s->k_leaves > 1)
-    launch_process_wu(s, pm->ep, pm->ar, s->step_k, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
+    sb_launch_process_wu(s, pm->ep, pm->ar, s->step_k, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
   else
-    launch_process(s, pm->ep, pm->ar, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
+    sb_launch_process(s, pm->ep, pm->ar, root_noise_enabled ? 1u : 0u, s->step_rows ? dev_v : nullptr, s->step_rows ? dev_pi : nullptr, st);
   SB_TRY(hipGetLastError());
   s->step_pending = false;
   s->sims_done += s->step_k; s->steps += 1;
@@ -694,7 +602,7 @@ int azmi_search_process_results(azmi_search* s, const float* dev_v, const float*
 }
 
 int azmi_search_process_results_host(azmi_search* s, const float* v, const float* pi, int root_noise_enabled) {
-  int rc = begin_step(s, "process_results"); if (rc) return rc;
+  int rc = sb_begin_step(s, "process_results"); if (rc) return rc;
   if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "process_results: no leaf batch is pending; call find_leaves first");
   if (s->step_rows && (!v || !pi)) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   azmi_pm* pm = s->pm;
@@ -713,13 +621,13 @@ int azmi_search_process_results_host(azmi_search* s, const float* v, const float
 }
 
 int azmi_search_run_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream) {
-  int rc = begin_step(s, "search"); if (rc) return rc;
+  int rc = sb_begin_step(s, "search"); if (rc) return rc;
   if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "search: a find_leaves step is pending; call process_results first");
-  rc = check_budget(s, "search", visits); if (rc) return rc;
-  SearchArgs a;
-  rc = search_args(s, "search", eval_type, net, cache, &a); if (rc) return rc;
+  rc = sb_check_budget(s, "search", visits); if (rc) return rc;
+  SbSearchArgs a;
+  rc = sb_search_args(s, "search", eval_type, net, cache, &a); if (rc) return rc;
   SB_TRY(hipSetDevice(s->pm->device));
-  return enqueue_search(s, a, visits, root_noise_enabled ? 1u : 0u, s->pm->pick(stream));
+  return sb_enqueue_search(s, a, visits, root_noise_enabled ? 1u : 0u, s->pm->pick(stream));
 }
 
 int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream) {
@@ -727,7 +635,7 @@ int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t v
 }
 
 int azmi_search_set_rollout_seeds(azmi_search* s, const uint64_t* seeds) {
-  int rc = begin_move(s, "set_rollout_seeds"); if (rc) return rc;
+  int rc = sb_begin_move(s, "set_rollout_seeds"); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   std::vector<uint64_t> roll(s->n);
@@ -738,19 +646,19 @@ int azmi_search_set_rollout_seeds(azmi_search* s, const uint64_t* seeds) {
 }
 
 int azmi_search_pick_moves(azmi_search* s, float temp, int32_t* host_moves, void* stream) {
-  int rc = begin_move(s, "pick_moves"); if (rc) return rc;
+  int rc = sb_begin_move(s, "pick_moves"); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
-  launch_pick(s, temp, st);
+  sb_launch_pick(s, temp, st);
   SB_TRY(hipGetLastError());
   if (!host_moves) return AZMI_OK;
   SB_TRY(hipMemcpyAsync(host_moves, s->pl.move, static_cast<size_t>(s->n) * 4, hipMemcpyDeviceToHost, st));
-  return check_device(s, st);
+  return sb_check_device(s, st);
 }
 
 int azmi_search_update_roots(azmi_search* s, const int32_t* host_moves, void* stream) {
-  int rc = begin_move(s, "update_roots"); if (rc) return rc;
+  int rc = sb_begin_move(s, "update_roots"); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
@@ -762,22 +670,22 @@ int azmi_search_update_roots(azmi_search* s, const int32_t* host_moves, void* st
     }
     SB_TRY(hipMemcpyAsync(s->d_moves_in, host_moves, static_cast<size_t>(s->n) * 4, hipMemcpyHostToDevice, st));
   }
-  launch_update_root(s, host_moves ? s->d_moves_in : s->pl.move, st);
+  sb_launch_update_root(s, host_moves ? s->d_moves_in : s->pl.move, st);
   SB_TRY(hipGetLastError());
   // a caller's moves may be unknown to a root: that is reported here, with the tree's index (the picked ones are children of their roots)
-  rc = host_moves ? check_device(s, st) : AZMI_OK;
+  rc = host_moves ? sb_check_device(s, st) : AZMI_OK;
   // every live tree moved, none refused its move: compaction has made room for the next search
   if (!s->flat_arena && all && rc == AZMI_OK) s->sims_done = 0;
   return rc;
 }
 
 int azmi_search_root_prior(azmi_search* s, int apply_temp, int add_noise, void* stream) {
-  int rc = begin_move(s, "root_prior"); if (rc) return rc;
+  int rc = sb_begin_move(s, "root_prior"); if (rc) return rc;
   if (!apply_temp && !add_noise) return AZMI_OK;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
-  launch_root_prior(s, apply_temp ? 1u : 0u, add_noise ? 1u : 0u, st);
+  sb_launch_root_prior(s, apply_temp ? 1u : 0u, add_noise ? 1u : 0u, st);
   SB_TRY(hipGetLastError());
   return AZMI_OK;
 }
@@ -789,35 +697,35 @@ int azmi_search_play(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t 
 
 int azmi_search_play_eval(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, uint32_t visits, float temp, uint32_t max_moves,
                           int root_noise, void* stream) {
-  int rc = begin_move(s, "play"); if (rc) return rc;
+  int rc = sb_begin_move(s, "play"); if (rc) return rc;
   // the whole call's budget before anything is enqueued: Connect4 counts every move's search; a wide game's first search comes on
   // top of the descents since the last update_roots, and every later one starts behind a compaction
-  rc = check_budget(s, "play", s->flat_arena ? static_cast<uint64_t>(visits) * max_moves : (max_moves ? visits : 0u)); if (rc) return rc;
-  SearchArgs a;
-  rc = search_args(s, "play", eval_type, net, cache, &a); if (rc) return rc;
+  rc = sb_check_budget(s, "play", s->flat_arena ? static_cast<uint64_t>(visits) * max_moves : (max_moves ? visits : 0u)); if (rc) return rc;
+  SbSearchArgs a;
+  rc = sb_search_args(s, "play", eval_type, net, cache, &a); if (rc) return rc;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->pick(stream);
   const uint32_t rn = root_noise ? 1u : 0u, rt = s->root_temp != 1.0f ? 1u : 0u;
   for (uint32_t m = 0; m < max_moves; ++m) {
-    if (s->capture) launch_capture(s, st);
-    rc = enqueue_search(s, a, visits, rn, st); if (rc) return rc;
-    launch_pick(s, temp, st);
-    launch_update_root(s, s->pl.move, st);
+    if (s->capture) sb_launch_capture(s, st);
+    rc = sb_enqueue_search(s, a, visits, rn, st); if (rc) return rc;
+    sb_launch_pick(s, temp, st);
+    sb_launch_update_root(s, s->pl.move, st);
     if (!s->flat_arena) s->sims_done = 0;
-    if (rn || rt) launch_root_prior(s, rt, rn, st);
+    if (rn || rt) sb_launch_root_prior(s, rt, rn, st);
   }
   SB_TRY(hipGetLastError());
   return AZMI_OK;
 }
 
 int azmi_search_game_state(azmi_search* s, int32_t* status, uint32_t* log_len, int32_t* log, float* final_scores) {
-  int rc = begin_read(s, "game_state"); if (rc) return rc;      // a read-out: legal while a find_leaves step is pending
+  int rc = sb_begin_read(s, "game_state"); if (rc) return rc;      // a read-out: legal while a find_leaves step is pending
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->last;
   const size_t N = s->n;
-  rc = check_device(s, st); if (rc) return rc;      // (synchronises)
+  rc = sb_check_device(s, st); if (rc) return rc;      // (synchronises)
   if (status) SB_TRY(hipMemcpy(status, s->sb.status, N * 4, hipMemcpyDeviceToHost));
   if (log_len) SB_TRY(hipMemcpy(log_len, s->pl.log_len, N * 4, hipMemcpyDeviceToHost));
   if (log) SB_TRY(hipMemcpy(log, s->pl.log, N * s->pl.log_cap * 4, hipMemcpyDeviceToHost));
@@ -826,24 +734,24 @@ int azmi_search_game_state(azmi_search* s, int32_t* status, uint32_t* log_len, i
 }
 
 int azmi_search_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, float* out_f, uint32_t* out_u) {
-  int rc = begin_step(s, "query"); if (rc) return rc;
+  int rc = sb_begin_step(s, "query"); if (rc) return rc;
   if (!(kind <= kQGumbelFinal || kind == kQPrincipalVariation || kind == kQSetGumbelSims))
     return SB_FAIL(AZMI_ERR_INVALID, "query kind %u is not available on a batched search", kind);
   if (kind == kQPrincipalVariation && arg > 60) arg = 60;
   azmi_pm* pm = s->pm;
   SB_TRY(hipSetDevice(pm->device));
   hipStream_t st = pm->last;
-  launch_query(s, kind, temp, arg, st);
+  sb_launch_query(s, kind, temp, arg, st);
   SB_TRY(hipGetLastError());
   if (out_f) SB_TRY(hipMemcpyAsync(out_f, s->d_qf, static_cast<size_t>(s->n) * s->vec_f * 4, hipMemcpyDeviceToHost, st));
   if (out_u) SB_TRY(hipMemcpyAsync(out_u, s->d_qu, static_cast<size_t>(s->n) * s->vec_u * 4, hipMemcpyDeviceToHost, st));
-  return check_device(s, st);
+  return sb_check_device(s, st);
 }
 
 int azmi_search_sync(azmi_search* s) {
   if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
   SB_TRY(hipSetDevice(s->pm->device));
-  return check_device(s, s->pm->last);
+  return sb_check_device(s, s->pm->last);
 }
 
 int azmi_search_stats(azmi_search* s, uint64_t out[6]) {
@@ -864,10 +772,8 @@ int azmi_search_stats(azmi_search* s, uint64_t out[6]) {
 
 }  // extern "C"
 
-namespace {
-
 // ---- EvalType::PLAYOUT: rollouts on the device; see search_batch_kernels.h for the three step shapes ----------------------------
-void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, hipStream_t st) {
+void sb_launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t root_noise, hipStream_t st) {
   const uint32_t n = s->n;
   sb_for_game(s->pm->game,
               [&](auto tag) {
@@ -877,153 +783,25 @@ void launch_step_playout(azmi_search* s, const EngineParams& ep, const EngineArr
                 s->launches += 2;
               },
               [&](auto tag) { using GM = decltype(tag); k_sb_big_find_po<GM><<<n, 64, 0, st>>>(ep, ar, s->sb, s->ro, n); s->launches += 1; });
-  launch_process(s, ep, ar, root_noise, nullptr, nullptr, st);
+  sb_launch_process(s, ep, ar, root_noise, nullptr, nullptr, st);
 }
 
-void launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st) {
+void sb_launch_step_playout_wu(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_find_wu_po, k_sb_big_find_wu_po, ep, ar, s->sb, s->wu, s->ro, s->n, kk, root_noise);
 }
 
-}  // namespace
-
 // ---- search to per-tree root_n targets, snapshots at checkpoints (mcts_analysis.py:884-972, 975-1063) ---------------------------
-namespace {
-
-void launch_checkpoint(azmi_search* s, float temp, uint32_t pruned, uint32_t resume, hipStream_t st) {
+void sb_launch_checkpoint(azmi_search* s, float temp, uint32_t pruned, uint32_t resume, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_checkpoint, k_sb_big_checkpoint, s->pm->ep, s->pm->ar, s->sb, s->sw, s->n, temp, pruned, resume);
 }
 
-// room for `j` checkpoints: one block, [taken | root_n | counts | probs | root_values | root_q] (cleared by every call) and
-// [target | cps] behind them (uploaded by every call).  Rows are indexed with the call's own J, so a block grown for more
-// checkpoints serves fewer
-int sweep_reserve(azmi_search* s, uint32_t j) {
-  const size_t N = s->n, M = s->pm->gi.M;
-  if (!s->sw_block || j > s->sw_cap) {
-    const size_t cap = std::max<uint32_t>(j, 1u);
-    const size_t clear_words = N * (1 + cap * (1 + 3 * M + 3));
-    void* q = nullptr;
-    SB_TRY(hipMalloc(&q, (clear_words + N + kSbMaxCheckpoints) * 4));
-    if (s->sw_block) (void)hipFree(s->sw_block);      // (waits for the device)
-    s->sw_block = q; s->sw_cap = static_cast<uint32_t>(cap); s->sw_clear_bytes = clear_words * 4;
-    uint32_t* w = static_cast<uint32_t*>(q);
-    s->sw.taken = w; w += N;
-    s->sw.root_n = w; w += N * cap;
-    s->sw.counts = w; w += N * cap * M;
-    s->sw.probs = reinterpret_cast<float*>(w); w += N * cap * M;
-    s->sw.root_values = reinterpret_cast<float*>(w); w += N * cap * 3;
-    s->sw.root_q = reinterpret_cast<float*>(w); w += N * cap * M;
-    s->sw.target = w; w += N;
-    s->sw.cps = w;
-  }
-  s->sw.n_cp = j;
-  return AZMI_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int azmi_search_run_to(azmi_search* s, int eval_type, azmi_net* net, azmi_cache* cache, const uint32_t* targets, const uint32_t* checkpoints,
-                       uint32_t n_checkpoints, float temp, int pruned, int root_noise_enabled, void* stream) {
-  int rc = begin_step(s, "search_to"); if (rc) return rc;
-  if (s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "search_to: a find_leaves step is pending; call process_results first");
-  if (!targets || (n_checkpoints && !checkpoints)) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
-  if (s->dl_L > 1)
-    return SB_FAIL(AZMI_ERR_INVALID, "search_to with descents_per_step = %u: the checkpoint launches are planned from one root_n read and one "
-                   "descent of every tree per step; use search(visits), or descents_per_step = 1", s->dl_L);
-  if (s->gumbel)
-    return SB_FAIL(AZMI_ERR_INVALID, "search_to on a Gumbel batch: sequential halving plans a fixed budget at its first descent, and a "
-                   "root_n target on a reused tree is not one; use search(visits)");
-  if (n_checkpoints > kSbMaxCheckpoints) return SB_FAIL(AZMI_ERR_INVALID, "search_to: at most %u checkpoints, got %u", kSbMaxCheckpoints, n_checkpoints);
-  for (uint32_t j = 0; j < n_checkpoints; ++j)
-    if (checkpoints[j] == 0 || (j && checkpoints[j] <= checkpoints[j - 1]))
-      return SB_FAIL(AZMI_ERR_INVALID, "search_to: checkpoints must be positive and strictly ascending (checkpoint %u is %u)", j, checkpoints[j]);
-  SearchArgs a;
-  rc = search_args(s, "search_to", eval_type, net, cache, &a); if (rc) return rc;
-  azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  hipStream_t prev = pm->last;
-  hipStream_t st = pm->pick(stream);
-  if (prev != st) SB_TRY(hipStreamSynchronize(prev));      // the previous call's upload may still read sw_upload
-  const uint32_t n = s->n, K = s->k_leaves, J = n_checkpoints;
-  // the one read of the call: root_n (kind-5 read-out, column 1) and the status of every tree.  `launches` counts what the call
-  // enqueues behind it
-  std::vector<uint32_t> r(n);
-  std::vector<int32_t> status(n);
-  launch_query(s, kQScalars, 0.0f, 0u, st);
-  s->launches -= 1;
-  SB_TRY(hipGetLastError());
-  SB_TRY(hipMemcpy2DAsync(r.data(), 4, s->d_qu + 1, static_cast<size_t>(s->vec_u) * 4, 4, n, hipMemcpyDeviceToHost, st));
-  SB_TRY(hipMemcpyAsync(status.data(), s->sb.status, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st));
-  SB_TRY(hipStreamSynchronize(st));
-  // root_n rises by exactly one per backed-up simulation, so tree i holds r[i] + t * K after step t until it reaches its target,
-  // at step ceil(rem / K): the steps at which a tree newly reaches a checkpoint or its target are known here
-  uint32_t T = 0;
-  for (uint32_t i = 0; i < n; ++i)
-    if (status[i] == 0 && targets[i] > r[i]) T = std::max(T, (targets[i] - r[i] + K - 1) / K);
-  rc = check_budget(s, "search_to", static_cast<uint64_t>(T) * K); if (rc) return rc;
-  std::vector<uint8_t> event(static_cast<size_t>(T) + 1, 0);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (status[i] != 0) continue;
-    const uint32_t ti = targets[i] > r[i] ? (targets[i] - r[i] + K - 1) / K : 0u;
-    if (T) event[ti] = 1;      // the pause (with T == 0 no step follows that a pause could keep a tree out of)
-    for (uint32_t j = 0; j < J; ++j) {
-      const uint32_t tj = checkpoints[j] > r[i] ? (checkpoints[j] - r[i] + K - 1) / K : 0u;
-      if (tj <= ti) event[tj] = 1;
-    }
-  }
-  if (T) event[T] = 1;         // the resume
-  rc = sweep_reserve(s, J); if (rc) return rc;
-  s->sw_upload.assign(targets, targets + n);
-  if (J) s->sw_upload.insert(s->sw_upload.end(), checkpoints, checkpoints + J);
-  s->sw_upload.resize(static_cast<size_t>(n) + kSbMaxCheckpoints, 0u);
-  SB_TRY(hipMemsetAsync(s->sw_block, 0, s->sw_clear_bytes, st));
-  SB_TRY(hipMemcpyAsync(s->sw.target, s->sw_upload.data(), s->sw_upload.size() * 4, hipMemcpyHostToDevice, st));
-  s->sw_valid = true;
-  if (T == 0 && !event[0]) return AZMI_OK;
-  const uint32_t rn = root_noise_enabled ? 1u : 0u, pr = pruned ? 1u : 0u;
-  // from the first checkpoint launch on a tree may be paused: every way out goes through a launch that resumes
-  rc = AZMI_OK;
-  for (uint32_t t = 0; t < T && rc == AZMI_OK; ++t) {
-    if (event[t]) launch_checkpoint(s, temp, pr, 0u, st);
-    rc = enqueue_step(s, a, K, rn, st);
-    if (rc == AZMI_OK) s->sims_done += K;
-  }
-  launch_checkpoint(s, temp, pr, 1u, st);
-  if (rc != AZMI_OK) return rc;
-  SB_TRY(hipGetLastError());
-  return AZMI_OK;
-}
-
-int azmi_search_checkpoints(azmi_search* s, uint32_t* taken_mask, uint32_t* root_n, uint32_t* counts, float* probs, float* root_values,
-                            float* root_q) {
-  int rc = begin_read(s, "checkpoints"); if (rc) return rc;
-  if (!s->sw_valid) return SB_FAIL(AZMI_ERR_STATE, "checkpoints: no search_to call has been made on this batch");
-  azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  rc = check_device(s, pm->last); if (rc) return rc;      // (synchronises)
-  const size_t N = s->n, J = s->sw.n_cp, M = pm->gi.M;
-  if (taken_mask) SB_TRY(hipMemcpy(taken_mask, s->sw.taken, N * 4, hipMemcpyDeviceToHost));
-  if (!J) return AZMI_OK;
-  if (root_n) SB_TRY(hipMemcpy(root_n, s->sw.root_n, N * J * 4, hipMemcpyDeviceToHost));
-  if (counts) SB_TRY(hipMemcpy(counts, s->sw.counts, N * J * M * 4, hipMemcpyDeviceToHost));
-  if (probs) SB_TRY(hipMemcpy(probs, s->sw.probs, N * J * M * 4, hipMemcpyDeviceToHost));
-  if (root_values) SB_TRY(hipMemcpy(root_values, s->sw.root_values, N * J * 3 * 4, hipMemcpyDeviceToHost));
-  if (root_q) SB_TRY(hipMemcpy(root_q, s->sw.root_q, N * J * M * 4, hipMemcpyDeviceToHost));
-  return AZMI_OK;
-}
-
-}  // extern "C"
-
 // ---- descents_per_step > 1: the kernels of search_batch_kernels.h's last section, instantiated behind everything else -------------
-namespace {
-
-void launch_todo_set(azmi_search* s, uint32_t visits, hipStream_t st) {
+void sb_launch_todo_set(azmi_search* s, uint32_t visits, hipStream_t st) {
   k_sb_todo_set<<<(s->n + 255) / 256, 256, 0, st>>>(s->sb, s->dl, s->n, visits);
   s->launches += 1;
 }
 
-void launch_find_dl(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, uint32_t eval_random, uint32_t root_noise,
+void sb_launch_find_dl(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, uint32_t eval_random, uint32_t root_noise,
                     hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_find_dl, k_sb_big_find_dl, ep, ar, s->sb, s->dl, s->n, s->dl_L, parity, eval_random, root_noise);
   if (eval_random) return;      // no row is ever pending: nothing to number
@@ -1031,7 +809,7 @@ void launch_find_dl(azmi_search* s, const EngineParams& ep, const EngineArrays& 
   s->launches += 1;
 }
 
-void launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, hipStream_t st) {
+void sb_launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const EngineArrays& ar, uint32_t parity, hipStream_t st) {
   const uint32_t n = s->n;
   SB_LAUNCH(s, st, k_sb_find_dl_po, k_sb_big_find_dl_po, ep, ar, s->sb, s->dl, s->ro, n, s->dl_L, parity);
   sb_for_game(s->pm->game,
@@ -1039,356 +817,60 @@ void launch_find_dl_playout(azmi_search* s, const EngineParams& ep, const Engine
               [&](auto) {});
 }
 
-}  // namespace
-
 // ---- frozen-set capture, first-occurrence dedup, net versus search: the kernels of search_pool_kernels.h, behind everything else ---
-namespace {
-
-void launch_capture(azmi_search* s, hipStream_t st) {
+void sb_launch_capture(azmi_search* s, hipStream_t st) {
   SB_LAUNCH(s, st, k_sb_capture, k_sb_big_capture, s->pm->ep, s->pm->ar, s->sb, s->pl, s->cp, s->n);
 }
 
-}  // namespace
-
-extern "C" {
-
-int azmi_search_set_capture(azmi_search* s, int on) {
-  if (!s) return SB_FAIL(AZMI_ERR_INVALID, "null argument");
-  if (on && !s->cp.key) {
-    azmi_pm* pm = s->pm;
-    SB_TRY(hipSetDevice(pm->device));
-    const size_t rows = static_cast<size_t>(s->n) * s->pl.log_cap;
-    SbCaptureArrays cp{};
-    int rc = pm->alloc(cp.key, rows, true);
-    if (rc == AZMI_OK) rc = pm->alloc(cp.player, rows, true);
-    if (rc == AZMI_OK) rc = pm->alloc(cp.variant, rows, true);
-    if (rc == AZMI_OK) rc = pm->alloc(cp.len, s->n, true);
-    if (rc != AZMI_OK) return rc;      // (what was allocated stays with the engine and is freed with it)
-    s->cp = cp;
-  }
-  s->capture = on != 0;
-  return AZMI_OK;
-}
-
-int azmi_search_capture_roots(azmi_search* s, void* stream) {
-  int rc = begin_move(s, "capture_roots"); if (rc) return rc;
-  if (!s->capture) return SB_FAIL(AZMI_ERR_STATE, "capture_roots: capture is off; call set_capture(true) first");
+void sb_launch_root_canon(azmi_search* s, hipStream_t st) {
   azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  launch_capture(s, pm->pick(stream));
-  SB_TRY(hipGetLastError());
-  return AZMI_OK;
-}
-
-int azmi_search_captured(azmi_search* s, uint64_t* key, uint8_t* player, int8_t* variant, uint32_t* len) {
-  int rc = begin_read(s, "captured"); if (rc) return rc;
-  if (!s->cp.key) return SB_FAIL(AZMI_ERR_STATE, "captured: capture was never on for this batch; call set_capture(true) before playing");
-  azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  rc = check_device(s, pm->last); if (rc) return rc;      // (synchronises)
-  const size_t rows = static_cast<size_t>(s->n) * s->pl.log_cap;
-  if (key) SB_TRY(hipMemcpy(key, s->cp.key, rows * 8, hipMemcpyDeviceToHost));
-  if (player) SB_TRY(hipMemcpy(player, s->cp.player, rows, hipMemcpyDeviceToHost));
-  if (variant) SB_TRY(hipMemcpy(variant, s->cp.variant, rows, hipMemcpyDeviceToHost));
-  if (len) SB_TRY(hipMemcpy(len, s->cp.len, static_cast<size_t>(s->n) * 4, hipMemcpyDeviceToHost));
-  return AZMI_OK;
-}
-
-int azmi_search_net_metrics(azmi_search* s, azmi_net* net, double* out, float* raw_v, float* raw_pi, uint8_t* valid, void* stream) {
-  int rc = begin_move(s, "net_vs_search"); if (rc) return rc;
-  if (!net) return SB_FAIL(AZMI_ERR_INVALID, "net_vs_search: needs a net");
-  azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  if (!s->d_nm_out) {
-    rc = pm->alloc(s->d_nm_valid, s->n, true); if (rc) return rc;
-    rc = pm->alloc(s->d_nm_out, static_cast<size_t>(s->n) * 3, true); if (rc) return rc;
-  }
-  hipStream_t st = pm->pick(stream);
-  const size_t N = s->n, V = pm->gi.P + 1, M = pm->gi.M;
-  // the step API's staging buffers are free (no step is pending): the roots' planes, the net's raw rows
   SB_LAUNCH(s, st, k_sb_root_canon, k_sb_big_root_canon, pm->ep, pm->ar, s->sb, s->n, s->d_batch, s->d_nm_valid);
-  rc = azmi_net_forward(net, s->d_batch, s->d_vrows, s->d_pirows, s->n, st);
-  if (rc != AZMI_OK) return SB_FAIL(rc, "leaf net: %s", azmi_net_last_error());
-  s->net_calls += 1;
+}
+
+void sb_launch_net_metrics(azmi_search* s, hipStream_t st) {
+  azmi_pm* pm = s->pm;
   SB_LAUNCH(s, st, k_sb_net_metrics, k_sb_big_net_metrics, pm->ep, pm->ar, s->n, s->d_nm_valid, s->d_vrows, s->d_pirows, s->d_nm_out, s->d_qf,
             s->vec_f, s->d_qu, s->vec_u);
-  SB_TRY(hipGetLastError());
-  if (out) SB_TRY(hipMemcpyAsync(out, s->d_nm_out, N * 3 * 8, hipMemcpyDeviceToHost, st));
-  if (raw_v) SB_TRY(hipMemcpyAsync(raw_v, s->d_vrows, N * V * 4, hipMemcpyDeviceToHost, st));
-  if (raw_pi) SB_TRY(hipMemcpyAsync(raw_pi, s->d_pirows, N * M * 4, hipMemcpyDeviceToHost, st));
-  if (valid) SB_TRY(hipMemcpyAsync(valid, s->d_nm_valid, N, hipMemcpyDeviceToHost, st));
-  return check_device(s, st);      // the one synchronisation
 }
 
-int azmi_pool_unique(const uint64_t* keys, const uint8_t* valid, uint32_t n, uint32_t* first_index_out, uint32_t* n_unique, uint32_t* n_duplicates,
-                     int device, void* stream) {
-  if (n > kPoolMaxRecords)
-    return SB_FAIL(AZMI_ERR_INVALID, "azmi_pool_unique: n = %u records: the table takes a power of two of at least 2 n slots indexed by 32 bits, "
-                   "at most %u records", n, kPoolMaxRecords);
-  if (!n_unique || !n_duplicates || (n && (!keys || !first_index_out))) return SB_FAIL(AZMI_ERR_INVALID, "azmi_pool_unique: null argument");
-  *n_unique = 0; *n_duplicates = 0;
-  if (n == 0) return AZMI_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SB_FAIL(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
-  if (device < 0 || device >= ndev) return SB_FAIL(AZMI_ERR_INVALID, "device %d out of range", device);
-  SB_TRY(hipSetDevice(device));
-  hipStream_t st = stream == AZMI_STREAM_ENGINE ? nullptr : static_cast<hipStream_t>(stream);
-  uint32_t slots = 64;
-  while (slots < 2u * n) slots <<= 1;
-  DevTemps tmp;
-  uint64_t* d_keys = nullptr; uint8_t* d_valid = nullptr; uint32_t *d_owner = nullptr, *d_first = nullptr, *d_slot_of = nullptr, *d_out = nullptr, *d_counts = nullptr;
-  std::vector<uint8_t> all;
-  if (!valid) { all.assign(n, 1); valid = all.data(); }
-  AZMI_HIP_TRY_NODEV(tmp.upload_async(d_keys, keys, n, st));
-  hipError_t e = tmp.upload_async(d_valid, valid, n, st);
-  if (e == hipSuccess) e = tmp.alloc(d_owner, slots);
-  if (e == hipSuccess) e = tmp.alloc(d_first, slots);
-  if (e == hipSuccess) e = tmp.alloc(d_slot_of, n);
-  if (e == hipSuccess) e = tmp.alloc(d_out, n);
-  if (e == hipSuccess) e = tmp.alloc(d_counts, 2);
-  if (e == hipSuccess) e = hipMemsetAsync(d_owner, 0xFF, static_cast<size_t>(slots) * 4, st);      // kPoolEmpty
-  if (e == hipSuccess) e = hipMemsetAsync(d_first, 0xFF, static_cast<size_t>(slots) * 4, st);
-  if (e == hipSuccess) {
-    k_pool_claim<<<(n + 255u) / 256u, 256, 0, st>>>(d_keys, d_valid, n, slots - 1u, d_owner, d_first, d_slot_of);
-    k_pool_compact<<<1, 1024, 0, st>>>(d_valid, n, d_first, d_slot_of, d_out, d_counts);
-    e = hipGetLastError();
-  }
-  uint32_t counts[2] = {0, 0};
-  if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(first_index_out, d_out, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);      // always: what was queued reads the buffers tmp is about to free
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return SB_FAIL(e == hipErrorOutOfMemory ? AZMI_ERR_OOM : AZMI_ERR_NO_DEVICE, "azmi_pool_unique: %s", hipGetErrorString(e));
-  *n_unique = counts[0]; *n_duplicates = counts[1];
-  return AZMI_OK;
+void sb_launch_pool_claim(const uint64_t* d_keys, const uint8_t* d_valid, uint32_t n, uint32_t mask, uint32_t* d_owner, uint32_t* d_first,
+                          uint32_t* d_slot_of, hipStream_t st) {
+  k_pool_claim<<<(n + 255u) / 256u, 256, 0, st>>>(d_keys, d_valid, n, mask, d_owner, d_first, d_slot_of);
 }
 
-}  // extern "C"
+void sb_launch_pool_compact(const uint8_t* d_valid, uint32_t n, const uint32_t* d_first, const uint32_t* d_slot_of, uint32_t* d_out, uint32_t* d_counts,
+                            hipStream_t st) {
+  k_pool_compact<<<1, 1024, 0, st>>>(d_valid, n, d_first, d_slot_of, d_out, d_counts);
+}
 
 // ---- opening-tree frontier: the kernels of search_frontier_kernels.h, behind everything else -------------------------------------
-namespace {
-
-// the per-tree block (first call) and room for `cap` records (first call, and whenever a call asks for more)
-int frontier_reserve(azmi_search* s, uint32_t cap) {
-  const size_t N = s->n, M = s->pm->gi.M, V = s->pm->gi.P + 1;
-  if (!s->fr_trees) {
-    void* q = nullptr;
-    const size_t bytes = 8 * (2 * N + 2 * N * M + N + 3 * N + N) + 4 * (N + (N + 1) + 1) + (N + N * M);
-    SB_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->fr_host), 2 * N * sizeof(double), hipHostMallocDefault));
-    SB_TRY(hipEventCreateWithFlags(&s->fr_uploaded, hipEventDisableTiming));
-    SB_TRY(hipMalloc(&q, bytes));
-    s->fr_trees = q;
-    double* d = static_cast<double*>(q);
-    s->fr.reach = d; d += N;
-    s->fr.temp = d; d += N;
-    s->fr.raw_pi = d; d += N * M;
-    s->fr.samp_pi = d; d += N * M;
-    s->fr.entropy = d; d += N;
-    s->fr.value = d; d += 3 * N;
-    s->fr.key = reinterpret_cast<uint64_t*>(d); d += N;
-    uint32_t* w = reinterpret_cast<uint32_t*>(d);
-    s->fr.kept = w; w += N;
-    s->fr.first_child = w; w += N + 1;
-    s->fr.total = w; w += 1;
-    uint8_t* b = reinterpret_cast<uint8_t*>(w);
-    s->fr.kind = b; b += N;
-    s->fr.keep = b;
-  }
-  if (!s->fr_records || cap > s->fr_cap) {
-    void* q = nullptr;
-    const size_t C = cap;
-    SB_TRY(hipMalloc(&q, C * (8 + 8 + 4 + 4 + 4 * V + 3)));
-    if (s->fr_records) (void)hipFree(s->fr_records);      // (waits for the device)
-    s->fr_records = q; s->fr_cap = cap;
-    double* d = static_cast<double*>(q);
-    s->fr.child_reach = d; d += C;
-    s->fr.child_key = reinterpret_cast<uint64_t*>(d); d += C;
-    uint32_t* w = reinterpret_cast<uint32_t*>(d);
-    s->fr.parent = w; w += C;
-    s->fr.action = w; w += C;
-    s->fr.child_scores = reinterpret_cast<float*>(w); w += C * V;
-    uint8_t* b = reinterpret_cast<uint8_t*>(w);
-    s->fr.child_player = b; b += C;
-    s->fr.child_variant = reinterpret_cast<int8_t*>(b); b += C;
-    s->fr.child_terminal = b;
-  }
-  return AZMI_OK;
+void sb_launch_frontier_policy(azmi_search* s, double min_reach, hipStream_t st) {
+  azmi_pm* pm = s->pm;
+  SB_LAUNCH(s, st, k_sb_frontier_policy, k_sb_big_frontier_policy, pm->ep, pm->ar, s->sb, s->fr, s->n, min_reach, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
 }
 
-}  // namespace
-
-extern "C" {
-
-int azmi_search_expand(azmi_search* s, const double* reach, const double* temp, double min_reach, uint32_t max_children, void* stream) {
-  int rc = begin_move(s, "expand_frontier"); if (rc) return rc;
-  if (!reach || !temp) return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: null argument");
-  if (!(min_reach > 0.0) || !std::isfinite(min_reach)) return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: min_reach must be positive and finite, got %g", min_reach);
-  if (max_children == 0) return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: max_children must be > 0");
-  for (uint32_t i = 0; i < s->n; ++i) {
-    if (!(reach[i] >= 0.0) || !std::isfinite(reach[i]))
-      return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: tree %u: reach must be finite and not negative, got %g", i, reach[i]);
-    if (!(temp[i] >= 0.0) || !std::isfinite(temp[i]))
-      return SB_FAIL(AZMI_ERR_INVALID, "expand_frontier: tree %u: temp must be finite and not negative, got %g", i, temp[i]);
-  }
-  azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  const bool first = s->fr_host == nullptr;
-  rc = frontier_reserve(s, max_children); if (rc) return rc;
-  hipStream_t st = pm->pick(stream);
-  const size_t N = s->n;
-  if (!first) SB_TRY(hipEventSynchronize(s->fr_uploaded));      // the previous call's upload may still read fr_host
-  std::memcpy(s->fr_host, reach, N * sizeof(double));
-  std::memcpy(s->fr_host + N, temp, N * sizeof(double));
-  SB_TRY(hipMemcpyAsync(const_cast<double*>(s->fr.reach), s->fr_host, 2 * N * sizeof(double), hipMemcpyHostToDevice, st));      // (reach | temp are neighbours)
-  SB_TRY(hipEventRecord(s->fr_uploaded, st));
-  s->fr.max_children = max_children;
-  s->fr_valid = true;
-  SB_LAUNCH(s, st, k_sb_frontier_policy, k_sb_big_frontier_policy, pm->ep, pm->ar, s->sb, s->fr, s->n, min_reach, s->d_qf, s->vec_f, s->d_qu, s->vec_u);
+void sb_launch_frontier_scan(azmi_search* s, hipStream_t st) {
   k_frontier_scan<1024><<<1, 1024, 0, st>>>(s->fr.kept, s->n, s->fr.first_child, s->fr.total);
   s->launches += 1;
-  SB_LAUNCH(s, st, k_sb_frontier_emit, k_sb_big_frontier_emit, pm->ep, pm->ar, s->fr, s->n);
-  SB_TRY(hipGetLastError());
-  return AZMI_OK;
 }
 
-int azmi_search_frontier(azmi_search* s, uint8_t* kind, uint64_t* key, double* raw_pi, double* sampling_pi, double* entropy, double* value,
-                         uint32_t* first_child, uint32_t* parent, uint32_t* action, double* child_reach, uint64_t* child_key, uint8_t* child_player,
-                         int8_t* child_variant, uint8_t* child_terminal, float* child_scores) {
-  int rc = begin_read(s, "frontier"); if (rc) return rc;
-  if (!s->fr_valid) return SB_FAIL(AZMI_ERR_STATE, "frontier: no expand_frontier call has been made on this batch");
+void sb_launch_frontier_emit(azmi_search* s, hipStream_t st) {
   azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  hipStream_t st = pm->last;
-  uint32_t total = 0;
-  SB_TRY(hipMemcpyAsync(&total, s->fr.total, 4, hipMemcpyDeviceToHost, st));
-  rc = check_device(s, st); if (rc) return rc;      // the one synchronisation
-  const size_t N = s->n, M = pm->gi.M, V = pm->gi.P + 1;
-  if (kind) SB_TRY(hipMemcpy(kind, s->fr.kind, N, hipMemcpyDeviceToHost));
-  if (key) SB_TRY(hipMemcpy(key, s->fr.key, N * 8, hipMemcpyDeviceToHost));
-  if (raw_pi) SB_TRY(hipMemcpy(raw_pi, s->fr.raw_pi, N * M * 8, hipMemcpyDeviceToHost));
-  if (sampling_pi) SB_TRY(hipMemcpy(sampling_pi, s->fr.samp_pi, N * M * 8, hipMemcpyDeviceToHost));
-  if (entropy) SB_TRY(hipMemcpy(entropy, s->fr.entropy, N * 8, hipMemcpyDeviceToHost));
-  if (value) SB_TRY(hipMemcpy(value, s->fr.value, N * 3 * 8, hipMemcpyDeviceToHost));
-  if (first_child) SB_TRY(hipMemcpy(first_child, s->fr.first_child, (N + 1) * 4, hipMemcpyDeviceToHost));
-  if (total > s->fr.max_children)
-    return SB_FAIL(AZMI_ERR_OVERFLOW, "frontier: the trees keep %u children, max_children = %u: the first %u records were written; expand again "
-                   "with room for all of them", total, s->fr.max_children, s->fr.max_children);
-  const size_t T = total;
-  if (!T) return AZMI_OK;
-  if (parent) SB_TRY(hipMemcpy(parent, s->fr.parent, T * 4, hipMemcpyDeviceToHost));
-  if (action) SB_TRY(hipMemcpy(action, s->fr.action, T * 4, hipMemcpyDeviceToHost));
-  if (child_reach) SB_TRY(hipMemcpy(child_reach, s->fr.child_reach, T * 8, hipMemcpyDeviceToHost));
-  if (child_key) SB_TRY(hipMemcpy(child_key, s->fr.child_key, T * 8, hipMemcpyDeviceToHost));
-  if (child_player) SB_TRY(hipMemcpy(child_player, s->fr.child_player, T, hipMemcpyDeviceToHost));
-  if (child_variant) SB_TRY(hipMemcpy(child_variant, s->fr.child_variant, T, hipMemcpyDeviceToHost));
-  if (child_terminal) SB_TRY(hipMemcpy(child_terminal, s->fr.child_terminal, T, hipMemcpyDeviceToHost));
-  if (child_scores) SB_TRY(hipMemcpy(child_scores, s->fr.child_scores, T * V * 4, hipMemcpyDeviceToHost));
-  return AZMI_OK;
+  SB_LAUNCH(s, st, k_sb_frontier_emit, k_sb_big_frontier_emit, pm->ep, pm->ar, s->fr, s->n);
 }
-
-}  // extern "C"
 
 // ---- sweep metrics: the kernels of search_sweep_metrics_kernels.h, behind everything else ------------------------------------------
-namespace {
-
-// the output block of azmi_search_sweep_metrics for the J checkpoints of the current snapshot set
-struct SweepMetricsOut {
-  double *rows, *ceiling, *mean, *outcomes;
-  uint32_t* count;
-  uint8_t* valid;
-};
-
-int sweep_metrics_reserve(azmi_search* s, uint32_t j, SweepMetricsOut* o) {
-  const size_t N = s->n;
-  if (!s->sm_block || j > s->sm_cap) {
-    const size_t cap = std::max<uint32_t>(j, 1u);
-    void* q = nullptr;
-    SB_TRY(hipMalloc(&q, 8 * (N * cap * kSweepCols + 2 * N + cap * kSweepCols) + 4 * cap * kSweepCols + N * cap));
-    if (s->sm_block) (void)hipFree(s->sm_block);      // (waits for the device)
-    s->sm_block = q; s->sm_cap = static_cast<uint32_t>(cap);
-  }
-  const size_t cap = s->sm_cap;
-  double* d = static_cast<double*>(s->sm_block);
-  o->rows = d; d += N * cap * kSweepCols;
-  o->ceiling = d; d += N;
-  o->mean = d; d += cap * kSweepCols;
-  o->outcomes = d; d += N;
-  o->count = reinterpret_cast<uint32_t*>(d);
-  o->valid = reinterpret_cast<uint8_t*>(o->count + cap * kSweepCols);
-  return AZMI_OK;
+void sb_launch_sweep_metrics(azmi_search* s, const azmi_search* ref, uint32_t anchor, int32_t raw, const double* d_outcomes, const SweepMetricsOut& o,
+                             hipStream_t st) {
+  SB_LAUNCH(s, st, k_sb_sweep_metrics, k_sb_big_sweep_metrics, s->sw, ref->sw, s->n, anchor, raw, d_outcomes, o.rows, o.ceiling, o.valid);
 }
 
-}  // namespace
-
-extern "C" {
-
-int azmi_search_sweep_metrics(azmi_search* s, azmi_search* ref, uint32_t anchor, int32_t raw, const double* outcomes, double* out_rows,
-                              double* out_tree, double* out_mean, uint32_t* out_count, uint8_t* valid, void* stream) {
-  int rc = begin_move(s, "sweep_metrics"); if (rc) return rc;
-  if (!ref) ref = s;
-  if (!s->sw_valid) return SB_FAIL(AZMI_ERR_STATE, "sweep_metrics: no search_to call has been made on this batch");
-  if (!ref->sw_valid) return SB_FAIL(AZMI_ERR_STATE, "sweep_metrics: no search_to call has been made on the reference batch");
-  if (ref->step_pending) return SB_FAIL(AZMI_ERR_STATE, "sweep_metrics: a find_leaves step is pending on the reference batch; call process_results first");
-  if (ref->pm->game != s->pm->game || ref->n != s->n || ref->pm->device != s->pm->device)
-    return SB_FAIL(AZMI_ERR_INVALID, "sweep_metrics: the reference batch must hold the same game, tree count and device (game %d, %u trees, "
-                   "device %d against game %d, %u trees, device %d)", ref->pm->game, ref->n, ref->pm->device, s->pm->game, s->n, s->pm->device);
-  const uint32_t J = s->sw.n_cp, Jr = ref->sw.n_cp;
-  if (anchor >= Jr) return SB_FAIL(AZMI_ERR_INVALID, "sweep_metrics: anchor %u out of range: the reference set has %u checkpoints", anchor, Jr);
-  if (raw < -1 || (raw >= 0 && static_cast<uint32_t>(raw) >= Jr))
-    return SB_FAIL(AZMI_ERR_INVALID, "sweep_metrics: raw %d out of range: -1 for none, or one of the reference set's %u checkpoints", raw, Jr);
-  azmi_pm* pm = s->pm;
-  SB_TRY(hipSetDevice(pm->device));
-  hipStream_t prev = pm->last;
-  hipStream_t st = pm->pick(stream);
-  if (prev != st) SB_TRY(hipStreamSynchronize(prev));                              // the snapshots may still be on their way
-  if (ref != s && ref->pm->last != st) SB_TRY(hipStreamSynchronize(ref->pm->last));
-  SweepMetricsOut o;
-  rc = sweep_metrics_reserve(s, J, &o); if (rc) return rc;
-  const size_t N = s->n;
-  if (outcomes) SB_TRY(hipMemcpyAsync(o.outcomes, outcomes, N * 8, hipMemcpyHostToDevice, st));
-  SB_LAUNCH(s, st, k_sb_sweep_metrics, k_sb_big_sweep_metrics, s->sw, ref->sw, s->n, anchor, raw, outcomes ? o.outcomes : nullptr, o.rows, o.ceiling,
-            o.valid);
+void sb_launch_sweep_mean(azmi_search* s, uint32_t J, const SweepMetricsOut& o, hipStream_t st) {
   k_sb_sweep_mean<<<std::max(J, 1u), kSweepMeanThreads, 0, st>>>(o.rows, s->n, J, o.mean, o.count);
   s->launches += 1;
-  SB_TRY(hipGetLastError());
-  if (out_tree) SB_TRY(hipMemcpyAsync(out_tree, o.ceiling, N * 8, hipMemcpyDeviceToHost, st));
-  if (J) {
-    if (out_rows) SB_TRY(hipMemcpyAsync(out_rows, o.rows, N * J * kSweepCols * 8, hipMemcpyDeviceToHost, st));
-    if (out_mean) SB_TRY(hipMemcpyAsync(out_mean, o.mean, static_cast<size_t>(J) * kSweepCols * 8, hipMemcpyDeviceToHost, st));
-    if (out_count) SB_TRY(hipMemcpyAsync(out_count, o.count, static_cast<size_t>(J) * kSweepCols * 4, hipMemcpyDeviceToHost, st));
-    if (valid) SB_TRY(hipMemcpyAsync(valid, o.valid, N * J, hipMemcpyDeviceToHost, st));
-  }
-  return check_device(s, st);      // the one synchronisation
 }
 
-int azmi_policy_divergences(const float* p, const float* q, uint32_t rows, uint32_t M, double* out, int device, void* stream) {
-  constexpr uint32_t kMaxRows = 1u << 30, kMaxMoves = 1u << 20;
-  if (rows > kMaxRows || M == 0 || M > kMaxMoves)
-    return SB_FAIL(AZMI_ERR_INVALID, "azmi_policy_divergences: rows = %u, M = %u: at most %u rows of 1 to %u moves", rows, M, kMaxRows, kMaxMoves);
-  if (rows && (!p || !q || !out)) return SB_FAIL(AZMI_ERR_INVALID, "azmi_policy_divergences: null argument");
-  if (rows == 0) return AZMI_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SB_FAIL(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
-  if (device < 0 || device >= ndev) return SB_FAIL(AZMI_ERR_INVALID, "device %d out of range", device);
-  SB_TRY(hipSetDevice(device));
-  hipStream_t st = stream == AZMI_STREAM_ENGINE ? nullptr : static_cast<hipStream_t>(stream);
-  const size_t cells = static_cast<size_t>(rows) * M;
-  DevTemps tmp;
-  float *d_p = nullptr, *d_q = nullptr;
-  double* d_out = nullptr;
-  AZMI_HIP_TRY_NODEV(tmp.upload_async(d_p, p, cells, st));
-  hipError_t e = tmp.upload_async(d_q, q, cells, st);
-  if (e == hipSuccess) e = tmp.alloc(d_out, static_cast<size_t>(rows) * kPolicyCols);
-  if (e == hipSuccess) {
-    if (M <= 8) k_policy_divergences<8><<<(rows + 31u) / 32u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
-    else k_policy_divergences<64><<<(rows + 3u) / 4u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, static_cast<size_t>(rows) * kPolicyCols * 8, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);      // always: what was queued reads the buffers tmp is about to free
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return SB_FAIL(e == hipErrorOutOfMemory ? AZMI_ERR_OOM : AZMI_ERR_NO_DEVICE, "azmi_policy_divergences: %s", hipGetErrorString(e));
-  return AZMI_OK;
+void sb_launch_policy_divergences(const float* d_p, const float* d_q, uint32_t rows, uint32_t M, double* d_out, hipStream_t st) {
+  if (M <= 8) k_policy_divergences<8><<<(rows + 31u) / 32u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
+  else k_policy_divergences<64><<<(rows + 3u) / 4u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
 }
-
-}  // extern "C"

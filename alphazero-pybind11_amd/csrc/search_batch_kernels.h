@@ -19,35 +19,9 @@
 // in most of them.  Shared is what compiles to the same code: the seed kernels' tail and the compaction kernels' scan.
 #pragma once
 #include "mcts_object_kernels.h"
+#include "search_batch_types.h"      // SbPend, SbStatus, kNoRow and the Sb*Arrays views named below
 
 namespace azmi {
-
-enum SbPend : uint8_t {
-  kPendNone = 0,    // nothing to back up: terminal leaf (backed up by the find kernel), or a stopped tree
-  kPendRow = 1,     // the leaf's planes are in the slot's canonical row: the evaluator's answer is awaited
-  kPendCached = 2,  // a cache hit: the answer is already in the slot's (v, pi) rows
-  kPendRandom = 3,  // EvalType::RANDOM: process_result synthesises dumb_eval
-  kPendRollout = 4  // EvalType::PLAYOUT: the answer of the leaf's rollout is (Connect4: will be, behind k_sb_rollout) in the slot's (v, pi) rows
-};
-enum SbStatus : int32_t {
-  kSbFinished = 1,     // the game is over
-  kSbPaused = 2,       // the tree has reached its target of the running search_to call: set and cleared by the checkpoint kernels alone
-  kSbBadStart = -1,    // bad start position
-  kSbFindFailed = -2,  // find_leaf failed: arena / path capacity
-  kSbBadMove = -3,     // update_root was given a move the root does not have
-  kSbNoVisits = -4,    // a move was asked of a root without visits
-  kSbBadState = -5     // the root state did not take a move its tree has
-};
-constexpr uint32_t kNoRow = 0xFFFFFFFFu;
-
-struct SbArrays {
-  uint8_t* pend;       // [N]
-  int32_t* status;     // [N]
-  uint32_t* row_of;    // [N]
-  uint32_t* rows;      // [N]
-  uint32_t* n_rows;    // [1]
-  uint32_t* n_term;    // [N] simulations that ended in a terminal leaf since the last reset
-};
 
 // ---- seed: N serialized positions -> N root states, N empty trees, one pcg32 stream per tree -----------------------------
 // moves[offs[i] .. offs[i + 1]) are tree i's moves from its start position (init + i * init_stride, NULL = initial position)
@@ -280,18 +254,7 @@ __global__ __launch_bounds__(64) void k_sb_big_process(EngineParams ep, EngineAr
 // attempt count fixed at K.  Descent k of tree i owns entry k * N + i ("[K][N]-major") of every step-sized array, so that an
 // EngineArrays copy whose canon / v / pi / cache_keys pointers are moved by k * N rows makes emit_leaf, cache_lookup,
 // process_result and k_cache_insert, which address rows by slot, work on that entry.  The VISIBLE row order is ascending tree,
-// then descent: k_sb_compact_wu numbers the pending entries in that order.
-struct SbWuArrays {
-  WuArrays wu;         // nif [N * P * cap]; in-flight records [K * N]: ifl_path[max_depth], ifl_plen, ifl_cur
-  uint8_t* pend;       // [K * N] SbPend of descent k of tree i (kPendRow or kPendNone: everything else is backed up by the find kernel)
-  uint32_t* row_of;    // [K * N] compacted row of the entry (kNoRow = none)
-  uint32_t* rows;      // [K * N] entry of compacted row r: the net's row list
-  uint32_t* tree_of;   // [K * N] tree of compacted row r (ascending, with repeats)
-  float* canon;        // [K * N, C, H, W]
-  float* v;            // [K * N, P + 1]
-  float* pi;           // [K * N, M]
-  uint64_t* keys;      // [K * N] cache keys of the evaluated entries (0 = none)
-};
+// then descent: k_sb_compact_wu numbers the pending entries in that order.  (SbWuArrays)
 
 // `al` is the kernel's own copy of the engine arrays that the slot context reads through: entry (k, slot) becomes "the slot's row"
 __device__ __forceinline__ void sb_wu_point(EngineArrays& al, const SbWuArrays& w, size_t row0, uint32_t chw, uint32_t nv, uint32_t np) {
@@ -540,13 +503,7 @@ __global__ __launch_bounds__(64) void k_sb_big_query(EngineParams ep, EngineArra
 //                  pick was consumed by an update-root launch: an update_roots without a pick before it moves nothing)
 //   log[i][0..len) the moves played on tree i since reset (capacity log_cap = max_turns + 8), log_len[i] = len
 //   final[i][P+1]  GameState::scores() of a finished tree
-struct SbPlayArrays {
-  int32_t* move;       // [N]
-  int32_t* log;        // [N, log_cap]
-  uint32_t* log_len;   // [N]
-  float* final;        // [N, P + 1]
-  uint32_t log_cap;
-};
+// (SbPlayArrays)
 
 // what the two update-root kernels share once the tree is re-rooted and `mv` is played: move log, finished rule
 template <class GM, class State>
@@ -734,11 +691,7 @@ __global__ __launch_bounds__(64) void k_sb_big_root_prior(EngineParams ep, Engin
 //   K > 1              a playout leaf is an immediate: its process_result_batched runs before the tree's next descent, which has to
 //                      see the back-up and not the in-flight mark (play.py:306-307).  So the rollout sits between two descents of
 //                      one tree, inside the *_find_wu_po loop, and a step is 1 launch
-struct SbRollArrays {
-  uint64_t* seeds;     // [N] rollout_seeds
-  uint32_t* count;     // [N] rollouts of tree i since the last reset: the j of its next one
-  uint8_t* states;     // [N] GM::State (Connect4, K == 1): the leaf that awaits k_sb_rollout
-};
+// (SbRollArrays: the rollout seed and count of every tree, the parked leaf states)
 __host__ __device__ __forceinline__ uint64_t sb_rollout_seed(uint64_t tree_seed, uint32_t j) {
   return mix64(tree_seed + kRollSalt * (static_cast<uint64_t>(j) + 1));
 }
@@ -924,20 +877,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find_wu_po(EngineParams ep, Engin
 //   taken[i]      bit j: snapshot j of tree i is taken; it is taken once, at the first launch that sees root_n(i) >= cps[j]
 //   root_n / counts / probs / root_values / root_q   row (i, j) of [N, J] / [N, J, M] / [N, J, M] / [N, J, 3] / [N, J, M]
 // The rows are written by the read-out bodies of kinds 0, 1 | 2, 3, 4 (mcts_query_slot / mcts_big_query_slot), the same bodies
-// the pick kernel reuses; rows that were not taken keep the zeros the host cleared them to.
-constexpr uint32_t kSbMaxCheckpoints = 32;
-
-struct SbSweepArrays {
-  uint32_t* target;     // [N]
-  uint32_t* cps;        // [kSbMaxCheckpoints]
-  uint32_t* taken;      // [N]
-  uint32_t* root_n;     // [N, J]
-  uint32_t* counts;     // [N, J, M]
-  float* probs;         // [N, J, M]
-  float* root_values;   // [N, J, 3]
-  float* root_q;        // [N, J, M]
-  uint32_t n_cp;        // J
-};
+// the pick kernel reuses; rows that were not taken keep the zeros the host cleared them to.  (SbSweepArrays, kSbMaxCheckpoints)
 
 // what both checkpoint kernels end with: pause at the target, resume at the end of the call (lane 0 of the tree)
 __device__ __forceinline__ void sb_checkpoint_tail(const SbArrays& sb, const SbSweepArrays& sw, uint32_t slot, int32_t status, uint32_t root_n,
@@ -1030,10 +970,7 @@ __global__ __launch_bounds__(64) void k_sb_big_checkpoint(EngineParams ep, Engin
 //   todo_max[2]   the largest todo a step leaves behind, by step parity: the find kernel of step t raises word t & 1 with one
 //                 atomicMax per tree that still owes descents and clears word (t + 1) & 1 for the step behind it, so the word
 //                 costs no launch of its own.  The host reads word t & 1 behind step t: 0 = the search is complete
-struct SbDlArrays {
-  uint32_t* todo;       // [N]
-  uint32_t* todo_max;   // [2]
-};
+// (SbDlArrays)
 
 __global__ __launch_bounds__(256) void k_sb_todo_set(SbArrays sb, SbDlArrays dl, uint32_t n, uint32_t visits) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -12,34 +12,7 @@
 
 namespace azmi {
 
-//   reach[i], temp[i]       the caller's reach probability and sampling temperature of tree i
-//   kind[i]                 0 a searched live root, 1 a terminal root (value = its scores, no children), 2 the tree takes no part
-//                           (finished, stopped or reach == 0: zero rows)
-//   keep[i][a]              move a of tree i is kept; kept[i] = how many are
-//   record r of tree i      first_child[i] <= r < first_child[i + 1], ascending action; r >= max_children is not written
-struct SbFrontierArrays {
-  const double* reach;     // [N]
-  const double* temp;      // [N]
-  uint8_t* kind;           // [N]
-  uint64_t* key;           // [N]
-  double* raw_pi;          // [N, M]
-  double* samp_pi;         // [N, M]
-  uint8_t* keep;           // [N, M]
-  double* entropy;         // [N]
-  double* value;           // [N, 3]
-  uint32_t* kept;          // [N]
-  uint32_t* first_child;   // [N + 1]
-  uint32_t* total;         // [1]
-  uint32_t* parent;        // [max_children] ...
-  uint32_t* action;
-  double* child_reach;
-  uint64_t* child_key;
-  uint8_t* child_player;
-  int8_t* child_variant;   // -1 for a game without variants
-  uint8_t* child_terminal;
-  float* child_scores;     // [max_children, P + 1]
-  uint32_t max_children;
-};
+// (the arrays: SbFrontierArrays, search_batch_types.h)
 
 // The sum of one float64 term per move over the L lanes of a tree; `acc` is the lane's own strided sum.  With M <= L lane m holds
 // term m alone and the terms are added in ascending move order, numpy's order for fewer than 8 terms; otherwise the lanes' sums

@@ -14,16 +14,7 @@
 
 namespace azmi {
 
-// ======================= root capture =================================================================================================
-//   key[i][p], player[i][p], variant[i][p]   the root of tree i when it had played p moves since reset (p < log_cap)
-//   len[i]                                   1 + the largest ply captured of tree i since reset
-struct SbCaptureArrays {
-  uint64_t* key;       // [N, log_cap]
-  uint8_t* player;     // [N, log_cap]
-  int8_t* variant;     // [N, log_cap]  -1 for a game without variants
-  uint32_t* len;       // [N]
-};
-
+// ======================= root capture (SbCaptureArrays, search_batch_types.h) ===========================================================
 // one lane records; capturing the same ply again stores the same values
 __device__ __forceinline__ void sb_capture_store(const SbCaptureArrays& cp, const SbPlayArrays& pl, uint32_t slot, uint64_t key, uint32_t player,
                                                  int32_t variant) {
@@ -65,10 +56,7 @@ __global__ __launch_bounds__(64) void k_sb_big_capture(EngineParams ep, EngineAr
 // keys themselves stay in the input array, which nobody writes, so a key of 0 is a key like any other and no 64-bit atomic is
 // needed.  Which record claims a slot, and therefore where a key sits, depends on scheduling; first[slot] = the smallest index
 // among the records of that key (atomicMin) does not, and k_pool_compact emits exactly the records that are their key's smallest
-// index, in ascending order, from one workgroup.
-constexpr uint32_t kPoolEmpty = 0xFFFFFFFFu;
-constexpr uint32_t kPoolMaxRecords = 1u << 30;      // 2 n slots indexed by 32 bits
-
+// index, in ascending order, from one workgroup.  (kPoolEmpty, kPoolMaxRecords: search_batch_types.h)
 __global__ __launch_bounds__(256) void k_pool_claim(const uint64_t* keys, const uint8_t* valid, uint32_t n, uint32_t mask, uint32_t* owner,
                                                     uint32_t* first, uint32_t* slot_of) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

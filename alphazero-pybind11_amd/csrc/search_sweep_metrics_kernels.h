@@ -23,13 +23,7 @@
 
 namespace azmi {
 
-// the columns of a row, in the order of azmi_search_sweep_metrics' out_rows
-enum SweepCol : uint32_t {
-  kSwJsd = 0, kSwTv, kSwHellinger, kSwTop1, kSwTop3, kSwTop9,      // the six of azmi_policy_divergences, in its order
-  kSwReward, kSwRegret, kSwPressure, kSwBenefit, kSwEntropy, kSwValueGap, kSwAbsErr, kSwCloserAnchor, kSwCloserRaw,
-  kSweepCols
-};
-constexpr uint32_t kPolicyCols = 6;
+// (the columns of a row: SweepCol, kSweepCols, kPolicyCols in search_batch_types.h)
 constexpr uint32_t kSwNone = 0xFFFFFFFFu;
 
 __device__ __forceinline__ double sw_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
@@ -222,9 +216,7 @@ __global__ __launch_bounds__(64) void k_sb_big_sweep_metrics(SbSweepArrays sw, S
 // ======================= the means of a checkpoint ======================================================================================
 // One workgroup per checkpoint j; for every column, mean[j, c] over the trees whose row (i, j) is not NaN there and count[j, c]
 // of them (NaN mean for a count of 0).  Lane t adds trees t, t + 256, ... in ascending order, then a fixed-shape LDS tree folds
-// the 256 partial sums: the result depends on n alone, never on scheduling.  No floating-point atomics.
-constexpr uint32_t kSweepMeanThreads = 256;
-
+// the 256 partial sums (kSweepMeanThreads): the result depends on n alone, never on scheduling.  No floating-point atomics.
 __global__ __launch_bounds__(256) void k_sb_sweep_mean(const double* rows, uint32_t n, uint32_t J, double* mean, uint32_t* count) {
   __shared__ double s_sum[kSweepMeanThreads];
   __shared__ uint32_t s_cnt[kSweepMeanThreads];

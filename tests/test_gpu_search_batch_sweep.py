@@ -376,3 +376,35 @@ def test_the_object_is_as_before_after_search_to(az):
             _assert_snaps(snap, i, want, 1, "behind a move")
             _assert_final(out, i, ms[i], "behind a move")
     assert not mb.finished()[[i for i in range(n) if live[i]]].any()
+
+
+# ---- 9. the snapshot block and the metric block regrow on a live batch ---------------------------------------------------------------
+def _bits_of(x):
+    if isinstance(x, dict):
+        return {k: _bits_of(v) for k, v in x.items()}
+    a = np.asarray(x)
+    return a.dtype.str, a.shape, a.tobytes()
+
+
+@pytest.mark.parametrize("name,n", [("Connect4GS", 3), ("BrandubhGS", 2)])
+def test_more_checkpoints_then_fewer_on_one_batch_equal_fresh_batches(az, name, n):
+    """One checkpoint, then four (the snapshot block and the sweep-metrics block are allocated again, larger, and cut again),
+    then one (the grown blocks serve fewer): snapshots and sweep_metrics of every call on the one batch are the bits of the
+    same call on a batch created for it.  8 visits, evaluator="random"."""
+    Game = getattr(az, name)
+    seeds = [900 + 7 * i for i in range(n)]
+
+    def run(mb, cps):
+        states = [Game() for _ in range(n)]
+        for skip, g in enumerate(states[1:]):
+            g.play_move(int(np.flatnonzero(g.valid_moves())[skip]))
+        mb.reset(states)
+        mb.search_to(8, evaluator="random", checkpoints=cps)
+        snap = mb.checkpoints()
+        assert snap["taken"].shape == (n, len(cps)) and snap["taken"].all()
+        return _bits_of(snap), _bits_of(mb.sweep_metrics(anchor=-1, raw=0, outcomes=np.linspace(-1.0, 1.0, n)))
+
+    live = az.MCTSBatch(Game, n, 1.25, max_simulations=8, seeds=seeds)
+    for cps in ((8,), (1, 2, 4, 8), (8,)):
+        got = run(live, cps)
+        assert got == run(az.MCTSBatch(Game, n, 1.25, max_simulations=8, seeds=seeds), cps), f"checkpoints {cps}"
