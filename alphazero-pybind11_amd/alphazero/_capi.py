@@ -177,6 +177,8 @@ SYMBOLS = {
     "azmi_debug_pipe_log_dupes": (C.c_int, [_VP, _VP]),
     "azmi_debug_pipe_net_bench": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _VP]),
     "azmi_debug_group_select": (C.c_int, [C.c_int, C.c_uint32] + [_VP] * 12),
+    "azmi_debug_group_expand": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32] + [_VP] * 7),
+    "azmi_debug_shard_index": (C.c_int, [C.c_int, C.c_uint32, _VP, C.c_uint32, _VP]),
     "azmi_debug_cache_find_group": (C.c_int, [_VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP, _VP]),
     "azmi_debug_cache_insert_locked": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _PP(C.c_uint32)]),
     "azmi_comm_available": (C.c_int, []),

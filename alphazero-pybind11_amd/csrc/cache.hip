@@ -34,7 +34,7 @@ __global__ void k_cache_insert_many(CacheView c, const uint64_t* hashes, const f
   ShardCtx ctx(c, sh);
   for (uint32_t i = 0; i < n; ++i) {
     const uint64_t h = hashes[i];
-    if (h % c.shards != sh) continue;
+    if (shard_of(c, h) != sh) continue;
     const int slot = ctx.insert(h);
     if (slot < 0) continue;
     float* dp = c.policy + (static_cast<size_t>(sh) * c.cap + slot) * c.np;
@@ -93,6 +93,12 @@ __global__ __launch_bounds__(256) void k_debug_insert_locked(CacheView c, uint32
     const bool ok = wave_shard_insert_locked<false>(c, locks, keys[i], p, v, lane);
     if (!ok && lane == 0) atomicAdd(failed, 1u);
   }
+}
+
+// shard_of as the device compiles it, one hash per thread
+__global__ void k_debug_shard_index(uint32_t shards, uint64_t mul, const uint64_t* hashes, uint32_t n, uint32_t* out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = shard_of(hashes[i], shards, mul);
 }
 
 // the finds of one call: host arrays in, host arrays out.  group_lanes = 0: the generic tables, one lane per query
@@ -221,6 +227,31 @@ int azmi_debug_cache_insert_locked(azmi_cache* c, const uint64_t* hashes, const 
   if (e == hipSuccess) e = hipMemcpy(failed_out, dl + c->c.shards, 4, hipMemcpyDeviceToHost);
   (void)hipFree(dh); (void)hipFree(dp); (void)hipFree(dv); (void)hipFree(dl);
   return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "azmi_debug_cache_insert_locked: %s", hipGetErrorString(e));
+}
+
+int azmi_debug_shard_index(int device, uint32_t shards, const uint64_t* hashes, uint32_t n, uint32_t* out) {
+  if (shards == 0u) return cfail(AZMI_ERR_INVALID, "azmi_debug_shard_index: shards must be at least 1");
+  if (n && (!hashes || !out)) return cfail(AZMI_ERR_INVALID, "azmi_debug_shard_index: null argument");
+  if (n == 0) return AZMI_OK;
+  const uint64_t mul = shard_multiplier(shards);
+  if (device < 0) {      // the host's compilation of shard_of: what cache_alloc's callers and the insert logs' readers would run
+    for (uint32_t i = 0; i < n; ++i) out[i] = shard_of(hashes[i], shards, mul);
+    return AZMI_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return cfail(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  if (hipSetDevice(device) != hipSuccess) return cfail(AZMI_ERR_NO_DEVICE, "hipSetDevice failed");
+  uint64_t* dh = nullptr; uint32_t* dout = nullptr;
+  hipError_t e = hipMalloc(&dh, n * 8ULL);
+  if (e == hipSuccess) e = hipMalloc(&dout, n * 4ULL);
+  if (e == hipSuccess) e = hipMemcpy(dh, hashes, n * 8ULL, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    k_debug_shard_index<<<(n + 255u) / 256u, 256>>>(shards, mul, dh, n, dout);
+    e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dout, n * 4ULL, hipMemcpyDeviceToHost);
+  (void)hipFree(dh); (void)hipFree(dout);
+  return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "azmi_debug_shard_index: %s", hipGetErrorString(e));
 }
 
 int azmi_cache_stats(azmi_cache* c, uint64_t out[6]) {

@@ -20,6 +20,7 @@ inline hipError_t cache_alloc(CacheView& c, std::vector<void*>& allocs, uint32_t
   c = CacheView{};
   c.shards = shards; c.cap = max_size / shards; c.ghost_cap = ghost_size / shards;
   c.np = np; c.nv = nv;
+  c.shard_mul = shard_multiplier(shards);
   c.tcap = pow2_at_least(2 * c.cap + 2);
   c.gcap = pow2_at_least(2 * c.ghost_cap + 2);
   auto get = [&](void** p, size_t bytes) {

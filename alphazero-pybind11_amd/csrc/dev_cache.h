@@ -3,7 +3,7 @@
 //
 // position key -> (pi[num_policy], v[num_value]); per shard a Small and a Main FIFO ring of slot
 // indices, a Ghost ring of evicted keys, a 2-bit frequency per slot (s3fifo_cache.h:41-59, 82-150).
-// shard = key % shards, exactly as the reference.  absl's flat_hash_{map,set} become two
+// shard = key % shards, exactly as the reference (shard_of below: the same value without the division).  absl's flat_hash_{map,set} become two
 // open-addressing tables per shard (linear probing, backward-shift deletion, key 0 = empty).
 // Key 0 therefore cannot be stored as itself: cache_key() maps hash 0 onto 0x9E3779B97F4A7C15, while the shard is still taken
 // from the hash (0 % shards).  Hash 0 and hash 0x9E3779B97F4A7C15 share ONE entry when they fall into the same shard (always with
@@ -30,6 +30,7 @@ struct CacheView {
   uint32_t shards, cap, ghost_cap;  // per-shard capacities (max_size / shards, ghost_size / shards)
   uint32_t tcap, gcap;              // table sizes (powers of two), per shard
   uint32_t np, nv;                  // num_policy, num_value
+  uint64_t shard_mul;               // shard_multiplier(shards): shard_of's multiplier, filled where the view is made (cache_alloc)
   uint64_t* hashes;                 // [shards][cap]
   uint32_t* freq;                   // [shards][cap]
   float* policy;                    // [shards][cap][np]
@@ -43,6 +44,24 @@ struct CacheView {
   uint64_t* gset_key;               // [shards][gcap]
   unsigned long long* stats;        // [shards][4]: hits misses evictions reinserts
 };
+
+// ---- shard = hash % shards without a division --------------------------------------------------------------------------
+// A 64-bit `%` by a run-time value is a software routine of a couple of hundred dependent instructions on this target, and the
+// probe's key loads cannot be addressed before it is done.  With M = floor((2^64 - 1) / d) = (2^64 - e) / d, 1 <= e <= d:
+// h * M / 2^64 = h / d - h * e / (d * 2^64), and the subtrahend lies in [0, 1) for every h < 2^64; so q = mulhi(h, M) is
+// floor(h / d) or one less, r = h - q * d lies in [0, 2 d), and one conditional subtraction gives exactly h % d - for every d
+// from 1 to 2^32 - 1, a power of two or not.  Host and device run the same function (tests/test_shard_index.py).
+__host__ __device__ inline uint64_t shard_multiplier(uint32_t shards) { return shards ? ~0ull / shards : 0ull; }
+__host__ __device__ __forceinline__ uint32_t shard_of(uint64_t hash, uint32_t shards, uint64_t mul) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint64_t q = __umul64hi(hash, mul);
+#else
+  const uint64_t q = static_cast<uint64_t>((static_cast<unsigned __int128>(hash) * mul) >> 64);
+#endif
+  const uint64_t r = hash - q * shards;
+  return static_cast<uint32_t>(r >= shards ? r - shards : r);
+}
+__host__ __device__ __forceinline__ uint32_t shard_of(const CacheView& c, uint64_t hash) { return shard_of(hash, c.shards, c.shard_mul); }
 
 enum { kSHead = 0, kSSize, kMHead, kMSize, kNextFree, kGHead, kGCount, kSize };
 
@@ -95,7 +114,7 @@ __device__ inline bool table_erase(uint64_t* keys, uint32_t* vals, uint32_t n, u
 // ---- S3FIFOCache::find, s3fifo_cache.h:41-59 — returns the slot index (shard-relative) or -1 ----------
 __device__ inline int cache_find(const CacheView& c, uint64_t hash, uint32_t* shard_out) {
   const uint64_t k = cache_key(hash);
-  const uint32_t sh = static_cast<uint32_t>(hash % c.shards);
+  const uint32_t sh = shard_of(c, hash);
   *shard_out = sh;
   const int at = table_find(c.map_key + static_cast<size_t>(sh) * c.tcap, c.tcap, k);
   return at < 0 ? -1 : static_cast<int>(c.map_val[static_cast<size_t>(sh) * c.tcap + at]);
@@ -350,7 +369,7 @@ using WaveShard = WaveShardT<false>;
 template <bool PROBE_SAFE = true>
 __device__ inline bool wave_shard_insert_locked(const CacheView& c, uint32_t* locks, uint64_t hash, float p_lane, float v_lane,
                                                 uint32_t lane, uint32_t spin_cap = 1u << 20) {
-  const uint32_t sh = static_cast<uint32_t>(hash % c.shards);
+  const uint32_t sh = shard_of(c, hash);
   // the key check and the first try at the lock travel together (one round trip): an entry that is already there gives the lock
   // straight back; a wavefront that waits for the lock keeps looking at the keys, so a batch of identical positions - every
   // slot's opening move - is done with the shard as soon as the first of them is in
@@ -398,7 +417,7 @@ struct NoPreload { __device__ __forceinline__ void operator()() const {} };
 template <int G, class F = NoPreload>
 __device__ __forceinline__ int wave_shard_find(const CacheView& c, uint64_t hash, uint32_t glane, uint32_t* shard_out, F&& before_loads = F()) {
   const uint64_t k = cache_key(hash);
-  const uint32_t sh = static_cast<uint32_t>(hash % c.shards);
+  const uint32_t sh = shard_of(c, hash);
   *shard_out = sh;
   const uint64_t* hs = c.hashes + static_cast<size_t>(sh) * kWaveCap;
   // all of the lane's key loads are issued, then the caller's preloads (they return behind the keys: one round trip for both), then
@@ -477,7 +496,7 @@ __device__ __forceinline__ void cache_apply_batch(const CacheView& c, const uint
   for (uint32_t j = tid; j < n; j += blockDim.x) {
     const bool ours = !(groups && groups[j] != group);                 // elements of another model group are not ours
     const uint64_t k = keys[j];
-    s_sid[j] = (ours && (ZERO_IS_KEY || k)) ? static_cast<uint32_t>(k % c.shards) : 0xFFFFFFFFu;
+    s_sid[j] = (ours && (ZERO_IS_KEY || k)) ? shard_of(c, k) : 0xFFFFFFFFu;
   }
   __syncthreads();
   if (i >= n) return;

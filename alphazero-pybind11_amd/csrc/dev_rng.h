@@ -67,6 +67,19 @@ __device__ __forceinline__ uint32_t lemire_below(Pcg32& g, uint32_t range) {
   return static_cast<uint32_t>(product >> 32);
 }
 
+// 2^32 mod range: the rejection threshold of Lemire's method (a compile-time constant wherever the range is one)
+__host__ __device__ constexpr uint32_t lemire_threshold(uint32_t range) { return (0u - range) % range; }
+// lemire_below with the threshold handed in (a constant, or a select between constants).  threshold < range, so
+// `low < threshold` alone decides what `low < range` guards in lemire_below: the same draws are rejected, the same number of
+// next() calls is made, and no `%` is left at the call site.
+__device__ __forceinline__ uint32_t lemire_below_thr(Pcg32& g, uint32_t range, uint32_t threshold) {
+  uint64_t product = static_cast<uint64_t>(g.next()) * static_cast<uint64_t>(range);
+  while (static_cast<uint32_t>(product) < threshold) product = static_cast<uint64_t>(g.next()) * static_cast<uint64_t>(range);
+  return static_cast<uint32_t>(product >> 32);
+}
+template <uint32_t RANGE>
+__device__ __forceinline__ uint32_t lemire_below_c(Pcg32& g) { return lemire_below_thr(g, RANGE, lemire_threshold(RANGE)); }
+
 __device__ __forceinline__ float canonical01(Pcg32& g) {
   const float ret = static_cast<float>(g.next()) / 4294967296.0f;
   return ret >= 1.0f ? 0.99999994f /* nextafter(1,0) */ : ret;

@@ -74,6 +74,17 @@ __device__ __forceinline__ uint32_t gum_plan(uint32_t m, uint32_t n, uint32_t wa
   return count;
 }
 
+// x / b == (x * shuffle_recip16(b)) >> 16 for every x below (b - 1) * b, b = 3 .. 9: the divisions of std::shuffle's pair
+// draws for up to eight children (expand_node), checked here for every such x
+__host__ __device__ constexpr uint32_t shuffle_recip16(uint32_t b) { return (65536u + b - 1u) / b; }
+constexpr bool shuffle_recip16_exact() {
+  for (uint32_t b = 3; b <= 9; ++b)
+    for (uint32_t x = 0; x < (b - 1u) * b; ++x)
+      if (((x * shuffle_recip16(b)) >> 16) != x / b) return false;
+  return true;
+}
+static_assert(shuffle_recip16_exact(), "the reciprocal multiply must be the division");
+
 // lane image of a simulation's path (see PendRec, engine_types.h): level i in lane i, paths of <= 8 levels
 struct PathRegs {
   uint32_t node = 0, n = 0, pp = 0, mv = 0;
@@ -426,6 +437,10 @@ struct SlotCtx {
 
   // ---- Node::add_children: legal moves ascending, std::shuffle, append to the arena ----
   // Returns false when the arena is full.  `meta_keep` supplies move/player/term of `node`.
+  // LANE_PACK: the packed move word is built by the group's lanes (one move each, three DPP moves) instead of a loop over
+  // the legal moves.  The pipeline's tree kernel asks for it; k_sim and k_round keep the loop, where the lane form costs
+  // spilled registers (k_sim: 14 -> 18 VGPRs, scratch 60 -> 76 B) - profiles/tree_iteration_chain_resources.txt.
+  template <bool LANE_PACK = false>
   __device__ __forceinline__ bool expand_node(uint32_t seat, uint32_t node, const typename GM::State& st, uint64_t meta_keep,
                               uint32_t& c0_out, uint32_t& k_out, uint32_t* mv_out = nullptr) {
     const size_t tb = tree_base(seat);
@@ -434,30 +449,45 @@ struct SlotCtx {
     // (stl_algo.h:3729-3792) then swaps fields of that word — the draws are group-uniform anyway — instead of moving
     // values between lanes (a dependent ds_bpermute chain per swap); each lane finally picks field `lane`.
     static_assert(GM::MAXK <= 8, "eight 4-bit move fields");
-    uint32_t packed = 0;
+    uint32_t packed;
     {
-      uint32_t vm = GM::valid_mask(st), pos = 0;
-      while (vm) { const uint32_t m = __builtin_ctz(vm); vm &= vm - 1; packed |= m << (4 * pos); ++pos; }
+      const uint32_t vm = GM::valid_mask(st);
+      if constexpr (LANE_PACK && G == 8) {
+        // no loop over the set bits: lane m asks whether move m is legal, its field is the number of legal moves below it, and
+        // the eight one-field words are ORed over the group by three DPP moves (xor 1, xor 2, the half-row mirror)
+        static_assert(GM::M <= 8, "one lane per move");
+        uint32_t w = ((vm >> lane) & 1u) ? lane << (4u * static_cast<uint32_t>(__builtin_popcount(vm & ((1u << lane) - 1u)))) : 0u;
+        w |= dpp_u<0xB1>(w); w |= dpp_u<0x4E>(w); w |= dpp_u<0x141>(w);
+        packed = w;
+      } else {
+        uint32_t rest = vm, pos = 0;
+        packed = 0;
+        while (rest) { const uint32_t m = __builtin_ctz(rest); rest &= rest - 1; packed |= m << (4 * pos); ++pos; }
+      }
     }
-    auto swap_fields = [&](uint32_t a, uint32_t b) {
-      const uint32_t fa = (packed >> (4 * a)) & 0xFu, fb = (packed >> (4 * b)) & 0xFu;
-      packed = (packed & ~((0xFu << (4 * a)) | (0xFu << (4 * b)))) | (fb << (4 * a)) | (fa << (4 * b));
+    auto swap_fields = [&](uint32_t a, uint32_t b) {      // (a == b: d = 0, nothing moves)
+      const uint32_t d = ((packed >> (4 * a)) ^ (packed >> (4 * b))) & 0xFu;
+      packed ^= (d << (4 * a)) | (d << (4 * b));
     };
     if (k > 1) {
-      uint32_t i = 1;
-      if ((k & 1u) == 0) {
-        const uint32_t j = lemire_below(rng, 2);
-        swap_fields(i, j);
-        ++i;
-      }
-      while (i != k) {
-        const uint32_t swap_range = i + 1, b1 = swap_range + 1;
-        const uint32_t x = lemire_below(rng, swap_range * b1);
-        const uint32_t p0 = x / b1, p1 = x % b1;
-        swap_fields(i, p0);
-        ++i;
-        swap_fields(i, p1);
-        ++i;
+      // std::shuffle's pair-swap form draws (x / b1, x % b1) with x below swap_range * b1 and b1 = swap_range + 1.  The first
+      // pair starts at field 1 (k odd) or, behind one draw below 2, at field 2 (k even), so pair s has b1 = 3 + 2 s or 4 + 2 s:
+      // the parity of k chooses between two compile-time constants for the range, the rejection threshold and the reciprocal
+      // of b1, with a select each.  No division is left, and the groups of a wavefront whose k differ in parity walk the
+      // same three steps together instead of one specialised chain after the other.
+      const bool even = (k & 1u) == 0u;
+      if (even) swap_fields(1u, lemire_below_c<2>(rng));
+#pragma unroll
+      for (uint32_t s = 0; s < static_cast<uint32_t>(GM::MAXK - 1) / 2u; ++s) {
+        const uint32_t b_odd = 3u + 2u * s, r_odd = (b_odd - 1u) * b_odd, b_even = b_odd + 1u, r_even = (b_even - 1u) * b_even;
+        const uint32_t i = 1u + 2u * s + (even ? 1u : 0u);
+        if (i < k) {           // (`i != k` in the library: i has k's parity and steps by two)
+          const uint32_t x = lemire_below_thr(rng, even ? r_even : r_odd, even ? lemire_threshold(r_even) : lemire_threshold(r_odd));
+          const uint32_t p0 = (x * (even ? shuffle_recip16(b_even) : shuffle_recip16(b_odd))) >> 16;      // x / b1
+          const uint32_t p1 = x - p0 * (even ? b_even : b_odd);                                           // x % b1
+          swap_fields(i, p0);
+          swap_fields(i + 1u, p1);
+        }
       }
     }
     const uint32_t mv = lane < k ? (packed >> (4 * lane)) & 0xFu : 0u;

@@ -607,7 +607,7 @@ __global__ __launch_bounds__(NT, AZMI_TREE_MINB) void k_pipe_tree(PipeKernArgs k
         if (n == 0) {
           term = GM::terminal(leaf);
           const uint64_t keep = meta_pack(0, 0, meta_mv(meta), leaf.player, term);
-          if (!c.expand_node(cp, cur, leaf, keep, lf_c0, lf_k, &lf_mv)) { final_state = kSlotDone; st = kGrpIdle; break; }
+          if (!c.template expand_node<true>(cp, cur, leaf, keep, lf_c0, lf_k, &lf_mv)) { final_state = kSlotDone; st = kGrpIdle; break; }
           lf_meta = meta_pack(lf_c0, lf_k, meta_mv(meta), leaf.player, term);
         }
         lf_term = term; lf_player = leaf.player;
@@ -2103,6 +2103,72 @@ extern "C" int azmi_debug_group_select(int device, uint32_t rows, const uint32_t
   if (e == hipSuccess) e = hipMemcpy(all64, d_all, n64w * 4u, hipMemcpyDeviceToHost);
   (void)hipFree(d);
   if (e != hipSuccess) return azmi_host_fail(AZMI_ERR_NO_DEVICE, "azmi_debug_group_select: %s", hipGetErrorString(e));
+  return AZMI_OK;
+}
+
+// ---- diagnostics: expand_node on its own, one wavefront (eight groups) per row, `reps` positions per group one after the other ------
+namespace azmi {
+template <bool LANE_PACK>
+__global__ __launch_bounds__(64) void k_debug_group_expand(uint32_t reps, uint32_t cap, NodeRec* nodes, Control* ctl, const uint64_t* bb0, const uint64_t* bb1,
+                                                           const uint32_t* player, const uint64_t* rng_in, uint32_t* words, uint64_t* rng_out) {
+  const uint32_t wlane = threadIdx.x & 63u, grp = wlane >> 3, lane = wlane & 7u;
+  const uint32_t slot = blockIdx.x * 8u + grp;
+  EngineParams ep{};
+  EngineArrays ar{};
+  ep.S = gridDim.x * 8u; ep.cap = cap;
+  ar.nodes = nodes; ar.ctl = ctl;
+  SlotCtx<Connect4> c(ep, ar, slot, lane);
+  c.t_bump[0] = reps; c.t_bump[1] = 0u;       // (tree 0 of the slot: nodes 0 .. reps-1 are the parents, the children follow)
+  for (uint32_t r = 0; r < reps; ++r) {
+    const size_t pi = static_cast<size_t>(slot) * reps + r;
+    Connect4::State st{{bb0[pi], bb1[pi]}, 0u, player[pi]};
+    c.rng.state = rng_in[pi];
+    uint32_t c0 = 0xFFFFFFFFu, k = 0xFFFFFFFFu, mv = 0xFFFFFFFFu;
+    const bool ok = c.template expand_node<LANE_PACK>(0u, r, st, meta_pack(0, 0, r & 7u, st.player, 0), c0, k, &mv);
+    const size_t o = pi * 8u + lane;
+    words[o * 4u + 0u] = mv; words[o * 4u + 1u] = c0; words[o * 4u + 2u] = k; words[o * 4u + 3u] = ok ? 1u : 0u;
+    rng_out[o] = c.rng.state;
+    if (!ok) break;
+  }
+}
+}  // namespace azmi
+
+extern "C" int azmi_debug_group_expand(int device, uint32_t lane_pack, uint32_t rows, uint32_t reps, uint32_t cap, const uint64_t* bb0, const uint64_t* bb1,
+                                       const uint32_t* player, const uint64_t* rng_in, uint32_t* words, uint64_t* rng_out, void* nodes_out) {
+  using namespace azmi;
+  if (!bb0 || !bb1 || !player || !rng_in || !words || !rng_out || !nodes_out) return azmi_host_fail(AZMI_ERR_INVALID, "azmi_debug_group_expand: null buffer");
+  if (rows == 0u || rows > 4096u || reps == 0u || reps > 64u) return azmi_host_fail(AZMI_ERR_INVALID, "azmi_debug_group_expand: rows must be 1 .. 4096, reps 1 .. 64");
+  if (cap < reps + reps * 8u || cap > 65536u) return azmi_host_fail(AZMI_ERR_INVALID, "azmi_debug_group_expand: cap must hold the parents and eight children each (%u .. 65536)", reps + reps * 8u);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return azmi_host_fail(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  AZMI_HIP_TRY(hipSetDevice(device));
+  const size_t slots = static_cast<size_t>(rows) * 8u, calls = slots * reps, lanes = calls * 8u;
+  const size_t node_bytes = slots * Connect4::P * cap * sizeof(NodeRec);
+  NodeRec* d_nodes = nullptr; Control* d_ctl = nullptr; uint64_t* d_in = nullptr; uint32_t* d_player = nullptr; uint64_t* d_rng_out = nullptr; uint32_t* d_words = nullptr;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_nodes), node_bytes);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_ctl), sizeof(Control));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_in), calls * 8u * 3u);          // bb0, bb1, rng_in
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_player), calls * 4u);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rng_out), lanes * 8u);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_words), lanes * 16u);
+  if (e == hipSuccess) e = hipMemset(d_nodes, 0xAB, node_bytes);        // (what expand_node does not write stays recognisable)
+  if (e == hipSuccess) e = hipMemset(d_ctl, 0, sizeof(Control));
+  if (e == hipSuccess) e = hipMemset(d_words, 0xFF, lanes * 16u);
+  if (e == hipSuccess) e = hipMemset(d_rng_out, 0xFF, lanes * 8u);
+  if (e == hipSuccess) e = hipMemcpy(d_in, bb0, calls * 8u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_in + calls, bb1, calls * 8u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_in + 2u * calls, rng_in, calls * 8u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_player, player, calls * 4u, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    if (lane_pack) k_debug_group_expand<true><<<rows, 64>>>(reps, cap, d_nodes, d_ctl, d_in, d_in + calls, d_player, d_in + 2u * calls, d_words, d_rng_out);
+    else k_debug_group_expand<false><<<rows, 64>>>(reps, cap, d_nodes, d_ctl, d_in, d_in + calls, d_player, d_in + 2u * calls, d_words, d_rng_out);
+    e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(words, d_words, lanes * 16u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(rng_out, d_rng_out, lanes * 8u, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(nodes_out, d_nodes, node_bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(d_nodes); (void)hipFree(d_ctl); (void)hipFree(d_in); (void)hipFree(d_player); (void)hipFree(d_rng_out); (void)hipFree(d_words);
+  if (e != hipSuccess) return azmi_host_fail(AZMI_ERR_NO_DEVICE, "azmi_debug_group_expand: %s", hipGetErrorString(e));
   return AZMI_OK;
 }
 

@@ -850,6 +850,20 @@ int azmi_debug_pipe_log_dupes(azmi_pm* pm, uint64_t* out);
 int azmi_debug_group_select(int device, uint32_t rows, const uint32_t* k8, const uint32_t* n64, const float* q64, const float* p64,
                             const float* v_parent8, const uint32_t* n_parent8, const float* fpu8, const float* cpuct8, const uint64_t* pred,
                             float* sum64, uint32_t* best64, uint32_t* all64);
+/* diagnostics: expand_node (Node::add_children, mcts.cc:93-101) on its own, in the form of the lock-step kernels (lane_pack = 0) or of
+ * the pipeline's tree kernel (lane_pack = 1: the move word is packed by the group's lanes).  One wavefront per row; each of its eight 8-lane groups
+ * expands `reps` Connect4 positions one after the other into tree 0 of its own slot (slot = 8 row + group; `cap` nodes per tree, nodes
+ * 0 .. reps-1 are the parents, children are appended behind them).  Inputs per call (rows x 8 x reps, call r of slot s at s reps + r):
+ * the two bitboards, the player to move, the RNG state the call starts from.  Outputs per lane of a call ((s reps + r) 8 + lane):
+ * words[4] = the lane's child move, c0, k, 1 when the arena had room; rng_out = the RNG state afterwards; nodes_out = the arena
+ * (rows x 8 slots x 2 trees x cap records of 32 bytes: u32 n, f32 q, pr, d, v, u32 unused, u64 meta), prefilled with 0xAB bytes.
+ * tests/test_gpu_group_expand.py */
+int azmi_debug_group_expand(int device, uint32_t lane_pack, uint32_t rows, uint32_t reps, uint32_t cap, const uint64_t* bb0, const uint64_t* bb1,
+                            const uint32_t* player, const uint64_t* rng_in, uint32_t* words, uint64_t* rng_out, void* nodes_out);
+/* diagnostics: out[i] = the cache shard of hashes[i] among `shards` (hash % shards, computed the way the kernels compute it: a
+ * multiply by a constant of the cache and one correction).  device < 0: the host's compilation, no GPU needed; otherwise one
+ * thread per hash on that device.  tests/test_shard_index.py */
+int azmi_debug_shard_index(int device, uint32_t shards, const uint64_t* hashes, uint32_t n, uint32_t* out);
 /* diagnostics: azmi_cache_find_many on a cache of 64-entry wave shards, probing with wave_shard_find<group_lanes> - the lane groups the
  * engines probe with (GM::GROUP: 8 and 64); the stand-alone call always uses 8.  Same accounting, same outputs.  Other values of
  * group_lanes and caches in another layout are errors (azmi_cache_last_error).  tests/test_gpu_cache_edges.py */
