@@ -324,6 +324,18 @@ __device__ __forceinline__ bool mcts_big_replay(BigSlot<GM>& c, const uint8_t* i
   }
 }
 
+// entry of the evaluator's row that the reference leaves in entry i of its by-reference `value` after process_result: a game
+// with relative values rotates the row to absolute seats in place (relative_to_absolute(value, current_->player),
+// mcts.cc:522-524, game_state.h:36-46: out[(player + j) % P] = value[j], the draw entry stays)
+template <class GM>
+__device__ __forceinline__ int mcts_big_value_src(uint64_t leaf_meta, int i) {
+  constexpr int P = GM::P;
+  if constexpr (GM::kRelative) {
+    if (i < P) return (i + P - static_cast<int>(meta_player(leaf_meta)) % P) % P;
+  }
+  return i;
+}
+
 template <class GM>
 __global__ __launch_bounds__(64) void k_mcts_big_find_leaf(EngineParams ep, EngineArrays ar, uint32_t* nif, const uint8_t* init, uint32_t init_stride,
                                                            const int32_t* moves, uint32_t len, int32_t* out_moves, uint32_t* out_len, int32_t* status) {
@@ -357,10 +369,11 @@ __global__ __launch_bounds__(64) void k_mcts_big_process_result(EngineParams ep,
   const uint32_t lane = threadIdx.x;
   BigSlot<GM> c(ep, ar, sm, 0, lane);
   c.load();
-  const uint32_t term = meta_term(ar.META[c.tree_base(0) + c.cur]);
+  const uint64_t leaf_meta = ar.META[c.tree_base(0) + c.cur];
+  const uint32_t term = meta_term(leaf_meta);
   c.process_result(0, true, root_noise != 0);
   if (lane == 0)
-    for (int i = 0; i <= P; ++i) value_out[i] = term ? ((static_cast<int>(term) - 1 == i) ? 1.0f : 0.0f) : ar.v[i];
+    for (int i = 0; i <= P; ++i) value_out[i] = term ? ((static_cast<int>(term) - 1 == i) ? 1.0f : 0.0f) : ar.v[mcts_big_value_src<GM>(leaf_meta, i)];
   c.store(kSlotWaitEval);
 }
 
@@ -408,10 +421,11 @@ __global__ __launch_bounds__(64) void k_mcts_big_process_result_batched(EnginePa
     for (uint32_t i = 0; i < c.plen; ++i) { ar.path[i] = rec[i]; --nif[rec[i]]; }
   }
   c.sync();
-  const uint32_t term = meta_term(ar.META[c.tree_base(0) + c.cur]);
+  const uint64_t leaf_meta = ar.META[c.tree_base(0) + c.cur];
+  const uint32_t term = meta_term(leaf_meta);
   c.process_result(0, true, root_noise != 0);
   if (lane == 0)
-    for (int i = 0; i <= P; ++i) value_out[i] = term ? ((static_cast<int>(term) - 1 == i) ? 1.0f : 0.0f) : ar.v[i];
+    for (int i = 0; i <= P; ++i) value_out[i] = term ? ((static_cast<int>(term) - 1 == i) ? 1.0f : 0.0f) : ar.v[mcts_big_value_src<GM>(leaf_meta, i)];
   c.store(kSlotWaitEval);
 }
 

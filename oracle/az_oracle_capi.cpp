@@ -32,6 +32,7 @@ struct MctsBox {
   Pcg32 rng;
   std::unique_ptr<Mcts> m;
   std::unique_ptr<Game> leaf;
+  float last_uniform = 0.0f;   // the uniform the last orc_mcts_pick_move drew
 };
 struct PmBox {
   std::unique_ptr<PlayManager> pm;
@@ -274,8 +275,12 @@ void orc_mcts_probs(void* h, float temp, int pruned, float* out) {
 }
 uint32_t orc_mcts_pick_move(void* h, const float* p, uint32_t n) {
   auto* b = static_cast<MctsBox*>(h);
+  Pcg32 peek = b->rng;               // pick_move draws exactly one uniform01 first (mcts.cc:718)
+  b->last_uniform = uniform01(peek);
   return Mcts::pick_move(std::vector<float>(p, p + n), b->rng);
 }
+float orc_mcts_last_uniform(void* h) { return static_cast<MctsBox*>(h)->last_uniform; }
+uint64_t orc_mcts_rng_state(void* h) { return static_cast<MctsBox*>(h)->rng.state; }
 uint32_t orc_mcts_depth(void* h) { return static_cast<MctsBox*>(h)->m->depth(); }
 uint32_t orc_mcts_root_n(void* h) { return static_cast<MctsBox*>(h)->m->root_n(); }
 float orc_mcts_avg_leaf_depth(void* h) { return static_cast<MctsBox*>(h)->m->avg_leaf_depth(); }
@@ -297,6 +302,22 @@ uint32_t orc_mcts_root_children(void* h, uint32_t* moves, float* policy, uint32_
     moves[i] = c.move; policy[i] = c.policy; n[i] = c.n; q[i] = c.q;
   }
   return r.nchild;
+}
+// root children in stored order with every field the read-outs use: moves[k], n[k], q[k], policy[k], d[k]; returns k
+uint32_t orc_mcts_root_children_full(void* h, uint32_t* moves, uint32_t* n, float* q, float* policy, float* d) {
+  auto* m = static_cast<MctsBox*>(h)->m.get();
+  const Node& r = m->root();
+  for (uint32_t i = 0; i < r.nchild; ++i) {
+    const Node& c = m->node(r.child0 + i);
+    moves[i] = c.move; n[i] = c.n; q[i] = c.q; policy[i] = c.policy; d[i] = c.d;
+  }
+  return r.nchild;
+}
+// the root's own v, d and n: vd[0] = v, vd[1] = d; returns n
+uint32_t orc_mcts_root_node(void* h, float* vd) {
+  const Node& r = static_cast<MctsBox*>(h)->m->root();
+  vd[0] = r.v; vd[1] = r.d;
+  return r.n;
 }
 // Node::uct on explicit numbers (mcts_test.cc:14-38 known answers)
 float orc_node_uct(float q, float policy, uint32_t n, float sqrt_parent_n, float cpuct, float fpu) {

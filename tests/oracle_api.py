@@ -33,6 +33,8 @@ lib.orc_pm_hist_count.restype = C.c_uint64
 lib.orc_pm_move_count.restype = C.c_uint64
 lib.orc_mcts_avg_leaf_depth.restype = C.c_float
 lib.orc_mcts_entropy.restype = C.c_float
+lib.orc_mcts_last_uniform.restype = C.c_float
+lib.orc_mcts_rng_state.restype = C.c_uint64
 lib.orc_node_uct.restype = C.c_float
 lib.orc_node_uct.argtypes = [C.c_float, C.c_float, C.c_uint32, C.c_float, C.c_float, C.c_float]
 
@@ -279,6 +281,27 @@ class Mcts:
         mv = np.zeros(4096, np.uint32); pol = np.zeros(4096, np.float32); n = np.zeros(4096, np.uint32); q = np.zeros(4096, np.float32)
         k = lib.orc_mcts_root_children(self.h, _p(mv), _p(pol), _p(n), _p(q))
         return mv[:k], pol[:k], n[:k], q[:k]
+
+    def root_children_full(self):
+        """root children in stored order -> (move, n, q, policy, d), every field the read-outs use"""
+        mv = np.zeros(4096, np.uint32); n = np.zeros(4096, np.uint32)
+        q = np.zeros(4096, np.float32); pol = np.zeros(4096, np.float32); d = np.zeros(4096, np.float32)
+        k = lib.orc_mcts_root_children_full(self.h, _p(mv), _p(n), _p(q), _p(pol), _p(d))
+        return mv[:k].copy(), n[:k].copy(), q[:k].copy(), pol[:k].copy(), d[:k].copy()
+
+    def root_node(self):
+        """the root's own (v, d, n)"""
+        vd = np.zeros(2, np.float32)
+        n = lib.orc_mcts_root_node(self.h, _p(vd))
+        return vd[0], vd[1], int(n)
+
+    def last_uniform(self):
+        """the uniform the last pick_move drew"""
+        return np.float32(lib.orc_mcts_last_uniform(self.h))
+
+    def rng_state(self):
+        """position of the object's pcg32 stream"""
+        return int(lib.orc_mcts_rng_state(self.h))
 
 
 def dumb_eval(game):

@@ -130,6 +130,49 @@ def test_playmanager_parity(az, oracle, name, cfg):
     assert sorted((a.tobytes(), b.tobytes(), d.tobytes()) for a, b, d in zip(hc, hv, hp)) == sorted(rows_orc)
 
 
+def test_brandubh_sharp_evaluator_with_decaying_temperature_and_pruned_targets(az, oracle):
+    """4 concurrent games, 16 visits, the temperature decaying from 1.0 to 0.2, target pruning on, the scripted sharp evaluator
+    of tests/mcts_readout_ref.py through build_batch / update_inferences: moves, visit counts, history rows (pi targets
+    included) and scores equal the oracle PlayManager driven by the same function."""
+    import mcts_readout_ref as ref
+    evaluator = ref.sharp_evaluator("brandubh", oracle)
+    pp = az.PlayParams()
+    pp.games_to_play, pp.concurrent_games, pp.max_batch_size = 4, 4, 4
+    pp.model_groups = [0, 0]
+    pp.mcts_visits = [16, 16]
+    pp.cpuct, pp.fpu_reduction = 1.25, 0.25
+    pp.start_temp, pp.final_temp, pp.temp_decay_half_life = 1.0, 0.2, 3.0
+    pp.epsilon, pp.policy_target_pruning = 0.25, True
+    pp.history_enabled = True
+    seed = 405
+    pm = az.PlayManager(az.BrandubhGS(), pp, seed=seed, log_moves=True)
+    batch = np.zeros((4, 7, 7, 7), np.float32)
+    while pm.remaining_games() > 0:
+        idx = pm.build_batch(0, batch)
+        if not idx:
+            continue
+        v, pi = evaluator(batch[: len(idx)])
+        pm.update_inferences(0, idx, v, pi)
+    rows, counts = pm.move_log()
+    hc, hv, hp = pm.history()
+    tot = np.zeros(3, np.float32)
+    rows_orc = []
+    for s in range(4):
+        one = az.PlayParams(); one.__dict__.update(pp.__dict__)
+        one.games_to_play, one.concurrent_games = 1, 1
+        o = oracle.PlayManager(oracle.GAME_BRANDUBH, one, oracle.slot_seed(seed, s), per_slot_rng=False)
+        o.run(evaluator)
+        orows, ocounts = o.moves()
+        sel = rows[:, 0] == s
+        assert np.array_equal(rows[sel][:, 2:], orows[:, 2:]), s
+        assert np.array_equal(counts[sel], ocounts), s
+        tot += o.scores()
+        c, v, p = o.history()
+        rows_orc += [(a.tobytes(), b.tobytes(), d.tobytes()) for a, b, d in zip(c, v, p)]
+    assert np.array_equal(pm.scores(), tot)
+    assert sorted((a.tobytes(), b.tobytes(), d.tobytes()) for a, b, d in zip(hc, hv, hp)) == sorted(rows_orc)
+
+
 def test_symmetries_match_oracle(az, oracle):
     rng = np.random.default_rng(2)
     for Game, n, C in ((az.BrandubhGS, 7, 7), (az.OpenTaflGS, 11, 8)):
