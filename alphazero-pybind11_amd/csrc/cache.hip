@@ -80,7 +80,7 @@ __global__ void k_cache_find_many(CacheView c, const uint64_t* hashes, uint32_t 
   for (uint32_t j = 0; j < c.nv; ++j) value[static_cast<size_t>(i) * c.nv + j] = sv[j];
 }
 
-// k_pipe_cache_insert's shape (pipeline.hip) on host-given entries: `waves` wavefronts stride over the n entries, each entry
+// k_pipe_cache_insert's shape (pipe_net_kernels.h) on host-given entries: `waves` wavefronts stride over the n entries, each entry
 // under its shard's insert lock
 __global__ __launch_bounds__(256) void k_debug_insert_locked(CacheView c, uint32_t* locks, const uint64_t* keys, const float* policy,
                                                              const float* value, uint32_t n, uint32_t waves, uint32_t* failed) {

@@ -168,9 +168,9 @@ __global__ __launch_bounds__(256, 2) void k_net_move(azmi_net_dev::NetDesc nd, a
 }
 
 }  // namespace
-// the two between-epoch steps of the asynchronous pipeline (pipeline.hip): the move step of a split round over the slots the
+// the two between-epoch steps of the asynchronous pipeline (pipeline_run.hip): the move step of a split round over the slots the
 // tree side listed, as a launch of its own, and the restart / retire bookkeeping
-unsigned long long azmi_host_pipe_l0_hits(azmi_pm* pm, hipStream_t st);    // pipeline.hip
+unsigned long long azmi_host_pipe_l0_hits(azmi_pm* pm, hipStream_t st);    // pipeline_state.hip
 int azmi_host_launch_move_step(azmi_pm* pm, hipStream_t st) {
   const uint32_t blocks = (pm->ep.S * Connect4::GROUP + 255u) / 256u;
   k_round<Connect4, false, true><<<blocks, 256, 0, st>>>(pm->ep, pm->ar);

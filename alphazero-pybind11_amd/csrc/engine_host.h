@@ -5,7 +5,8 @@
 //                     shares a module with) and launches them for the two files below; defines k_assign
 //   mcts_object.hip   the stand-alone MCTS object (azmi_mcts_*) on a one-slot engine; host code only
 //   replay.hip        rules replay, playout evaluation, StarGambit images and the RNG probe; host code only
-//   pipeline.hip      the asynchronous tree / net pipeline
+//   pipeline.hip      the asynchronous tree / net pipeline: the one device module of the three pipe_*_kernels.h and their launch
+//                     functions; pipeline_state.hip, pipeline_run.hip and pipeline_debug.hip are its host code (pipeline_host.h)
 //   search_batch.hip  the batched position search (azmi_search_*): the one device module of the four search_*_kernels.h, every
 //                     launch of them, and the core entry points.  search_batch_sweep.hip, search_batch_pool.hip and
 //                     search_batch_frontier.hip hold the entry points of those three families; host code only, they launch
@@ -99,7 +100,7 @@ struct GameInfo {
   uint32_t cap_branch;  // children per expansion the tree arena is sized for (== maxk when that is affordable)
 };
 
-// the asynchronous pipeline's own HBM (pipeline.hip), created on first use
+// the asynchronous pipeline's own HBM (pipeline_host.h), created on first use
 struct PipeState;
 void pipe_state_free(PipeState* p);
 }  // namespace azmi
@@ -140,7 +141,7 @@ struct azmi_pm {
   // The reference's callers reach one PlayManager from several Python threads (mcts_workers x play(), batcher threads with
   // build_batch / update_inferences, the main thread with counters): every entry point that touches the engine's host state
   // takes this lock, so such callers are serialised instead of racing.  (Recursive: entry points call each other.)
-  azmi::PipeState* pipe = nullptr;   // the asynchronous tree / net pipeline (pipeline.hip), created by its first run
+  azmi::PipeState* pipe = nullptr;   // the asynchronous tree / net pipeline (pipeline_host.h), created by its first run
   std::recursive_mutex mu;    // PlayManager::stop(), play_manager.h:177 (may be set from another thread)
 
   template <class T>

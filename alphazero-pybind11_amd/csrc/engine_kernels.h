@@ -1327,7 +1327,7 @@ struct SlotCtx {
 // net launch of the round; a leaf it sends to the net is only written (kSlotQueued), the next round's k_sim lists it.
 // round_slot: the round of ONE slot by its lane group (lane = 0 .. GROUP-1); returns the slot state it stored (kSlotWaitEval,
 // kSlotQueued, kSlotEnded, kSlotDone) or 0xFF when it had nothing to do.  round_body maps a thread to its slot (kMover: through
-// ar.mover_list); the asynchronous pipeline's mover wavefronts (pipeline.hip) call round_slot on the slots their tokens name.
+// ar.mover_list); the asynchronous pipeline's mover wavefronts (pipe_tree_kernels.h) call round_slot on the slots their tokens name.
 template <class GM, bool kPlayout = false, bool kMover = false>
 __device__ __forceinline__ uint32_t round_slot(const EngineParams& ep, const EngineArrays& ar, const uint32_t slot, const uint32_t lane) {
   constexpr int G = GM::GROUP;

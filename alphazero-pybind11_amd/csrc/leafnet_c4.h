@@ -6,6 +6,8 @@
 
 #include <type_traits>
 
+#include "leafnet_c4_types.h"
+
 namespace azmi_net_dev {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -21,23 +23,7 @@ constexpr int NWAVES = NTHREADS / 64;
 constexpr int WFRAG_BYTES = 1024; // one MFMA A-fragment: 64 lanes x 16 B
 constexpr int MT = 4;             // m-tiles (16 output channels each)
 
-struct NetDesc {
-  int C_in, H, W, depth, num_moves, num_players, v_hidden;
-};
-
-struct NetPtrs {           // device pointers into the folded weight blob
-  const uint8_t* stem_w;   // [2 ks][4 mt] fragments
-  const float* stem_b;     // [64]
-  const uint8_t* blocks;   // per block: a1[64] b1[64] c1[64] (fp32) | conv1 frags | conv2 frags
-  const uint8_t* head_w;   // [2 ks][4 mt] fragments (rows 0-31 value conv, 32-63 policy conv)
-  const float* head_b;     // [64]
-  const float* v_fc1_w;    // f32 A-fragments [v_hidden / 16][2][64 lanes][4] (hip_net._f32_frags)
-  const float* v_fc1_b;    // [v_hidden]
-  const float* v_fc2_w;    // [P+1][v_hidden]
-  const float* v_fc2_b;    // [P+1]
-  const uint8_t* pi_fc_w;  // per pixel position p: bf16 A-fragment of W_p[m][c] = W[m][c*H*W + p] (rows >= M zero), high parts, then low parts
-  const float* pi_fc_b;    // [M]
-};
+// (NetDesc, NetPtrs and azmi_net_c4_view: leafnet_c4_types.h)
 
 __device__ __forceinline__ bf16x8 lds_read_frag(const uint8_t* p) {
   return *reinterpret_cast<const bf16x8*>(p);
@@ -150,7 +136,7 @@ __device__ __forceinline__ void barrier_lds() {
 // 6 = stem only, 7 = stem + trunk, 8 = ... + head 1x1 convolution, 9 = ... + policy FC partials and value pool, 10 = ... + value FCs
 // `tile_index` = which tile of TBW rows this workgroup takes (the block index of the plain launch; the fused net + move-step
 // launch of the engine passes its own); `lds` = the workgroup's LDS_BYTES of dynamic LDS.
-// PIPE (the asynchronous pipeline's persistent net workgroups, pipeline.hip): the caller has already written the tile's raw
+// PIPE (the asynchronous pipeline's persistent net workgroups, pipe_net_kernels.h): the caller has already written the tile's raw
 // input planes into their LDS staging area (ring slot 4: [board][CIN][PIX] floats) - there is no DMA from `canon` -, and the
 // outputs leave as tagged result granules instead of rows: entry k of board b (pi entries first, then the value entries) goes to
 // pio->res[pio->slot[b] * pio->stride + k] as ONE 8-byte agent-scope store {pio->seq[b] << 32 | float bits}; boards whose
@@ -764,16 +750,6 @@ __global__ __launch_bounds__(NTH, 2) void k_leafnet_c4(NetDesc nd, NetPtrs np, c
 
 }  // namespace azmi_net_dev
 
-// the net object behind the C ABI (leafnet.hip owns it; engine.hip reads nd / np / lds_bytes for the fused launch)
-struct azmi_net_c4_view {
-  azmi_net_dev::NetDesc nd;
-  azmi_net_dev::NetPtrs np;
-  size_t lds_bytes;
-  int x3;                 // the bf16x3 tier (split bf16 operands, Tile<.., SPLIT>): one workgroup per CU; only the pipeline runs it through a view
-};
-// fills `out` when `net` is a Connect4-family net on the matrix cores (bf16, or bf16x3: out->x3 - the lock-step engine's fused
-// launch takes the bf16 tile only and checks the flag); returns 0 otherwise
-extern "C" int azmi_net_c4_view_get(const struct azmi_net* net, azmi_net_c4_view* out);
 // allocates the per-stream scratch a forward of up to `max_rows` rows on `stream` needs (a forward allocates it on first use,
 // which a stream capture does not allow); 0 = ok
 extern "C" int azmi_net_reserve_stream(struct azmi_net* net, void* stream, uint32_t max_rows);

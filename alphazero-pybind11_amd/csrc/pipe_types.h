@@ -1,4 +1,4 @@
-// Asynchronous tree / net pipeline of the Connect4 engine (pipeline.hip): the structures its kernels share.
+// Asynchronous tree / net pipeline of the Connect4 engine (pipeline_host.h names its translation units): the structures its kernels share.
 //
 // The reference's worker loop has no global barrier: every game advances on its own through the queues between the MCTS
 // workers and the batcher threads (play_manager.cc:258-600, concurrent_queue.h:130-217).  The lock-step round of
@@ -49,6 +49,7 @@ __host__ __device__ inline uint32_t pipe_l0_tag(uint64_t key, uint32_t k) { retu
 __host__ __device__ inline uint64_t pipe_lap_tag_r(uint32_t pos, uint32_t shift) { return static_cast<uint64_t>(((pos >> shift) & 0x7FFFu) + 1u); }
 constexpr unsigned long long kTokMove = 0x8000ull;     // token: the slot's next step is the move step's (a game start, the simulation that completes a search)
 constexpr unsigned long long kTokSlotMask = 0x7FFFull;
+constexpr uint32_t kTreeWindow = 8;      // tokens a tree wavefront draws per pass at most: one per 8-lane group (a READY ring has room for two windows beyond its slots' tokens)
 
 struct PipeWg {           // one 128-byte line per tree workgroup: its READY ring's positions (free-running)
   uint32_t rhead;         // positions drawn by the workgroup's wavefronts

@@ -201,7 +201,7 @@ __device__ __forceinline__ void barrier_lds() {
 // 6 = stem only, 7 = stem + trunk, 8 = ... + head 1x1 convolution, 9 = ... + policy FC partials and value pool, 10 = ... + value FCs
 // `tile_index` = which tile of TBW rows this workgroup takes (the block index of the plain launch; the fused net + move-step
 // launch of the engine passes its own); `lds` = the workgroup's LDS_BYTES of dynamic LDS.
-// PIPE (the asynchronous pipeline's persistent net workgroups, pipeline.hip): the caller has already written the tile's raw
+// PIPE (the asynchronous pipeline's persistent net workgroups, pipe_net_kernels.h): the caller has already written the tile's raw
 // input planes into their LDS staging area (ring slot 4: [board][CIN][PIX] floats) - there is no DMA from `canon` -, and the
 // outputs leave as tagged result granules instead of rows: entry k of board b (pi entries first, then the value entries) goes to
 // pio->res[pio->slot[b] * pio->stride + k] as ONE 8-byte agent-scope store {pio->seq[b] << 32 | float bits}; boards whose

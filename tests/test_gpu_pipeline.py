@@ -1,4 +1,4 @@
-"""-m gpu: the asynchronous tree / net pipeline (azmi_run_pipeline, csrc/pipeline.hip) plays the games of the lock-step engine and
+"""-m gpu: the asynchronous tree / net pipeline (azmi_run_pipeline, csrc/pipeline*.hip) plays the games of the lock-step engine and
 of the oracle.  A slot's game is a function of its seed alone: the answer to a position does not depend on when, where or in
 which tile the net evaluates it, so persistent tree wavefronts + persistent net workgroups (request ring, tagged result granules,
 moves and cache inserts between epochs) must reproduce, move for move / visit count for visit count / pcg32 position for pcg32
