@@ -5,25 +5,19 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "../../include/azmi.h"
 #include "cache_host.h"
+#include "host_error.h"
 
 using namespace azmi;
 
 namespace {
 thread_local std::string g_cache_err;
 int cfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_cache_err = buf;
+  AZMI_FORMAT_ERROR(g_cache_err, fmt);
   return code;
 }
 

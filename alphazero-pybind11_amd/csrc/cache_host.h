@@ -1,4 +1,4 @@
-// Host-side allocation of a device S3-FIFO cache (shared by engine.hip and cache.hip).
+// Host-side allocation of a device S3-FIFO cache (shared by engine_create.hip and cache.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

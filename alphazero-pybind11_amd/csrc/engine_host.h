@@ -1,10 +1,19 @@
 // Host-side state of one PlayManager engine and the host helpers shared by the translation units of libazmi.so that launch
 // kernels on it:
-//   engine.hip        the lock-step round loop, azmi_pm_* / azmi_run_rounds* and the error text.  It is also the one device
-//                     module of the engine, MCTS-object and replay kernels (the code of a kernel depends on the kernels it
-//                     shares a module with) and launches them for the two files below; defines k_assign
-//   mcts_object.hip   the stand-alone MCTS object (azmi_mcts_*) on a one-slot engine; host code only
-//   replay.hip        rules replay, playout evaluation, StarGambit images and the RNG probe; host code only
+//   engine.hip          the ONE device module of the engine, MCTS-object and replay kernels (the code of a kernel depends on the
+//                       kernels it shares a module with and on the order they are instantiated in, DESIGN.md sections 1 and 8.3):
+//                       the kernel headers, k_assign / k_seed / k_net_move / k_delay, the azmi_host_launch_* functions below and
+//                       nothing else
+//   engine_create.hip   the error text (azmi_host_fail, azmi_last_error), the defaults, the description of a game, the seat
+//                       tables, azmi_pm_create* / azmi_pm_destroy
+//   engine_rounds.hip   the lock-step round loop: azmi_pm_round*, azmi_run_rounds* and their hipGraph, azmi_pm_net_forward*,
+//                       azmi_pm_play, azmi_pm_poll, azmi_host_read_ctl
+//   engine_results.hip  the read-outs: scores, statistics, counters, slot state, the history ring, the move log, debug reads
+//   engine_hostbuf.hip  the host-buffer compatibility path: azmi_pm_build_batch*, azmi_pm_update_inferences
+//   mcts_object.hip     the stand-alone MCTS object (azmi_mcts_*) on a one-slot engine
+//   replay.hip          rules replay, playout evaluation, StarGambit images and the RNG probe
+//                       The last six are host code only: they launch through engine.hip, and an edit to them cannot move a kernel.
+//                       The four engine_* units include no kernel header and their objects carry no device code.
 //   pipeline.hip      the asynchronous tree / net pipeline: the one device module of the three pipe_*_kernels.h and their launch
 //                     functions; pipeline_state.hip, pipeline_run.hip and pipeline_debug.hip are its host code (pipeline_host.h)
 //   search_batch.hip  the batched position search (azmi_search_*): the one device module of the four search_*_kernels.h, every
@@ -26,7 +35,7 @@
 #include "../../include/azmi.h"
 #include "engine_types.h"
 
-// sets the thread's azmi_last_error() text and returns `code` (defined in engine.hip)
+// sets the thread's azmi_last_error() text and returns `code` (defined in engine_create.hip)
 int azmi_host_fail(int code, const char* fmt, ...);
 #define AZMI_HIP_TRY(expr)                                                                \
   do {                                                                                    \
@@ -166,12 +175,39 @@ struct azmi_pm {
   }
 };
 
-// ---- defined in engine.hip for mcts_object.hip and replay.hip ------------------------------------------------------------------------
-// the static description of a game id (false: unknown id), and the engine's Control block read back on `st` - after a settling
-// k_assign when `settle` - with a raised overflow mask turned into AZMI_ERR_OVERFLOW
+namespace azmi {
+// `n` elements of a device array into `dst`, behind everything queued on `st`
+template <class T>
+int d2h(std::vector<T>& dst, const T* src, size_t n, hipStream_t st) {
+  dst.resize(n);
+  AZMI_HIP_TRY(hipMemcpyAsync(dst.data(), src, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  AZMI_HIP_TRY(hipStreamSynchronize(st));
+  return AZMI_OK;
+}
+}  // namespace azmi
+
+// the static description of a game id (false: unknown id; engine_create.hip), and the engine's Control block read back on `st` -
+// after a settling k_assign when `settle` - with a raised overflow mask turned into AZMI_ERR_OVERFLOW (engine_rounds.hip)
 bool azmi_host_game_info(int game, azmi::GameInfo* gi);
 int azmi_host_read_ctl(azmi_pm* pm, hipStream_t st, azmi::Control* out, bool settle);
-// One launch each, arguments as the kernels take them.  Replay family: on the null stream, grids sized by n.
+
+// ---- defined in engine.hip, the device module: one launch each, arguments as the kernels take them ------------------------------------
+// A round of the engine's game on `st`: cache insert + restart / retire bookkeeping, then the tree kernels.  defer_moves (split
+// rounds only) leaves the move step to the azmi_host_launch_net_move that follows: the tiles of the round's eval list through the
+// net of `view` and the move step, in one launch.
+struct azmi_net_c4_view;
+int azmi_host_launch_round(azmi_pm* pm, hipStream_t st, bool defer_moves = false);
+int azmi_host_launch_net_move(azmi_pm* pm, const azmi_net_c4_view& view, hipStream_t st);
+// the two between-epoch steps of the pipeline: the move step of a split round as a launch of its own, and k_assign
+int azmi_host_launch_move_step(azmi_pm* pm, hipStream_t st);
+int azmi_host_launch_assign(azmi_pm* pm, hipStream_t st, uint32_t count_round);
+// k_assign that counts no round, unchecked: the read-back behind it reports (azmi_host_read_ctl)
+void azmi_host_launch_settle(azmi_pm* pm, hipStream_t st);
+// the three RNG streams of every slot from `seed`, on the engine's own stream
+void azmi_host_launch_seed(azmi_pm* pm, uint64_t seed);
+// one wavefront that holds `st` for about `us` microseconds
+void azmi_host_launch_delay(uint32_t us, hipStream_t st);
+// Replay family: on the null stream, grids sized by n.
 void azmi_host_launch_replay(int game, const uint8_t* d_init, uint32_t init_stride, const int32_t* d_moves, uint32_t n, uint32_t len, uint64_t* d_rep,
                              uint32_t stride, uint8_t* d_valid, float* d_scores, float* d_canon, uint32_t* d_player, uint32_t* d_turn, uint64_t* d_key,
                              int32_t* d_status, uint32_t flags);

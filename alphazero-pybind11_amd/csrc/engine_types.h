@@ -1,4 +1,4 @@
-// Plain-data views shared by the host side (engine.hip) and the kernels
+// Plain-data views shared by the host side (engine_*.hip) and the kernels
 // (engine_kernels.h).  Everything the engine owns lives in HBM as
 // structure-of-arrays; these structs only carry the base pointers.
 #pragma once

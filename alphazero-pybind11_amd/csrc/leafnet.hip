@@ -20,7 +20,6 @@
 // device, launches.  The fp32 correctness path lives in leafnet_f32.hip.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +29,7 @@
 #include <vector>
 
 #include "../../include/azmi.h"
+#include "host_error.h"
 #include "leafnet_f32.h"
 #include "leafnet_c4.h"
 #include "leafnet_sp.h"
@@ -40,12 +40,7 @@ using namespace azmi_net_dev;
 
 thread_local std::string g_net_err;
 int nfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_net_err = buf;
+  AZMI_FORMAT_ERROR(g_net_err, fmt);
   return code;
 }
 

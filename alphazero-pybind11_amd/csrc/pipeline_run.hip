@@ -17,10 +17,6 @@
 
 using namespace azmi;
 
-// defined in engine.hip: the move step of a split round as its own launch, and the restart / retire bookkeeping
-int azmi_host_launch_move_step(azmi_pm* pm, hipStream_t st);
-int azmi_host_launch_assign(azmi_pm* pm, hipStream_t st, uint32_t count_round);
-
 namespace {
 
 // An epoch's workgroup counts assume the chip to itself (placement): two engines' epochs at once would each find half of

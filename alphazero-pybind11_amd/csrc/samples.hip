@@ -5,14 +5,13 @@
 // asynchronous launch each, azmi_sample_metrics_reduce synchronises once for its record.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <mutex>
 #include <string>
 
 #include "../../include/azmi.h"
 #include "engine_host.h"
+#include "host_error.h"
 #include "samples_kernels.h"
 #include "sample_metrics_kernels.h"
 #include "samples_layout.h"
@@ -27,12 +26,7 @@ static_assert(kSampleMetricColumns == AZMI_SAMPLE_METRIC_COLUMNS && kMetricMaxBu
 thread_local std::string g_samples_err;
 
 int sfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_samples_err = buf;
+  AZMI_FORMAT_ERROR(g_samples_err, fmt);
   return code;
 }
 
