@@ -1,5 +1,6 @@
 """phase timing of the wide-game round kernel (a -DAZMI_BIG_PROF build: AZMI_HIPCC_EXTRA=-DAZMI_BIG_PROF python -c 'import __graft_entry__ as g; g.build()'):
-Tawlbwrdd 2048 x 400 on 4 lock-step shards with the HIP net, ticks per phase summed over every wave / rounds"""
+Tawlbwrdd 2048 x 400 on 4 lock-step shards with the HIP net, ticks per phase summed over every wave / rounds.  With the profile build
+kept beside the product's: AZMI_LIB=<that libazmi.so> GAME=stargambit timeout -k 10 300 python scripts/big_prof.py (profiles/r6_sg_phase_prof.txt)"""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "alphazero-pybind11_amd"))

@@ -1,6 +1,11 @@
 """Writes spx.h = csrc/leafnet_sp.h with early exits (-DX_DBG=n) for sp_exp.hip: 1 after the stem, 2 after the trunk, 3 after the head
 1x1 convolutions, 4 after the value head's extra convolution + pool, 5 after the policy head's convolutions and logits, 0 = the whole tile.
-Generated (not committed): the product header is the source, the experiment only adds exits."""
+Generated (not committed): the product header is the source, the experiment only adds exits.
+One binary per exit point, built first, then run one after the other (here, in scripts/micro/tile_exp; T = a directory for the binaries):
+    python make_spx.py
+    for d in 1 2 3 4 5 0; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -DX_DBG=$d sp_exp.hip -o $T/spx_$d || exit 1; done
+    for d in 1 2 3 4 5 0; do timeout -k 5 120 $T/spx_$d >> sp_tile_timing.txt 2>&1 || break; done
+    sort -k1,1 -k5,5n -k3,3n sp_tile_timing.txt                 (profiles/r6_sp_tile_timing.txt)"""
 import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 src = open(os.path.join(HERE, "..", "..", "..", "alphazero-pybind11_amd", "csrc", "leafnet_sp.h")).read()

@@ -1,4 +1,7 @@
-"""quick throughput probe of the pipeline (not the bench): Connect4 S x SIMS, bench flags, prints per-block rates"""
+"""quick throughput probe of the pipeline (not the bench): Connect4 S x SIMS, bench flags, prints per-block rates.
+The headline engine, as every A/B and one-knob sweep of profiles/r5_*.txt and r6_*.txt ran it (scripts/ab.py for two builds; for a sweep
+set the knob - AZMI_PIPE_TREE_WGS, AZMI_WHATIF_NET_DEPTH, Q with E = 20480 / Q - per run, the default first and last):
+    CACHE=128000000 Q=256 E=80 BLOCKS=4 PRE=1.0 timeout -k 10 240 python scripts/pipe_bench.py"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "alphazero-pybind11_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -1,6 +1,8 @@
 """the pipeline's tree kernel ALONE (every seat EvalType.RANDOM: no request ever leaves, no net kernel is launched): Connect4
 S x SIMS with the bench flags.  What `rocprofv3 --pmc` can look at (one persistent kernel, no partner), and what the tree side's
-latency chain costs without a net workgroup on its CU.  Prints simulations/s per block; AZMI_PIPE_PROF=1 adds the pass accounting."""
+latency chain costs without a net workgroup on its CU.  Prints simulations/s per block; AZMI_PIPE_PROF=1 adds the pass accounting.
+Under --pmc (profiles/r6_pmc_tree.csv): E=20 BLOCKS=2 STATS_OUT=<file.json> (the simulations per epoch, to divide the counters by), one
+counter set per pass (scripts/README.md, rocprofv3)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "alphazero-pybind11_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -1,5 +1,7 @@
 """bounded reproduction loop for an intermittent pipeline error on the generic tree kernel (AZMI_PIPE_GENERIC=1): the failing test's
-configuration, N engines one after the other; stops at the first error and prints it"""
+configuration, N engines one after the other; stops at the first error and prints it with the kernel's diagnostic words (stderr:
+"pipeline dbg: ...").  Bounded twice, by N and by a time limit - never an open-ended loop:
+    N=2500 timeout -k 10 1100 python scripts/repro_generic.py > repro_generic.txt 2>&1; tail -5 repro_generic.txt"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "alphazero-pybind11_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))

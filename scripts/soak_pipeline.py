@@ -5,7 +5,7 @@
   SHAPE=slots_16384      the headline engine with 16384 concurrent games (one group, PUCT)
   SHAPE=headline         the bench's engine itself (4096 x 800, 128 M-entry cache), epochs of 256 simulations per slot
 A pipeline error RAISES (no retry here): the run stops at the first one and prints it.  Credited freezes, lost requests and every
-error are counted in the last line."""
+error are counted in the last line.  profiles/r6_soak_*.txt: N=20000 (SHAPE=slots_16384: N=3000), each under `timeout -k 10 500`."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "alphazero-pybind11_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
