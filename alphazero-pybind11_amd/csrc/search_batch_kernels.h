@@ -16,7 +16,12 @@
 // Every step has two kernels: k_sb_X for Connect4's 8-lane engine (SlotCtx, 256 threads, slot = thread / GROUP) and k_sb_big_X
 // for the wavefront-per-tree engine (BigSlot, 64 threads, slot = block, BigScratch in LDS).  They stay plain twins: a body
 // shared through a template over the context type computes the same, but the compiler then allocates registers differently
-// in most of them.  Shared is what compiles to the same code: the seed kernels' tail and the compaction kernels' scan.
+// in most of them.  The grid-to-slot mapping and the loop over a step's descents are written per kernel.  What a second step
+// shape would repeat is a named __forceinline__ helper - on the concrete context type (SlotCtx<GM>& or BigSlot<GM>&) where it
+// calls a tree function (find_leaf, find_leaf_wu, process_result, playout_eval), across the engines only where it calls none -
+// IF every kernel then compiles to the code it had.  That holds for the bookkeeping rows: sb_seed_tail, sb_scan_1024,
+// sb_skip_tree, sb_checkpoint_tail, sb_dl_close_tree.  It does not hold for the verdict on a net leaf, the WU-UCT back-up at
+// once, the PLAYOUT leaf and the copied (v, pi) row, which stay pasted ("Layout of search_batch_kernels.h").
 #pragma once
 #include "mcts_object_kernels.h"
 #include "search_batch_types.h"      // SbPend, SbStatus, kNoRow and the Sb*Arrays views named below
@@ -84,16 +89,19 @@ __global__ __launch_bounds__(64) void k_sb_big_seed(EngineParams ep, EngineArray
 // A terminal leaf is backed up here.  Otherwise: RANDOM evaluator -> kPendRandom; cache hit -> the answer lands in the slot's
 // (v, pi) rows, kPendCached; else the leaf's planes go to the slot's canonical row (and its key to ar.cache_keys when a cache
 // is attached), kPendRow.  k_sb_compact then numbers the kPendRow trees in ascending tree order.
+
+// a tree that sits a step out (stopped, finished, paused, nothing owed) leaves neither a pending simulation nor a key to insert
+__device__ __forceinline__ void sb_skip_tree(const SbArrays& sb, const EngineParams& ep, const EngineArrays& ar, uint32_t slot, uint32_t lane) {
+  if (lane == 0) { sb.pend[slot] = kPendNone; if (ep.cache_on) ar.cache_keys[slot] = 0; }
+}
+
 template <class GM>
 __global__ __launch_bounds__(256) void k_sb_find(EngineParams ep, EngineArrays ar, SbArrays sb, uint32_t n, uint32_t eval_random) {
   constexpr int G = GM::GROUP;
   const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t slot = gtid / G, lane = gtid % G;
   if (slot >= n) return;
-  if (sb.status[slot] != 0) {
-    if (lane == 0) { sb.pend[slot] = kPendNone; if (ep.cache_on) ar.cache_keys[slot] = 0; }
-    return;
-  }
+  if (sb.status[slot] != 0) { sb_skip_tree(sb, ep, ar, slot, lane); return; }
   SlotCtx<GM> c(ep, ar, slot, lane);
   c.load();
   typename GM::State leaf;
@@ -127,10 +135,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find(EngineParams ep, EngineArray
   __shared__ BigScratch<GM> sm;
   const uint32_t slot = blockIdx.x, lane = threadIdx.x;
   if (slot >= n) return;
-  if (sb.status[slot] != 0) {
-    if (lane == 0) { sb.pend[slot] = kPendNone; if (ep.cache_on) ar.cache_keys[slot] = 0; }
-    return;
-  }
+  if (sb.status[slot] != 0) { sb_skip_tree(sb, ep, ar, slot, lane); return; }
   BigSlot<GM> c(ep, ar, sm, slot, lane);
   c.load();
   typename GM::State leaf;
@@ -978,6 +983,18 @@ __global__ __launch_bounds__(256) void k_sb_todo_set(SbArrays sb, SbDlArrays dl,
   if (i < n) dl.todo[i] = sb.status[i] == 0 ? visits : 0u;
 }
 
+// what a tree's step leaves behind (lane 0 of the tree): its pending leaf, the key to insert (KEYS: the net path; the PLAYOUT
+// kernels have no cache), the terminal leaves it met, the descents it still owes and their share of the step's maximum
+template <bool KEYS>
+__device__ __forceinline__ void sb_dl_close_tree(const SbArrays& sb, const SbDlArrays& dl, const EngineParams& ep, const EngineArrays& ar, uint32_t slot,
+                                                 uint32_t parity, uint32_t pend, uint32_t n_term, uint32_t left, uint64_t ins_key) {
+  sb.pend[slot] = static_cast<uint8_t>(pend);
+  if constexpr (KEYS) if (ep.cache_on) ar.cache_keys[slot] = ins_key;
+  if (n_term) sb.n_term[slot] += n_term;
+  dl.todo[slot] = left;
+  if (left) atomicMax(&dl.todo_max[parity], left);
+}
+
 template <class GM>
 __global__ __launch_bounds__(256) void k_sb_find_dl(EngineParams ep, EngineArrays ar, SbArrays sb, SbDlArrays dl, uint32_t n, uint32_t L,
                                                     uint32_t parity, uint32_t eval_random, uint32_t root_noise) {
@@ -987,10 +1004,7 @@ __global__ __launch_bounds__(256) void k_sb_find_dl(EngineParams ep, EngineArray
   if (gtid == 0) dl.todo_max[parity ^ 1u] = 0;
   if (slot >= n) return;
   uint32_t left = dl.todo[slot];
-  if (sb.status[slot] != 0 || left == 0) {      // (the step before left nothing pending)
-    if (lane == 0) { sb.pend[slot] = kPendNone; if (ep.cache_on) ar.cache_keys[slot] = 0; }
-    return;
-  }
+  if (sb.status[slot] != 0 || left == 0) { sb_skip_tree(sb, ep, ar, slot, lane); return; }      // (the step before left nothing pending)
   SlotCtx<GM> c(ep, ar, slot, lane);
   c.load();
   uint32_t pend = kPendNone, n_term = 0;
@@ -1019,13 +1033,7 @@ __global__ __launch_bounds__(256) void k_sb_find_dl(EngineParams ep, EngineArray
     }
     c.process_result(0, from_net != 0, term == 0 && root_noise != 0);     // what k_sb_find / k_sb_process pass for this kind of leaf
   }
-  if (lane == 0) {
-    sb.pend[slot] = static_cast<uint8_t>(pend);
-    if (ep.cache_on) ar.cache_keys[slot] = ins_key;
-    if (n_term) sb.n_term[slot] += n_term;
-    dl.todo[slot] = left;
-    if (left) atomicMax(&dl.todo_max[parity], left);
-  }
+  if (lane == 0) sb_dl_close_tree<true>(sb, dl, ep, ar, slot, parity, pend, n_term, left, ins_key);
   c.store(kSlotWaitEval);
 }
 
@@ -1037,10 +1045,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find_dl(EngineParams ep, EngineAr
   if (slot == 0 && lane == 0) dl.todo_max[parity ^ 1u] = 0;
   if (slot >= n) return;
   uint32_t left = dl.todo[slot];
-  if (sb.status[slot] != 0 || left == 0) {
-    if (lane == 0) { sb.pend[slot] = kPendNone; if (ep.cache_on) ar.cache_keys[slot] = 0; }
-    return;
-  }
+  if (sb.status[slot] != 0 || left == 0) { sb_skip_tree(sb, ep, ar, slot, lane); return; }
   BigSlot<GM> c(ep, ar, sm, slot, lane);
   c.load();
   uint32_t pend = kPendNone, n_term = 0;
@@ -1067,13 +1072,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find_dl(EngineParams ep, EngineAr
     }
     c.process_result(0, from_net != 0, term == 0 && root_noise != 0);
   }
-  if (lane == 0) {
-    sb.pend[slot] = static_cast<uint8_t>(pend);
-    if (ep.cache_on) ar.cache_keys[slot] = ins_key;
-    if (n_term) sb.n_term[slot] += n_term;
-    dl.todo[slot] = left;
-    if (left) atomicMax(&dl.todo_max[parity], left);
-  }
+  if (lane == 0) sb_dl_close_tree<true>(sb, dl, ep, ar, slot, parity, pend, n_term, left, ins_key);
   c.sync();
   c.store(kSlotWaitEval);
 }
@@ -1114,12 +1113,7 @@ __global__ __launch_bounds__(256) void k_sb_find_dl_po(EngineParams ep, EngineAr
     ++n_term;
     c.process_result(0, true, false);
   }
-  if (lane == 0) {
-    sb.pend[slot] = static_cast<uint8_t>(pend);
-    if (n_term) sb.n_term[slot] += n_term;
-    dl.todo[slot] = left;
-    if (left) atomicMax(&dl.todo_max[parity], left);
-  }
+  if (lane == 0) sb_dl_close_tree<false>(sb, dl, ep, ar, slot, parity, pend, n_term, left, 0);
   c.store(kSlotWaitEval);
 }
 
@@ -1157,12 +1151,7 @@ __global__ __launch_bounds__(64) void k_sb_big_find_dl_po(EngineParams ep, Engin
     ++n_term;
     c.process_result(0, true, false);
   }
-  if (lane == 0) {
-    sb.pend[slot] = static_cast<uint8_t>(pend);
-    if (n_term) sb.n_term[slot] += n_term;
-    dl.todo[slot] = left;
-    if (left) atomicMax(&dl.todo_max[parity], left);
-  }
+  if (lane == 0) sb_dl_close_tree<false>(sb, dl, ep, ar, slot, parity, pend, n_term, left, 0);
   c.sync();
   c.store(kSlotWaitEval);
 }
