@@ -10,8 +10,9 @@ reference lacks (`PlayManager.round`, `io_tensors`).
 Put the directory that contains this package on sys.path:
     sys.path.insert(0, "<repo>/alphazero-pybind11_amd"); import alphazero
 
-This file only re-exports; the code lives in the sibling modules (params, games, mcts, search_batch, opening_tree, evaluators, cache,
-play_manager, drivers, samples), whose imports follow that order and never form a cycle.
+This file only re-exports; the code lives in the sibling modules (params, games, mcts, search_batch_sweep, search_batch_pool,
+search_batch_frontier, search_batch, opening_tree, evaluators, cache, play_manager, drivers, samples), whose imports follow that order
+and never form a cycle; _args (the shared argument checks) and _rng (the seed derivations of csrc/dev_rng.h) import none of them.
 """
 from . import _capi
 from ._capi import lib, check
@@ -21,7 +22,9 @@ from .games import (GameState, Connect4GS, _TaflBoardGS, TawlbwrddGS, BrandubhGS
                     _StarGambitPlainGS, StarGambitSkirmishGS, StarGambitShowdownGS, StarGambitClashGS, StarGambitBattleGS, StarGambitGS,
                     _c4_from_bytes, _tafl_from_bytes, _sg_from_bytes, hash_game_state, game_replay, symmetries_batch, tafl_symmetries)
 from .mcts import MCTS, Query, _ENGINE_STREAM
-from .search_batch import MCTSBatch, pool_unique, policy_divergences, POLICY_COLUMNS, SWEEP_COLUMNS
+from .search_batch_sweep import policy_divergences, POLICY_COLUMNS, SWEEP_COLUMNS
+from .search_batch_pool import pool_unique
+from .search_batch import MCTSBatch
 from .opening_tree import build_opening_tree, OpeningTree, OpeningNode, temperature_at_depth, node_seed
 from .evaluators import dumb_eval, playout_eval_batch, playout_eval
 from .cache import ShardedS3FIFOCache, S3FIFOCache

@@ -3,8 +3,10 @@ import math
 
 import numpy as np
 
+from . import _args
+from ._rng import MASK64, mix64
 from .games import GameState, hash_game_state
-from .search_batch import MCTSBatch
+from .search_batch import MCTSBatch, _evaluator
 
 
 def temperature_at_depth(depth, start_temp=1.0, final_temp=0.2, half_life=10):
@@ -17,7 +19,7 @@ def temperature_at_depth(depth, start_temp=1.0, final_temp=0.2, half_life=10):
 def node_seed(seed, b):
     """The tree seed of node b (BFS index, root 0) of build_opening_tree(..., seed=seed): MCTS(..., seed=node_seed(seed, b)) searched
     from tree.state(b) is that node's stand-alone twin."""
-    return MCTSBatch._mix64((int(seed) + int(b)) & MCTSBatch._MASK64)
+    return mix64((int(seed) + int(b)) & MASK64)
 
 
 class OpeningNode:
@@ -75,29 +77,18 @@ def _tree_args(game, start_state, sims, evaluator, net, cache, start_temp, final
         raise RuntimeError(f"{what}: game must be a game class or a state of one, got {game!r}")
     if getattr(start_state, "GAME_ID", None) != game.GAME_ID:
         raise RuntimeError(f"{what}: start_state must be a state of the tree's game")
-
-    def integer(name, v, lo):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-            raise RuntimeError(f"{what}: {name} must be an integer >= {lo}, got {v!r}")
-
-    def number(name, v, positive=False):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0 or (positive and not v > 0):
-            raise RuntimeError(f"{what}: {name} must be a finite {'positive' if positive else 'non-negative'} number, got {v!r}")
-
-    integer("sims", sims, 1)
-    integer("batch", batch, 1)
-    integer("max_depth", max_depth, 0)
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
-        raise RuntimeError(f"{what}: seed must be an integer, got {seed!r}")
-    number("min_reach", min_reach, positive=True)
-    number("start_temp", start_temp)
-    number("final_temp", final_temp)
-    number("half_life", half_life)
+    _args.integer(sims, f"{what}: sims must be an integer >= 1, got {sims!r}", 1)
+    _args.integer(batch, f"{what}: batch must be an integer >= 1, got {batch!r}", 1)
+    _args.integer(max_depth, f"{what}: max_depth must be an integer >= 0, got {max_depth!r}", 0)
+    _args.integer(seed, f"{what}: seed must be an integer, got {seed!r}")
+    _args.number(min_reach, f"{what}: min_reach must be a finite positive number, got {min_reach!r}", positive=True)
+    for name, v in (("start_temp", start_temp), ("final_temp", final_temp), ("half_life", half_life)):
+        _args.number(v, f"{what}: {name} must be a finite non-negative number, got {v!r}")
     for name in ("max_simulations", "seeds", "capture", "n", "game"):
         if name in mcts_args:
             raise RuntimeError(f"{what}: {name} is set by the builder (one MCTSBatch of `batch` trees with max_simulations = sims, "
                                "node b searched with seed node_seed(seed, b))")
-    return game, MCTSBatch._evaluator(what, evaluator, net, cache)
+    return game, _evaluator(what, evaluator, net, cache)
 
 
 def build_opening_tree(game, start_state, sims, net=None, cache=None, evaluator=None, start_temp=1.0, final_temp=0.2, half_life=10,

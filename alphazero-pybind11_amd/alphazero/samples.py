@@ -16,6 +16,7 @@ import enum
 
 import numpy as np
 
+from . import _args
 from ._capi import lib, ResampleRecordC, SampleMetricsRecordC
 
 MAX_ROWS = 1 << 30
@@ -94,18 +95,6 @@ def _check_rows(what, n):
         raise RuntimeError(f"{what}: at most 2^30 rows, got {n}")
 
 
-def _check_seed(what, seed):
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
-        raise RuntimeError(f"{what}: seed must be an integer in [0, 2^64), got {seed!r}")
-    return int(seed)
-
-
-def _check_device(what, device):
-    if isinstance(device, bool) or not isinstance(device, (int, np.integer)) or device < 0:
-        raise RuntimeError(f"{what}: device must be a device index, got {device!r}")
-    return int(device)
-
-
 def _stage(x, device):
     import torch
     return torch.from_numpy(x).to(torch.device("cuda", device))
@@ -164,7 +153,7 @@ def sample_loss(target, p, scale=1.0, device=0, stream=None):
     if not np.isfinite(scale):
         raise RuntimeError(f"{what}: scale must be finite, got {scale!r}")
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
         if n and (target < 0).any():
             i, m = np.argwhere(target < 0)[0]
             raise RuntimeError(f"{what}: a negative target: target[{i}, {m}] = {target[i, m]!r}")
@@ -207,9 +196,9 @@ def resample_plan(loss, seed, device=0, stream=None):
     n = int(loss.shape[0])
     _check_rows(what, n)
     _check_dtype(what, "loss", loss, "float64")
-    seed = _check_seed(what, seed)
+    seed = _args.seed64(seed, what)
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
         if n == 0:
             return np.zeros(0, np.uint32), np.zeros(0, np.uint64), 0, 0.0
         loss_t = _stage(loss, device)
@@ -268,10 +257,10 @@ def resample_rows(copies, offsets, *arrays, rows_out=None, device=0, stream=None
     _check_dtype(what, "copies", copies, ("uint32", "int32"))
     _check_dtype(what, "offsets", offsets, ("uint64", "int64"))
     _check_row_arrays(what, n, named)
-    if rows_out is not None and (isinstance(rows_out, bool) or not isinstance(rows_out, (int, np.integer)) or rows_out < 0):
-        raise RuntimeError(f"{what}: rows_out must be a row count, got {rows_out!r}")
+    if rows_out is not None:
+        _args.integer(rows_out, f"{what}: rows_out must be a row count, got {rows_out!r}", 0)
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
         total = int(copies.sum(dtype=np.uint64)) if rows_out is None else int(rows_out)
         if n == 0 or total == 0 or not arrays:
             return [np.zeros((total,) + x.shape[1:], np.float32) for x in arrays]
@@ -290,8 +279,7 @@ def _check_samples(what, samples, batch_rows):
         raise RuntimeError(f"{what}: samples must be the (canonical, v, pi) triple") from None
     named = (("canonical", canonical), ("v", v), ("pi", pi))
     kind = _kind(what, named)
-    if isinstance(batch_rows, bool) or not isinstance(batch_rows, (int, np.integer)) or batch_rows < 1:
-        raise RuntimeError(f"{what}: batch_rows must be an integer >= 1, got {batch_rows!r}")
+    _args.integer(batch_rows, f"{what}: batch_rows must be an integer >= 1, got {batch_rows!r}", 1)
     cs, vs, ps = tuple(canonical.shape), tuple(v.shape), tuple(pi.shape)
     if len(cs) < 4 or len(vs) != len(cs) - 2 or len(ps) != len(cs) - 2 or cs[:-3] != vs[:-1] or cs[:-3] != ps[:-1]:
         raise RuntimeError(f"{what}: the shapes of canonical [n, C, H, W], v [n, V] and pi [n, M] (or [n, NS, ...] each) do not agree: "
@@ -334,11 +322,11 @@ def resample_by_surprise(samples, net, seed, batch_rows=65536, data_folder=None,
     file naming, checkpoint loading and clean-up stay with the caller."""
     what = "resample_by_surprise"
     kind, n, c, v, pi = _check_samples(what, samples, batch_rows)
-    seed = _check_seed(what, seed)
+    seed = _args.seed64(seed, what)
     if not hasattr(net, "forward"):
         raise RuntimeError(f"{what}: net must be a HipLeafNet, got {type(net).__name__}")
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
         if n == 0:
             return (c.copy(), v.copy(), pi.copy()), np.zeros(0, np.float64)
         c, v, pi = _stage(c, device), _stage(v, device), _stage(pi, device)
@@ -380,7 +368,7 @@ def iteration_losses(samples, net, cv=1.0, batch_rows=65536, device=0, stream=No
     if n == 0:
         return 0.0, 0.0
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
         c, v, pi = _stage(c, device), _stage(v, device), _stage(pi, device)
     loss_pi, loss_v = _net_losses(net, c, v, pi, n, batch_rows, cv, stream)
     means = []
@@ -405,9 +393,7 @@ def _check_cv(what, cv):
 
 
 def _check_index(what, name, x):
-    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or x < 0:
-        raise RuntimeError(f"{what}: {name} must be an integer >= 0, got {x!r}")
-    return int(x)
+    return _args.integer(x, f"{what}: {name} must be an integer >= 0, got {x!r}", 0)
 
 
 def _launch_metrics(t_pi, p_pi, t_v, p_v, n, cv, cols, lo, mcts, net, stream):
@@ -466,7 +452,7 @@ def sample_metrics(pi_target, pi_p, v_target, v_p, cv=1.0, device=0, stream=None
         _check_dtype(what, name, x, "float32")
     cv = _check_cv(what, cv)
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
         if n == 0:
             out = {name: np.zeros(0, np.float64) for name in METRIC_COLUMNS}
             out.update({name: np.zeros(0, np.uint32) for name in INDEX_COLUMNS})
@@ -511,7 +497,7 @@ def plane_argmax(canonical, first_plane, n_planes, row, col, device=0, stream=No
     if row >= H or col >= W:
         raise RuntimeError(f"{what}: the cell ({row}, {col}) is outside the {H} x {W} board")
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
         if n == 0:
             return np.zeros(0, np.uint8)
         canonical = _stage(canonical, device)
@@ -541,9 +527,7 @@ def _check_buckets(what, sample_arrays, n, buckets, n_buckets, names):
         if names is None:
             raise RuntimeError(f"{what}: with buckets, give n_buckets or names")
         n_buckets = len(names)
-    if isinstance(n_buckets, bool) or not isinstance(n_buckets, (int, np.integer)) or not 1 <= n_buckets <= MAX_BUCKETS:
-        raise RuntimeError(f"{what}: n_buckets must be an integer in [1, {MAX_BUCKETS}], got {n_buckets!r}")
-    n_buckets = int(n_buckets)
+    n_buckets = _args.integer(n_buckets, f"{what}: n_buckets must be an integer in [1, {MAX_BUCKETS}], got {n_buckets!r}", 1, MAX_BUCKETS)
     if names is None:
         names = [str(b) for b in range(n_buckets)]
     if len(names) != n_buckets:
@@ -604,7 +588,7 @@ def eval_metrics(samples, net, cv=1.0, batch_rows=65536, buckets=None, n_buckets
         raise RuntimeError(f"{what}: net must be a HipLeafNet, got {type(net).__name__}")
     B, names = _check_buckets(what, (("canonical", c), ("v", v), ("pi", pi)), n, buckets, n_buckets, names)
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
     if n == 0:
         return _eval_dict(None, 0, cv) if B is None else {"overall": _eval_dict(None, 0, cv)}
     if kind == "numpy":
@@ -649,7 +633,7 @@ def analyze_samples(samples, net, cv=1.0, batch_rows=65536, buckets=None, names=
             if any(not isinstance(x, str) for x in names) or len(set(names)) != len(names):
                 raise RuntimeError(f"{what}: names must be distinct strings, got {names!r}")
     if kind == "numpy":
-        device = _check_device(what, device)
+        device = _args.device_index(device, what)
     if n == 0:
         empty = {k: np.zeros(0, np.float64) for k in ANALYSIS_KEYS} if kind == "numpy" else None
         if empty is None:

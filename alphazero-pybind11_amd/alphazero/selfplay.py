@@ -196,10 +196,11 @@ def process_samples(game, samples, net, seed, **kwargs):
     game has more than one symmetry), then resample_by_surprise with `net` and `seed`; the keywords are resample_by_surprise's.
     -> ((canonical, v, pi) resampled, loss), loss holding one entry per symmetry-expanded sample."""
     from .games import symmetries_batch
-    from .samples import resample_by_surprise, _check_samples, _check_seed
+    from . import _args
+    from .samples import resample_by_surprise, _check_samples
     cls = game if isinstance(game, type) else type(game)
     _check_samples("process_samples", samples, kwargs.get("batch_rows", 65536))      # the named errors, before symmetries_batch's own
-    _check_seed("process_samples", seed)
+    _args.seed64(seed, "process_samples")
     if cls.NUM_SYMMETRIES() > 1 and int(samples[0].shape[0]) > 0:
         samples = symmetries_batch(cls, *samples)
     return resample_by_surprise(samples, net, seed, **kwargs)

@@ -57,7 +57,7 @@ def _batch(az, n=3, gumbel=False):
 
 def test_argument_errors_come_before_any_device_call(capi, monkeypatch):
     import alphazero as az
-    monkeypatch.setattr(az.search_batch, "lib", _Lib())
+    monkeypatch.setattr(az.search_batch_sweep, "lib", _Lib())
     mb = _batch(az)
     with pytest.raises(RuntimeError, match=r"one target per tree \(3\)"):
         mb.search_to([5, 5])
@@ -91,6 +91,6 @@ def test_argument_errors_come_before_any_device_call(capi, monkeypatch):
 
 def test_a_gumbel_batch_is_refused_with_the_reason(capi, monkeypatch):
     import alphazero as az
-    monkeypatch.setattr(az.search_batch, "lib", _Lib())
+    monkeypatch.setattr(az.search_batch_sweep, "lib", _Lib())
     with pytest.raises(RuntimeError, match="Gumbel.*sequential halving plans a fixed budget"):
         _batch(az, gumbel=True).search_to(10)

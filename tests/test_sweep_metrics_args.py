@@ -44,7 +44,7 @@ def test_the_two_symbols_exist_with_the_declared_signatures(capi):
 
 def test_the_names_are_exported_and_the_columns_are_the_issue_s(capi):
     import alphazero as az
-    assert az.policy_divergences is az.search_batch.policy_divergences
+    assert az.policy_divergences is az.search_batch_sweep.policy_divergences
     assert az.POLICY_COLUMNS == ("jsd", "tv", "hellinger", "top1", "top3", "top9")
     assert az.SWEEP_COLUMNS == az.POLICY_COLUMNS + ("reward", "regret", "pressure", "benefit", "entropy", "value_gap", "abs_err",
                                                     "closer_than_anchor", "closer_than_raw")
@@ -67,7 +67,7 @@ def _batch(az, n=3, game=None, device=0, sweep_j=3):
 
 def test_sweep_metrics_argument_errors_come_before_any_device_call(capi, monkeypatch):
     import alphazero as az
-    monkeypatch.setattr(az.search_batch, "lib", _Lib())
+    monkeypatch.setattr(az.search_batch_sweep, "lib", _Lib())
     mb = _batch(az)
     # the state of this batch
     with pytest.raises(RuntimeError, match="sweep_metrics: no search_to call has been made on this batch"):
@@ -137,7 +137,7 @@ def test_negative_indices_count_from_the_end_of_the_reference_set(capi):
 
 def test_policy_divergences_argument_errors_come_before_any_device_call(capi, monkeypatch):
     import alphazero as az
-    monkeypatch.setattr(az.search_batch, "lib", _Lib())
+    monkeypatch.setattr(az.search_batch_sweep, "lib", _Lib())
     p = np.full((4, 7), 1.0 / 7, np.float32)
     with pytest.raises(RuntimeError, match=r"one shape, got \(4, 7\) and \(4, 6\)"):
         az.policy_divergences(p, p[:, :6])
