@@ -16,10 +16,10 @@
 //                       The four engine_* units include no kernel header and their objects carry no device code.
 //   pipeline.hip      the asynchronous tree / net pipeline: the one device module of the three pipe_*_kernels.h and their launch
 //                     functions; pipeline_state.hip, pipeline_run.hip and pipeline_debug.hip are its host code (pipeline_host.h)
-//   search_batch.hip  the batched position search (azmi_search_*): the one device module of the four search_*_kernels.h, every
-//                     launch of them, and the core entry points.  search_batch_sweep.hip, search_batch_pool.hip and
-//                     search_batch_frontier.hip hold the entry points of those three families; host code only, they launch
-//                     through search_batch.hip (search_batch_host.h)
+//   search_batch.hip  the batched position search (azmi_search_*): the one device module of the four search_*_kernels.h and every
+//                     launch of them.  search_batch_create.hip, search_batch_steps.hip and search_batch_moves.hip hold the core
+//                     entry points, search_batch_sweep.hip, search_batch_pool.hip and search_batch_frontier.hip those of their
+//                     three families; host code only, they launch through search_batch.hip (search_batch_host.h)
 //   samples.hip       per-row losses, resample plan and metrics (azmi_sample_*, azmi_resample_*); DevBlock only
 // DevTemps are the device buffers of one call, DevBlock one that is kept between calls and grown.
 #pragma once

@@ -141,12 +141,8 @@ __global__ void k_mcts_process_result_batched(EngineParams ep, EngineArrays ar, 
   c.store(kSlotWaitEval);
 }
 
-enum MctsQuery : uint32_t {
-  kQCounts = 0, kQProbs = 1, kQProbsPruned = 2, kQRootValue = 3, kQRootQ = 4, kQScalars = 5, kQGumbelPolicy = 6,
-  kQGumbelFinal = 7, kQAddRootNoise = 8, kQApplyRootTemp = 9, kQPickMove = 10, kQPrincipalVariation = 11, kQSetGumbelSims = 12, kQRootChildren = 13
-};
-
-// every read-out / small mutation of the root: dense [M] vectors go to out_f / out_u (lane m writes entry m).
+// every read-out / small mutation of the root (`kind`: enum MctsQuery, search_batch_types.h): dense [M] vectors go to out_f / out_u
+// (lane m writes entry m).
 // mcts_query_slot: the read-out of ONE slot's seat-0 tree by its lane group (the object: slot 0; the batched search: every slot)
 template <class GM>
 __device__ __forceinline__ void mcts_query_slot(const EngineParams& ep, const EngineArrays& ar, uint32_t slot, uint32_t lane, uint32_t kind,

@@ -1,11 +1,18 @@
 // Host-side state of one batched position search and what the translation units behind azmi_search_* share:
 //   search_batch.hip           the one device module of the four search_*_kernels.h (a kernel's code depends on its module-mates
 //                              and on the order they are instantiated in, DESIGN.md sections 1 and 8.3): every launch function
-//                              below, the step and search helpers, the core entry points
+//                              below and nothing else
+//   search_batch_create.hip    azmi_search_create / destroy / set_leaves_per_step / set_descents_per_step / host_reads / reset /
+//                              set_rollout_seeds
+//   search_batch_steps.hip     the sb_begin_* / sb_check_* checks, sb_search_args, sb_enqueue_step / search; azmi_search_find_leaves /
+//                              leaves_to_host / process_results* / run*
+//   search_batch_moves.hip     azmi_search_pick_moves / update_roots / root_prior / play*, game_state / query / sync / stats
 //   search_batch_sweep.hip     azmi_search_run_to / checkpoints / sweep_metrics, azmi_policy_divergences
 //   search_batch_pool.hip      azmi_search_set_capture / capture_roots / captured / net_metrics, azmi_pool_unique
 //   search_batch_frontier.hip  azmi_search_expand / frontier
-// The last three are host code only: no kernel header, no launch of their own.
+// All but the first are host code only: no kernel header, no launch of their own, no device code in their objects.
+// The engine behind a search is a PlayManager engine with N slots built from the MCTS constructor's arguments (azmi_host_mcts_params,
+// as azmi_mcts_create does for its one slot); the engine's own game loop never runs on it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,7 +88,7 @@ struct azmi_search {
   uint32_t sm_cap = 0;                // checkpoints the block has room for
 };
 
-// ---- defined in search_batch.hip -----------------------------------------------------------------------------------------------------
+// ---- defined in search_batch_steps.hip -----------------------------------------------------------------------------------------------
 // the checks an entry point starts with: the trees have positions (begin_step); a NULL handle on a machine without a device
 // repeats the no-device failure of its create (begin_read); no find_leaves step is pending (begin_move: the calls that change the trees)
 int sb_begin_step(azmi_search* s, const char* what);
@@ -104,12 +111,13 @@ int sb_search_args(azmi_search* s, const char* what, int eval_type, azmi_net* ne
 int sb_enqueue_step(azmi_search* s, const SbSearchArgs& a, uint32_t kk, uint32_t rn, hipStream_t st);
 int sb_enqueue_search(azmi_search* s, const SbSearchArgs& a, uint32_t visits, uint32_t rn, hipStream_t st);
 
+// ---- defined in search_batch.hip -----------------------------------------------------------------------------------------------------
 // One launch function per kernel family, on `st`, each counted in s->launches; arguments as the kernels take them.
 void sb_launch_find(azmi_search* s, const azmi::EngineParams& ep, const azmi::EngineArrays& ar, uint32_t eval_random, hipStream_t st);
 void sb_launch_process(azmi_search* s, const azmi::EngineParams& ep, const azmi::EngineArrays& ar, uint32_t root_noise, const float* v_rows,
                        const float* pi_rows, hipStream_t st);
 void sb_launch_query(azmi_search* s, uint32_t kind, float temp, uint32_t arg, hipStream_t st);
-void sb_launch_query_scalars(azmi_search* s, hipStream_t st);      // kind kQScalars (the kinds are named in mcts_object_kernels.h)
+void sb_launch_query_scalars(azmi_search* s, hipStream_t st);      // kind kQScalars (enum MctsQuery, search_batch_types.h)
 void sb_launch_cache_insert(azmi_search* s, const azmi::EngineParams& ep, const azmi::EngineArrays& ar, uint32_t total, hipStream_t st);
 void sb_launch_find_wu(azmi_search* s, const azmi::EngineParams& ep, const azmi::EngineArrays& ar, uint32_t kk, uint32_t eval_random, uint32_t root_noise,
                        hipStream_t st);
@@ -118,6 +126,10 @@ void sb_launch_process_wu(azmi_search* s, const azmi::EngineParams& ep, const az
 void sb_launch_pick(azmi_search* s, float temp, hipStream_t st);
 void sb_launch_update_root(azmi_search* s, const int32_t* moves, hipStream_t st);
 void sb_launch_root_prior(azmi_search* s, uint32_t apply_temp, uint32_t noise, hipStream_t st);
+// reset: every tree's position from the uploaded start rows and game records; the step API: the step's kk * N (K > 1) or N rows into one batch
+void sb_launch_seed(azmi_search* s, const uint8_t* d_init, uint32_t init_stride, const int32_t* d_moves, const uint32_t* d_offs, const uint64_t* d_seeds,
+                    hipStream_t st);
+void sb_launch_gather(azmi_search* s, uint32_t kk, hipStream_t st);
 // EvalType::PLAYOUT steps
 void sb_launch_step_playout(azmi_search* s, const azmi::EngineParams& ep, const azmi::EngineArrays& ar, uint32_t root_noise, hipStream_t st);
 void sb_launch_step_playout_wu(azmi_search* s, const azmi::EngineParams& ep, const azmi::EngineArrays& ar, uint32_t kk, uint32_t root_noise, hipStream_t st);

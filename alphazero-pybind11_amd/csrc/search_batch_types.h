@@ -20,6 +20,12 @@ struct WuArrays {
   uint32_t* ifl_cur;    // [ifl_cap] InFlightLeaf::leaf
 };
 
+// the read-out kinds of azmi_mcts_query / azmi_search_query (mcts_object_kernels.h's too; here so that host-only units can name them)
+enum MctsQuery : uint32_t {
+  kQCounts = 0, kQProbs = 1, kQProbsPruned = 2, kQRootValue = 3, kQRootQ = 4, kQScalars = 5, kQGumbelPolicy = 6,
+  kQGumbelFinal = 7, kQAddRootNoise = 8, kQApplyRootTemp = 9, kQPickMove = 10, kQPrincipalVariation = 11, kQSetGumbelSims = 12, kQRootChildren = 13
+};
+
 // ---- search_batch_kernels.h ------------------------------------------------------------------------------------------------------
 enum SbPend : uint8_t {
   kPendNone = 0,    // nothing to back up: terminal leaf (backed up by the find kernel), or a stopped tree

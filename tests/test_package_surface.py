@@ -45,7 +45,7 @@ def test_importing_the_package_does_not_import_torch(az):
 
 
 def test_query_kinds_are_the_device_enum(az):
-    header = open(os.path.join(PKG, "csrc", "mcts_object_kernels.h")).read()
+    header = open(os.path.join(PKG, "csrc", "search_batch_types.h")).read()
     body = re.search(r"enum\s+MctsQuery\b[^{]*\{(.*?)\}", header, re.S).group(1)
     device = {re.sub(r"(?<!^)(?=[A-Z])", "_", name).upper(): int(value) for name, value in re.findall(r"\bkQ(\w+)\s*=\s*(\d+)", body)}
     assert len(device) == 14 and device["COUNTS"] == 0 and device["ROOT_CHILDREN"] == 13, device
