@@ -159,6 +159,8 @@ SYMBOLS = {
     "azmi_pm_update_inferences": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP]),
     "azmi_net_blob_bytes": (C.c_size_t, None),
     "azmi_net_create": (C.c_int, None),
+    "azmi_net_blob_bytes2": (C.c_size_t, None),
+    "azmi_net_create2": (C.c_int, None),
     "azmi_net_destroy": (None, None),
     "azmi_net_forward": (C.c_int, None),
     "azmi_net_last_error": (C.c_char_p, None),

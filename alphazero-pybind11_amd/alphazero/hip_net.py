@@ -24,6 +24,24 @@ class NetDescC(C.Structure):
                                          "pi_head_convs", "v_fc_layers", "policy_channels", "precision", "pi_hidden")]
 
 
+class NetDesc2C(C.Structure):
+    """azmi_net_desc2 (include/azmi.h): the first descriptor, then what came later.  Reads of the first one's fields pass through."""
+    _fields_ = [("base", NetDescC), ("dense_net", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+    def __getattr__(self, name):
+        return getattr(self.base, name)
+
+
+def blob_bytes(desc):
+    """azmi_net_blob_bytes / azmi_net_blob_bytes2 of a descriptor of either kind."""
+    fn = lib.azmi_net_blob_bytes2 if isinstance(desc, NetDesc2C) else lib.azmi_net_blob_bytes
+    return fn(C.byref(desc))
+
+
+lib.azmi_net_blob_bytes2.restype = C.c_size_t
+lib.azmi_net_blob_bytes2.argtypes = [C.POINTER(NetDesc2C)]
+lib.azmi_net_create2.restype = C.c_int
+lib.azmi_net_create2.argtypes = [C.POINTER(NetDesc2C), C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
 lib.azmi_net_blob_bytes.restype = C.c_size_t
 lib.azmi_net_blob_bytes.argtypes = [C.POINTER(NetDescC)]
 lib.azmi_net_create.restype = C.c_int
@@ -166,11 +184,15 @@ def fold_spatial(net, x3=False):
 
 
 def fold_fp32(net):
-    """fp32 path (csrc/leafnet_f32.hip): torch layouts, BatchNorms folded in double, no bf16 anywhere."""
+    """fp32 path (csrc/leafnet_f32.hip): torch layouts, BatchNorms folded in double, no bf16 anywhere.  A ResNet trunk (3x3 only, as
+    before) gets the first descriptor and azmi_net_create; a dense trunk (kernel sizes 1 / 3 / 5 / 7, its extra head convolutions
+    included) the second one (NetDesc2C) and azmi_net_create2."""
     spec = net.spec
     Cin, H, W = spec.in_shape
-    if not (spec.kernel_size == 3 and spec.head_pool):
-        raise RuntimeError("fp32 leaf net: 3x3 convolutions and pooled value / global-action heads only")
+    if not ((spec.kernel_size == 3 or spec.dense_net) and spec.head_pool):
+        raise RuntimeError("fp32 leaf net: 3x3 convolutions (dense trunks: 1, 3, 5 or 7) and pooled value / global-action heads only")
+    if spec.dense_net and spec.depth < 1:
+        raise RuntimeError("fp32 leaf net: a dense trunk needs at least one block")
     sd = {k: v.detach().double().cpu() for k, v in net.state_dict().items()}
     blob = bytearray()
 
@@ -178,8 +200,9 @@ def fold_fp32(net):
         a, b = (t.cpu() for t in bn_affine(bn))
         return _f32(sd[wname] * a[:, None, None, None]) + _f32(b)
 
-    blob += conv_bn("conv1.weight", net.bn1)
-    for i, blk in enumerate(net.conv_layers):
+    if not spec.dense_net:
+        blob += conv_bn("conv1.weight", net.bn1)
+    for i, blk in enumerate(net.conv_layers):   # both kinds of block: bn1's affine as it is, bn2 folded into conv1, conv2 raw
         a1, b1 = (t.cpu() for t in bn_affine(blk.bn1))
         blob += _f32(a1) + _f32(b1) + conv_bn(f"conv_layers.{i}.conv1.weight", blk.bn2) + _f32(sd[f"conv_layers.{i}.conv2.weight"])
     blob += conv_bn("v_conv.weight", net.v_bn)
@@ -201,10 +224,71 @@ def fold_fp32(net):
                 blob += _f32(sd[k])
     else:
         blob += _f32(sd["pi_fc1.weight"]) + _f32(sd["pi_fc1.bias"])
-    desc = NetDescC(Cin, H, W, spec.num_channels, spec.depth, 3, spec.head_channels, spec.v_fc_hidden, spec.num_moves, spec.num_players,
-                    spec.v_head_convs, spec.pi_head_convs, spec.v_fc_layers, pc, 1,
+    desc = NetDescC(Cin, H, W, spec.num_channels, spec.depth, spec.kernel_size, spec.head_channels, spec.v_fc_hidden, spec.num_moves,
+                    spec.num_players, spec.v_head_convs, spec.pi_head_convs, spec.v_fc_layers, pc, 1,
                     spec.pi_fc_hidden if (pc and spec.num_moves > pc * H * W) else 0)
-    assert len(blob) == lib.azmi_net_blob_bytes(C.byref(desc)), (len(blob), lib.azmi_net_blob_bytes(C.byref(desc)))
+    if spec.dense_net:
+        desc = NetDesc2C(desc, 1)
+    assert len(blob) == blob_bytes(desc), (len(blob), blob_bytes(desc))
+    return desc, bytes(blob)
+
+
+def _up(x, m):
+    return (x + m - 1) // m * m
+
+
+def fold_dense(net):
+    """The dense Connect4 family on the matrix cores (csrc/leafnet_dense.h; bf16 operands): 6x7, flat policy head, kernel_size 3 or
+    5, growth G <= 16, C_in + G*depth <= 128, head_channels 32.  Narrower widths are zero-padded: the padded channels have zero
+    scale, bias and weights and stay exactly 0.  Image (`frag` = hip_net._frags: [k-step][m-tile][64 lanes][8 bf16]; CF = C_in +
+    G*depth, CFP = CF rounded up to 32, C_i = C_in + G*i):
+      block i  a1[CFP] b1[CFP] (bn1 of the block over the raw features, zero behind C_i) c1[64] (bn2's bias) f32 |
+               W1 frag[roundup32(C_i)/32][ceil(4G/16)] (rows = bn2-scaled conv1, k = input channel) |
+               W2: per tap (dy, dx) row-major frag[ceil(4G/32)][1] (rows = the G outputs, rows >= G zero; k = bottleneck channel)
+      heads    bh[64] f32 | Wh frag[CFP/32][4] (rows 0-31 = v_conv * v_bn, rows 32-63 = pi_conv * pi_bn)
+      v_fc1 W[Hd][32] b[Hd] | v_fc2 W[P+1][Hd] b[P+1] | pi_fc1 W[M][32*42] b[M]   (f32, torch layouts)"""
+    spec = net.spec
+    Cin, H, W = spec.in_shape
+    G, D, K = spec.num_channels, spec.depth, spec.kernel_size
+    tail = "; use precision='fp32' for other shapes"
+    # the bounds of azmi_net_create2 (csrc/leafnet.hip dense_refusal), with its messages
+    if spec.policy_shape is not None or (H, W) != (6, 7):
+        raise RuntimeError("dense leaf net kernel covers the 6x7 board with the flat policy head" + tail)
+    if K not in (3, 5):
+        raise RuntimeError("dense leaf net kernel: kernel_size 3 or 5" + tail)
+    if not 1 <= G <= 16:
+        raise RuntimeError("dense leaf net kernel: growth rate (channels) 1..16" + tail)
+    if D < 1 or Cin < 1:
+        raise RuntimeError("dense leaf net kernel: at least one block and one input plane" + tail)
+    if Cin + G * D > 128:
+        raise RuntimeError("dense leaf net kernel: in_channels + channels * depth <= 128" + tail)
+    if not (spec.head_channels == 32 and spec.head_pool and spec.v_head_convs == 0 and spec.pi_head_convs == 0 and spec.v_fc_layers == 1):
+        raise RuntimeError("dense leaf net kernel: 32 head channels, pooled value head, no extra head convolutions, one value FC layer" + tail)
+    if not (16 <= spec.v_fc_hidden <= 256 and spec.v_fc_hidden % 16 == 0 and 1 <= spec.num_players <= 3 and 1 <= spec.num_moves <= 16):
+        raise RuntimeError("dense leaf net kernel: head sizes out of range (v_hidden: a multiple of 16, at most 256; 1..3 players; "
+                           "1..16 moves)" + tail)
+    sd = {k: v.detach().double().cpu() for k, v in net.state_dict().items()}
+    CF = Cin + G * D
+    CFP, M1, K2 = _up(CF, 32), _up(4 * G, 16), _up(4 * G, 32)
+    blob = bytearray()
+    for i, blk in enumerate(net.conv_layers):
+        Ci = Cin + G * i
+        a1, b1 = (t.cpu() for t in bn_affine(blk.bn1))
+        a2, b2 = (t.cpu() for t in bn_affine(blk.bn2))
+        blob += _f32(_pad(a1, CFP)) + _f32(_pad(b1, CFP)) + _f32(_pad(b2, 64))
+        blob += _frags(_pad(sd[f"conv_layers.{i}.conv1.weight"][:, :, 0, 0] * a2[:, None], M1, _up(Ci, 32)).numpy())
+        w2 = sd[f"conv_layers.{i}.conv2.weight"]                     # [G][4G][K][K]
+        for dy in range(K):
+            for dx in range(K):
+                blob += _frags(_pad(w2[:, :, dy, dx], 16, K2).numpy())
+    av, bv = (t.cpu() for t in bn_affine(net.v_bn))
+    ap, bp = (t.cpu() for t in bn_affine(net.pi_bn))
+    wh = torch.cat([sd["v_conv.weight"][:, :, 0, 0] * av[:, None], sd["pi_conv.weight"][:, :, 0, 0] * ap[:, None]], 0)
+    blob += _f32(torch.cat([bv, bp])) + _frags(_pad(wh, 64, CFP).numpy())
+    blob += _f32(sd["v_fc1.weight"]) + _f32(sd["v_fc1.bias"]) + _f32(sd["v_fc2.weight"]) + _f32(sd["v_fc2.bias"])
+    blob += _f32(sd["pi_fc1.weight"]) + _f32(sd["pi_fc1.bias"])
+    desc = NetDesc2C(NetDescC(Cin, H, W, G, D, K, 32, spec.v_fc_hidden, spec.num_moves, spec.num_players, 0, 0, 1, 0, 0, 0), 1)
+    assert len(blob) == blob_bytes(desc), (len(blob), blob_bytes(desc))
     return desc, bytes(blob)
 
 
@@ -225,15 +309,20 @@ def _split_frags(wmat, passes=("hi", "hi", "lo")):
 
 
 def fold(net, precision="bf16"):
-    """LeafNet (reference NNArch parameter names) -> (NetDescC, blob bytes).  precision: "bf16" (bf16 MFMA operands), "bf16x3"
-    (weights and activations as bf16 high + low parts, three MFMAs per product - the 1e-5 tier on the matrix cores; the Connect4
-    family and, since round 4, the spatial-head nets) or "fp32" (plain fp32 kernels, any shape)."""
+    """LeafNet (reference NNArch parameter names) -> (NetDescC or NetDesc2C, blob bytes).  precision: "bf16" (bf16 MFMA operands),
+    "bf16x3" (weights and activations as bf16 high + low parts, three MFMAs per product - the 1e-5 tier on the matrix cores; the
+    Connect4 family and, since round 4, the spatial-head nets) or "fp32" (plain fp32 kernels, any shape).  A dense trunk
+    (spec.dense_net) has the "bf16" tile of fold_dense and "fp32"."""
     if precision == "fp32":
         return fold_fp32(net)
     spec = net.spec
     x3 = precision == "bf16x3"
     if precision not in ("bf16", "bf16x3"):
         raise ValueError("precision must be 'bf16', 'bf16x3' or 'fp32'")
+    if spec.dense_net:
+        if x3:
+            raise RuntimeError("dense leaf net: no bf16x3 tier; the 1e-5 tier of dense nets is precision='fp32'")
+        return fold_dense(net)
     if spec.policy_shape is not None:
         return fold_spatial(net, x3)
     Cin, H, W = spec.in_shape
@@ -296,7 +385,8 @@ class HipLeafNet:
         self.desc, blob = fold(net, precision)
         self._blob = blob
         h = C.c_void_p()
-        rc = lib.azmi_net_create(C.byref(self.desc), blob, len(blob), int(device), C.byref(h))
+        create = lib.azmi_net_create2 if isinstance(self.desc, NetDesc2C) else lib.azmi_net_create    # dense trunk
+        rc = create(C.byref(self.desc), blob, len(blob), int(device), C.byref(h))
         if rc != 0:
             raise RuntimeError(lib.azmi_net_last_error().decode())
         self._h = h

@@ -1,7 +1,7 @@
 """Leaf-evaluation network: plumbing around the reference's `NNArch` weights.
 
-* `NetSpec` / `LeafNet` restate the inference forward of the reference's ResNet-mode
-  `NNArch` (/root/reference/src/neural_net.py:233-263 ResidualBlock, :266-510 NNArch) with
+* `NetSpec` / `LeafNet` restate the inference forward of the reference's `NNArch`
+  (/root/reference/src/neural_net.py:211-230 DenseBlock, :233-263 ResidualBlock, :266-510 NNArch) with
   IDENTICAL parameter names, so a reference checkpoint's `state_dict` loads unchanged and a
   random-init net of the same architecture can be built without the reference tree.
 * `process()` mirrors `NNWrapper.process` (neural_net.py:800-823): eval mode, optional bf16
@@ -9,8 +9,11 @@
 * `fold()` folds inference BatchNorms into the convolutions and lays the weights out for the
   hand-written MFMA kernels in csrc/ (see DESIGN.md §Leaf net).
 
-Only the ResNet trunk (`dense_net=False`, `trunk_norm="batch"`, `trunk_act="relu"`) with the value
-head and the flat / spatial policy heads is covered: that is what BASELINE.json's configs use.
+Covered: both trunks - the ResNet one (`dense_net=False`, what BASELINE.json's configs use) and the DenseNet one
+(`dense_net=True`, the reference's `TrainConfig` default: no stem, `conv_layers.{i}` = DenseBlock with bn_size 4) - with
+`trunk_norm="batch"`, `trunk_act="relu"`, any odd `kernel_size` in 1..7 (the HIP tiers: 3, and 1 / 5 / 7 on dense trunks), the value head and the flat / spatial policy heads.
+NOT covered (a spec cannot say them): `trunk_norm="layer"`, `trunk_act="crelu"`, `pi_fc_layers > 0`; `head_pool=False` builds
+in torch but no HIP tier takes it.
 """
 from dataclasses import dataclass
 
@@ -34,8 +37,11 @@ class NetSpec:
     v_fc_layers: int = 1
     policy_shape: tuple = None  # POLICY_SHAPE (C, H, W) -> spatial head (neural_net.py:390-427)
     pi_fc_hidden: int = -1   # -1 -> head_channels * 8; hidden width of pi_global (spatial head with global actions)
+    dense_net: bool = False  # NNArgs.dense_net: DenseNet trunk, num_channels = the growth rate (neural_net.py:302-338)
 
     def __post_init__(self):
+        if self.kernel_size not in (1, 3, 5, 7):
+            raise ValueError("kernel_size must be an odd value in 1..7")
         if self.v_fc_hidden == -1:
             self.v_fc_hidden = self.head_channels * 8
         if self.pi_fc_hidden == -1:
@@ -62,17 +68,38 @@ class ResidualBlock(nn.Module):  # neural_net.py:233-263 (no downsample)
         return out + x
 
 
+class DenseBlock(nn.Module):  # neural_net.py:211-230
+    def __init__(self, cin, growth, bn_size=4, k=3):
+        super().__init__()
+        self.bn1 = nn.BatchNorm2d(cin)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.conv1 = _conv(cin, growth * bn_size, 1)
+        self.bn2 = nn.BatchNorm2d(growth * bn_size)
+        self.relu2 = nn.ReLU(inplace=True)
+        self.conv2 = _conv(growth * bn_size, growth, k)
+
+    def forward(self, x):
+        out = self.conv1(self.relu1(self.bn1(x)))
+        out = self.conv2(self.relu2(self.bn2(out)))
+        return torch.cat([x, out], 1)
+
+
 class LeafNet(nn.Module):
     def __init__(self, spec: NetSpec):
         super().__init__()
         self.spec = spec
         C, H, W = spec.in_shape
         ch, HC, k = spec.num_channels, spec.head_channels, spec.kernel_size
-        self.conv1 = _conv(C, ch, k)
-        self.bn1 = nn.BatchNorm2d(ch)
-        self.conv_layers = nn.Sequential(*[ResidualBlock(ch, k) for _ in range(spec.depth)])
-        self.v_conv = _conv(ch, HC, 1)
-        self.pi_conv = _conv(ch, HC, 1)
+        if spec.dense_net:   # no stem (neural_net.py:302-306); the heads read every feature (:332-335)
+            self.conv_layers = nn.Sequential(*[DenseBlock(C + ch * i, ch, 4, k) for i in range(spec.depth)])
+            trunk_out = C + ch * spec.depth
+        else:
+            self.conv1 = _conv(C, ch, k)
+            self.bn1 = nn.BatchNorm2d(ch)
+            self.conv_layers = nn.Sequential(*[ResidualBlock(ch, k) for _ in range(spec.depth)])
+            trunk_out = ch
+        self.v_conv = _conv(trunk_out, HC, 1)
+        self.pi_conv = _conv(trunk_out, HC, 1)
         self.v_bn = nn.BatchNorm2d(HC)
         self.v_relu = nn.ReLU(inplace=True)
         if spec.v_head_convs > 0:
@@ -113,7 +140,8 @@ class LeafNet(nn.Module):
             self.pi_fc1 = nn.Linear(H * W * HC, spec.num_moves)
 
     def forward(self, s):  # neural_net.py:448-510 — returns LOG-probabilities like the reference
-        s = self.bn1(self.conv1(s))
+        if not self.spec.dense_net:
+            s = self.bn1(self.conv1(s))
         s = self.conv_layers(s)
         v = self.v_relu(self.v_bn(self.v_conv(s)))
         if hasattr(self, "v_extra_convs"):
@@ -153,6 +181,19 @@ def connect4_spec(depth=6, channels=64, kernel_size=3, head_channels=32):
     """BASELINE config 2: Connect4, 6 blocks x 64 channels, k=3, flat policy head."""
     return NetSpec(in_shape=(4, 6, 7), num_moves=7, num_players=2, num_channels=channels, depth=depth,
                    kernel_size=kernel_size, head_channels=head_channels)
+
+
+def connect4_dense_spec(depth=4, channels=12, kernel_size=5, head_channels=32):
+    """The reference's TrainConfig defaults (config.py:44-60; Connect4 has no YAML): DenseNet trunk, growth 12, 4 blocks, k=5."""
+    return NetSpec(in_shape=(4, 6, 7), num_moves=7, num_players=2, num_channels=channels, depth=depth,
+                   kernel_size=kernel_size, head_channels=head_channels, dense_net=True)
+
+
+def stargambit_dense_spec(depth=4, channels=16, kernel_size=3, head_channels=32):
+    """configs/star_gambit_skirmish.yaml and its single-variant siblings: they set kernel_size 3 and inherit the dense default;
+    spatial head over the 13 x 13 canvas + 19 global actions."""
+    return NetSpec(in_shape=(36, 13, 13), num_moves=1709, num_players=2, num_channels=channels, depth=depth,
+                   kernel_size=kernel_size, head_channels=head_channels, policy_shape=(10, 13, 13), dense_net=True)
 
 
 def tawlbwrdd_spec(depth=4):

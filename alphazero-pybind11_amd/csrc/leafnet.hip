@@ -16,6 +16,9 @@
 // into an LDS ring by DMA; the residual stream stays in fp32 MFMA accumulators):
 //   * leafnet_c4.h - the Connect4-family net (flat policy head), also launched fused with the engine's move step;
 //   * leafnet_sp.h - the spatial-policy-head nets (Tafl family, StarGambit).
+// and a third for the reference's DEFAULT trunk (dense_net, azmi_net_create2):
+//   * leafnet_dense.h - the dense Connect4 family (6x7, 3x3 / 5x5, flat policy head): one wavefront per board, every raw
+//     feature in LDS.
 // This file is the host side behind azmi_net_* (include/azmi.h): validation of the descriptor, the weight image on the
 // device, launches.  The fp32 correctness path lives in leafnet_f32.hip.
 #include <hip/hip_runtime.h>
@@ -33,6 +36,7 @@
 #include "leafnet_f32.h"
 #include "leafnet_c4.h"
 #include "leafnet_sp.h"
+#include "leafnet_dense.h"
 
 namespace {
 
@@ -54,6 +58,9 @@ struct azmi_net {
   void* f32_last_stream = nullptr;
   bool f32_last_stream_set = false;
   bool spatial = false;      // spatial policy head (Tafl family, StarGambit): sp::k_leafnet_sp
+  bool dense = false;        // DenseNet trunk on the matrix cores (dense Connect4 family): dn::k_leafnet_dense
+  dn::DnDesc dd{};
+  dn::DnPtrs dp{};
   sp::SpDesc sd{};
   sp::SpPtrs sp{};
   uint32_t sp_tbw = 0;       // boards per workgroup of the instantiated tile
@@ -109,6 +116,46 @@ __global__ void k_scatter_rows(const float* __restrict__ v_c, const float* __res
   for (uint32_t e = threadIdx.x; e < m; e += blockDim.x) pi[static_cast<size_t>(r) * m + e] = pi_c[static_cast<size_t>(i) * m + e];
 }
 bool is_spatial(const azmi_net_desc* d) { return d->policy_channels > 0; }
+dn::DnDesc dense_desc(const azmi_net_desc* d) {
+  const int cf = d->in_channels + d->channels * d->depth;
+  return dn::DnDesc{d->in_channels, d->channels, d->depth, d->kernel_size, cf, dn::round_up(cf, 32), d->num_moves, d->num_players, d->v_hidden};
+}
+// The bounds of the dense tile (leafnet_dense.h), stated once: NULL when `d` is inside them, else what is outside
+const char* dense_refusal(const azmi_net_desc* d) {
+  if (d->policy_channels != 0 || d->height != dn::BH || d->width != dn::BW)
+    return "dense leaf net kernel covers the 6x7 board with the flat policy head; use precision='fp32' for other shapes";
+  if (d->kernel_size != 3 && d->kernel_size != 5) return "dense leaf net kernel: kernel_size 3 or 5; use precision='fp32' for other shapes";
+  if (d->channels < 1 || d->channels > dn::MAX_G) return "dense leaf net kernel: growth rate (channels) 1..16; use precision='fp32' for other shapes";
+  if (d->depth < 1 || d->in_channels < 1) return "dense leaf net kernel: at least one block and one input plane; use precision='fp32' for other shapes";
+  if (static_cast<long long>(d->in_channels) + static_cast<long long>(d->channels) * d->depth > dn::MAX_CF)
+    return "dense leaf net kernel: in_channels + channels * depth <= 128; use precision='fp32' for other shapes";
+  if (d->head_channels != dn::HC1 || d->v_head_convs != 0 || d->pi_head_convs != 0 || d->v_fc_layers != 1)
+    return "dense leaf net kernel: 32 head channels, no extra head convolutions, one value FC layer; use precision='fp32' for other shapes";
+  if (d->v_hidden < 16 || d->v_hidden > 256 || d->v_hidden % 16 || d->num_players < 1 || d->num_players > 3 || d->num_moves < 1 || d->num_moves > 16)
+    return "dense leaf net kernel: head sizes out of range (v_hidden: a multiple of 16, at most 256; 1..3 players; 1..16 moves); use precision='fp32' for other shapes";
+  return nullptr;
+}
+size_t dense_blob_bytes(const azmi_net_desc* d) {
+  const dn::DnDesc dd = dense_desc(d);
+  size_t n = 0;
+  for (int i = 0; i < dd.depth; ++i) n += dn::block_bytes(dd, i);
+  n += dn::HEADCH * 4 + static_cast<size_t>(dd.CFP / 32) * 4 * WFRAG_BYTES;
+  n += (static_cast<size_t>(dd.v_hidden) * dn::HC1 + dd.v_hidden) * 4;
+  n += (static_cast<size_t>(dd.num_players + 1) * dd.v_hidden + dd.num_players + 1) * 4;
+  n += (static_cast<size_t>(dd.num_moves) * dn::HC1 * dn::PIX + dd.num_moves) * 4;
+  return n;
+}
+bool reserved_zero(const azmi_net_desc2* d) {
+  for (int32_t r : d->reserved) if (r != 0) return false;
+  return true;
+}
+// what a batch row is made of, whichever implementation stands behind the net
+void net_dims(const azmi_net* net, uint32_t* chw, uint32_t* p1, uint32_t* m) {
+  if (net->f32) azmi_f32::dims(net->f32, chw, p1, m);
+  else if (net->spatial) { *chw = net->sd.C_in * net->sd.H * net->sd.W; *p1 = net->sd.num_players + 1; *m = net->sd.num_moves; }
+  else if (net->dense) { *chw = net->dd.C_in * dn::PIX; *p1 = net->dd.num_players + 1; *m = net->dd.num_moves; }
+  else { *chw = net->nd.C_in * net->nd.H * net->nd.W; *p1 = net->nd.num_players + 1; *m = net->nd.num_moves; }
+}
 // weight image of a spatial net (alphazero/hip_net.py fold_spatial): the chunk stream | the fp32 parameters of the tower and
 // the heads | the value FC stack | pi_global
 size_t spatial_blob_bytes(const azmi_net_desc* d) {
@@ -130,7 +177,7 @@ const char* azmi_net_last_error(void) { return g_net_err.c_str(); }
 
 size_t azmi_net_blob_bytes(const azmi_net_desc* d) {
   if (!d) return 0;
-  if (d->precision == 1) return azmi_f32::blob_bytes(d);
+  if (d->precision == 1) return azmi_f32::blob_bytes(d, false);
   if (is_spatial(d)) return spatial_blob_bytes(d);
   // precision 2 (bf16x3): the stem's fragments twice (high, low parts), three chunks per tap and for the head 1x1 (leafnet_c4.h, SPLIT)
   const size_t x3 = d->precision == 2 ? 3 : 1;
@@ -144,18 +191,20 @@ size_t azmi_net_blob_bytes(const azmi_net_desc* d) {
   return n;
 }
 
+static int f32_create(const azmi_net_desc* d, bool dense, const void* blob, size_t blob_bytes, int device, azmi_net** out) {
+  const char* msg = "";
+  void* impl = nullptr;
+  const int rc = azmi_f32::create(d, dense, blob, blob_bytes, device, &impl, &msg);
+  if (rc != AZMI_OK) return nfail(rc, "%s", msg);
+  auto net = new azmi_net();
+  net->device = device; net->f32 = impl;
+  *out = net;
+  return AZMI_OK;
+}
+
 int azmi_net_create(const azmi_net_desc* d, const void* blob, size_t blob_bytes, int device, azmi_net** out) {
   if (!d || !blob || !out) return nfail(AZMI_ERR_INVALID, "null argument");
-  if (d->precision == 1) {
-    const char* msg = "";
-    void* impl = nullptr;
-    const int rc = azmi_f32::create(d, blob, blob_bytes, device, &impl, &msg);
-    if (rc != AZMI_OK) return nfail(rc, "%s", msg);
-    auto net = new azmi_net();
-    net->device = device; net->f32 = impl;
-    *out = net;
-    return AZMI_OK;
-  }
+  if (d->precision == 1) return f32_create(d, false, blob, blob_bytes, device, out);   // (a ResNet trunk: 3x3 only, azmi_f32::create)
   if (d->precision != 0 && d->precision != 2) return nfail(AZMI_ERR_INVALID, "precision must be 0 (bf16 MFMA), 1 (fp32) or 2 (bf16x3: split bf16 MFMA)");
   if (is_spatial(d)) {
     if (d->channels != CH || d->head_channels != sp::HCS || d->kernel_size != 3 || d->v_head_convs != 1 || d->pi_head_convs != 1)
@@ -270,6 +319,55 @@ int azmi_net_create(const azmi_net_desc* d, const void* blob, size_t blob_bytes,
   return AZMI_OK;
 }
 
+size_t azmi_net_blob_bytes2(const azmi_net_desc2* d) {
+  if (!d || !reserved_zero(d)) return 0;
+  if (!d->dense_net) return azmi_net_blob_bytes(&d->base);
+  if (d->base.precision == 1) return azmi_f32::blob_bytes(&d->base, true);
+  return d->base.precision == 0 && !dense_refusal(&d->base) ? dense_blob_bytes(&d->base) : 0;
+}
+
+int azmi_net_create2(const azmi_net_desc2* d2, const void* blob, size_t blob_bytes, int device, azmi_net** out) {
+  if (!d2 || !blob || !out) return nfail(AZMI_ERR_INVALID, "null argument");
+  if (!reserved_zero(d2)) return nfail(AZMI_ERR_INVALID, "azmi_net_desc2: reserved words must be zero");
+  if (d2->dense_net != 0 && d2->dense_net != 1) return nfail(AZMI_ERR_INVALID, "azmi_net_desc2: dense_net must be 0 or 1");
+  const azmi_net_desc* d = &d2->base;
+  if (!d2->dense_net) return azmi_net_create(d, blob, blob_bytes, device, out);      // the old entry, with everything it refuses
+  if (d->precision == 1) return f32_create(d, true, blob, blob_bytes, device, out);
+  if (d->precision == 2) return nfail(AZMI_ERR_INVALID, "dense leaf net: no bf16x3 tier; the 1e-5 tier of dense nets is precision='fp32'");
+  if (d->precision != 0) return nfail(AZMI_ERR_INVALID, "precision must be 0 (bf16 MFMA) or 1 (fp32) for a dense net");
+  if (const char* why = dense_refusal(d)) return nfail(AZMI_ERR_INVALID, "%s", why);
+  if (blob_bytes != dense_blob_bytes(d)) return nfail(AZMI_ERR_INVALID, "weight blob is %zu bytes, expected %zu", blob_bytes, dense_blob_bytes(d));
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return nfail(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  if (hipSetDevice(device) != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "hipSetDevice failed");
+  auto net = new azmi_net();
+  net->device = device; net->dense = true;
+  net->dd = dense_desc(d);
+  if (hipMalloc(&net->blob, blob_bytes) != hipSuccess) { delete net; return nfail(AZMI_ERR_OOM, "hipMalloc(weights) failed"); }
+  if (hipMemcpy(net->blob, blob, blob_bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(net->blob); delete net; return nfail(AZMI_ERR_NO_DEVICE, "weight upload failed"); }
+  net->blob_bytes = blob_bytes;
+  const uint8_t* p = static_cast<const uint8_t*>(net->blob);
+  auto f32p = [&](size_t count) { const float* q = reinterpret_cast<const float*>(p); p += count * 4; return q; };
+  dn::DnPtrs& dp = net->dp;
+  const dn::DnDesc& dd = net->dd;
+  dp.blocks = p;
+  for (int i = 0; i < dd.depth; ++i) p += dn::block_bytes(dd, i);
+  dp.head_b = f32p(dn::HEADCH);
+  dp.head_w = p; p += static_cast<size_t>(dd.CFP / 32) * 4 * WFRAG_BYTES;
+  dp.v_fc1_w = f32p(static_cast<size_t>(dd.v_hidden) * dn::HC1); dp.v_fc1_b = f32p(dd.v_hidden);
+  dp.v_fc2_w = f32p(static_cast<size_t>(dd.num_players + 1) * dd.v_hidden); dp.v_fc2_b = f32p(dd.num_players + 1);
+  dp.pi_fc_w = f32p(static_cast<size_t>(dd.num_moves) * dn::HC1 * dn::PIX); dp.pi_fc_b = f32p(dd.num_moves);
+  net->lds_bytes = dn::lds_bytes(dd);
+  // the kernel is shared by every dense net of the process: the attribute is what the widest accepted net asks for
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dn::k_leafnet_dense), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(dn::TBW * dn::board_lds(dn::MAX_CF))) != hipSuccess) {
+    (void)hipFree(net->blob); delete net;
+    return nfail(AZMI_ERR_NO_DEVICE, "cannot reserve %zu bytes of LDS", net->lds_bytes);
+  }
+  *out = net;
+  return AZMI_OK;
+}
+
 void azmi_net_destroy(azmi_net* net) {
   if (!net) return;
   if (net->f32) {
@@ -277,6 +375,7 @@ void azmi_net_destroy(azmi_net* net) {
     net->free_scratch();
     azmi_f32::destroy(net->f32); delete net; return;
   }
+  // spatial, dense and Connect4 tiles alike: the weight image and the per-stream scratch
   (void)hipSetDevice(net->device);
   (void)hipFree(net->blob);
   net->free_scratch();
@@ -304,6 +403,14 @@ static void c4_launch(azmi_net* net, const float* canon, float* v, float* pi, ui
     const uint32_t tiles = (rows_max + c4::TileSmall::TBW - 1) / c4::TileSmall::TBW;
     c4::k_leafnet_c4<c4::TileSmall, 4, 4, 16><<<tiles, c4::NTH, c4::TileSmall::LDS_BYTES, st>>>(net->nd, net->np, canon, v, pi, rows_max, rows, row_count);
   }
+}
+static int dense_forward(azmi_net* net, const float* canon, float* v, float* pi, uint32_t rows_max, const uint32_t* rows, const uint32_t* row_count,
+                         hipStream_t st) {
+  const uint32_t tiles = (rows_max + dn::TBW - 1) / dn::TBW;
+  dn::k_leafnet_dense<<<tiles, dn::NTH, net->lds_bytes, st>>>(net->dd, net->dp, canon, v, pi, rows_max, rows, row_count);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "k_leafnet_dense launch: %s", hipGetErrorString(e));
+  return AZMI_OK;
 }
 static int reserve_pool(azmi_net* net, void* stream, uint32_t batch) {
   azmi_net::StreamScratch& sc = net->scratch_of(stream);
@@ -359,7 +466,8 @@ static int spatial_forward(azmi_net* net, const float* dev_canonical, float* dev
 }
 int azmi_net_reserve_stream(azmi_net* net, void* stream, uint32_t max_rows) {
   if (!net) return nfail(AZMI_ERR_INVALID, "null argument");
-  return net->spatial ? reserve_pool(net, stream, max_rows) : AZMI_OK;
+  if (net->spatial) return reserve_pool(net, stream, max_rows);
+  return AZMI_OK;      // fp32 (sized by its first forward), dense and Connect4 tiles: nothing per stream
 }
 int azmi_net_forward(azmi_net* net, const float* dev_canonical, float* dev_v, float* dev_pi, uint32_t batch, void* stream) {
   return net_forward_live(net, dev_canonical, dev_v, dev_pi, batch, stream, nullptr);
@@ -379,6 +487,7 @@ static int net_forward_live(azmi_net* net, const float* dev_canonical, float* de
     return rc == AZMI_OK ? rc : nfail(rc, "%s", msg);
   }
   if (net->spatial) return spatial_forward(net, dev_canonical, dev_v, dev_pi, batch, stream, nullptr, nullptr);
+  if (net->dense) return dense_forward(net, dev_canonical, dev_v, dev_pi, batch, nullptr, nullptr, static_cast<hipStream_t>(stream));
   c4_launch(net, dev_canonical, dev_v, dev_pi, batch, nullptr, nullptr, static_cast<hipStream_t>(stream));
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "k_leafnet launch: %s", hipGetErrorString(e));
@@ -392,10 +501,11 @@ int azmi_net_forward_rows(azmi_net* net, const float* dev_canonical, float* dev_
   // Rows that are not listed are NOT touched (another model group's answers, cache hits already delivered: ADVICE r1,
   // play_manager.cc:577-597).  The MFMA kernels read and write through the list themselves; workgroups past the count exit.
   if (net->spatial) return spatial_forward(net, dev_canonical, dev_v, dev_pi, max_rows, stream, dev_rows, dev_row_count);
+  if (net->dense) return dense_forward(net, dev_canonical, dev_v, dev_pi, max_rows, dev_rows, dev_row_count, static_cast<hipStream_t>(stream));
   if (net->f32) {
     // the fp32 kernels take a dense batch: gather the listed rows, evaluate, scatter the answers back
     uint32_t chw, p1, m;
-    azmi_f32::dims(net->f32, &chw, &p1, &m);
+    net_dims(net, &chw, &p1, &m);
     hipStream_t st = static_cast<hipStream_t>(stream);
     azmi_net::StreamScratch& sc = net->scratch_of(stream);
     if (max_rows > sc.g_rows) {      // first use of this stream / a larger engine only (synchronous, outside the steady state)
@@ -442,9 +552,7 @@ void azmi_net_eval_host(const float* canonical, uint32_t n, float* v, float* pi,
   azmi_net* net = static_cast<azmi_net*>(net_v);
   if (!net || !canonical || !v || !pi || n == 0) return;
   uint32_t chw, p1, m;
-  if (net->f32) { azmi_f32::dims(net->f32, &chw, &p1, &m); }
-  else if (net->spatial) { chw = net->sd.C_in * net->sd.H * net->sd.W; p1 = net->sd.num_players + 1; m = net->sd.num_moves; }
-  else { chw = net->nd.C_in * net->nd.H * net->nd.W; p1 = net->nd.num_players + 1; m = net->nd.num_moves; }
+  net_dims(net, &chw, &p1, &m);
   auto poison = [&]() {
     for (size_t i = 0; i < static_cast<size_t>(n) * p1; ++i) v[i] = __builtin_nanf("");
     for (size_t i = 0; i < static_cast<size_t>(n) * m; ++i) pi[i] = __builtin_nanf("");
@@ -470,7 +578,7 @@ void azmi_net_eval_host(const float* canonical, uint32_t n, float* v, float* pi,
 }
 
 int azmi_net_c4_view_get(const azmi_net* net, azmi_net_c4_view* out) {
-  if (!net || !out || net->f32 || net->spatial) return 0;
+  if (!net || !out || net->f32 || net->spatial || net->dense) return 0;    // (a dense net never reaches c4_launch or the pipeline)
   out->nd = net->nd; out->np = net->np; out->x3 = net->x3 ? 1 : 0;
   out->lds_bytes = net->x3 ? c4::TileBigX3::LDS_BYTES : c4::TileSmall::LDS_BYTES;   // (bf16: the engine's fused launch runs the small tile)
   return 1;

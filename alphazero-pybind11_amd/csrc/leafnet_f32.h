@@ -7,9 +7,11 @@
 #include "../../include/azmi.h"
 
 namespace azmi_f32 {
-size_t blob_bytes(const azmi_net_desc* d);
+// dense: DenseNet trunk (azmi_net_desc2::dense_net), d->channels = the growth rate.  Bounds: kernel_size 3 (a dense trunk: 1 / 3 / 5 / 7), pooled
+// heads, any widths and depth (a dense trunk: depth >= 1); everything else is refused by name.
+size_t blob_bytes(const azmi_net_desc* d, bool dense);
 // returns AZMI_OK or a negative status; *err receives a static/thread-local message
-int create(const azmi_net_desc* d, const void* blob, size_t bytes, int device, void** impl, const char** err);
+int create(const azmi_net_desc* d, bool dense, const void* blob, size_t bytes, int device, void** impl, const char** err);
 int forward(void* impl, const float* canon, float* v, float* pi, uint32_t batch, void* stream, const char** err);
 int reserve(void* impl, uint32_t batch, const char** err);
 void destroy(void* impl);

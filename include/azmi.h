@@ -709,7 +709,8 @@ int azmi_search_frontier(azmi_search* s, uint8_t* kind, uint64_t* key, double* r
                          uint8_t* child_player, int8_t* child_variant, uint8_t* child_terminal, float* child_scores);
 
 /* ---- leaf policy/value network (the reference's NNArch forward + NNWrapper.process,
- *      neural_net.py:448-510, 800-823) as one fused MFMA kernel ---------------------------------
+ *      neural_net.py:448-510, 800-823) as one fused MFMA kernel; ResNet trunks through azmi_net_create, the reference's
+ *      default DenseNet trunk (with 1x1 / 5x5 / 7x7 convolutions on the fp32 path) through azmi_net_create2 ----------
  * `blob` is the BatchNorm-folded, MFMA-fragment-ordered weight image produced by
  * alphazero/hip_net.py::fold() (layout documented there and in DESIGN.md); it is copied to HBM.
  * forward(): canonical [batch,C,H,W] f32 -> v [batch,P+1], pi [batch,M] f32 probabilities, all
@@ -740,6 +741,24 @@ typedef struct azmi_net_desc {
 typedef struct azmi_net azmi_net;
 size_t azmi_net_blob_bytes(const azmi_net_desc* desc);
 int azmi_net_create(const azmi_net_desc* desc, const void* blob, size_t blob_bytes, int device, azmi_net** out);
+/* The second descriptor: azmi_net_desc is full and its layout is ABI, so what came later stands behind it.  The entry points
+ * yield the same handle type; dense_net = 0 forwards to azmi_net_blob_bytes / azmi_net_create, which refuse what they refused.
+ *   dense_net = 1   the reference's DenseNet trunk (NNArgs.dense_net, the TrainConfig default; neural_net.py:211-230, 302-338): no
+ *                   stem, block i = BN - ReLU - 1x1 to 4 * channels - BN - ReLU - k x k to `channels` (the growth rate) -
+ *                   concatenation; the heads read in_channels + channels * depth features.
+ *                   precision 0: one matrix-core kernel for the dense Connect4 family (csrc/leafnet_dense.h) - 6x7, flat policy
+ *                   head, kernel_size 3 or 5, 1 <= channels <= 16, depth >= 1, in_channels + channels * depth <= 128,
+ *                   head_channels 32, no extra head convolutions, v_fc_layers 1, v_hidden a multiple of 16 up to 256,
+ *                   num_players <= 3, num_moves <= 16; narrower widths are zero-padded by fold().  Everything else, and
+ *                   precision 2, is AZMI_ERR_INVALID with a message naming precision='fp32'.
+ *                   precision 1: any dense shape (every head the fp32 path has), kernel_size 1, 3, 5 or 7 for the trunk and the
+ *                   extra head convolutions.
+ *   reserved        must be zero (AZMI_ERR_INVALID otherwise; blob_bytes2 returns 0).
+ * A dense net runs everywhere an azmi_net does except the asynchronous pipeline, which hard-wires the Connect4 ResNet tile:
+ * azmi_pipeline_supported(_groups) return 0 with it and azmi_run_pipeline(_groups) refuse it. */
+typedef struct azmi_net_desc2 { azmi_net_desc base; int32_t dense_net; int32_t reserved[7]; } azmi_net_desc2;
+size_t azmi_net_blob_bytes2(const azmi_net_desc2* desc);
+int azmi_net_create2(const azmi_net_desc2* desc, const void* blob, size_t blob_bytes, int device, azmi_net** out);
 void azmi_net_destroy(azmi_net* net);
 int azmi_net_forward(azmi_net* net, const float* dev_canonical, float* dev_v, float* dev_pi, uint32_t batch, void* stream);
 /* the same on a subset of the rows: dev_rows[0 .. *dev_row_count) (device memory, read when the kernel runs) are
