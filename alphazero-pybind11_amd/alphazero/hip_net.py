@@ -25,11 +25,43 @@ class NetDescC(C.Structure):
 
 
 class NetDesc2C(C.Structure):
-    """azmi_net_desc2 (include/azmi.h): the first descriptor, then what came later.  Reads of the first one's fields pass through."""
+    """azmi_net_desc2 (include/azmi.h): the first descriptor, then what came later.  Reads of the first one's fields pass through.
+    `reserved` keeps the seven words behind dense_net under their old indices: words 0..2 have names now (trunk_norm, trunk_act,
+    pi_fc_layers, the properties below), reserved[3..6] are the ones that must still be zero."""
     _fields_ = [("base", NetDescC), ("dense_net", C.c_int32), ("reserved", C.c_int32 * 7)]
 
-    def __getattr__(self, name):
+    def __getattr__(self, name):      # (only reached for names the class does not have: the properties below come first)
         return getattr(self.base, name)
+
+    @property
+    def trunk_norm(self):
+        return self.reserved[0]
+
+    @trunk_norm.setter
+    def trunk_norm(self, v):
+        self.reserved[0] = v
+
+    @property
+    def trunk_act(self):
+        return self.reserved[1]
+
+    @trunk_act.setter
+    def trunk_act(self, v):
+        self.reserved[1] = v
+
+    @property
+    def pi_fc_layers(self):
+        return self.reserved[2]
+
+    @pi_fc_layers.setter
+    def pi_fc_layers(self, v):
+        self.reserved[2] = v
+
+
+def is_variant(spec):
+    """what only the second descriptor can say: layer norm, crelu, the policy FC stack.  The fp32 tier runs them all; the dense
+    Connect4 tile has a layer-norm instance (relu, no FC stack), no other tile takes any."""
+    return spec.trunk_norm != "batch" or spec.trunk_act != "relu" or spec.pi_fc_layers > 0
 
 
 def blob_bytes(desc):
@@ -186,7 +218,9 @@ def fold_spatial(net, x3=False):
 def fold_fp32(net):
     """fp32 path (csrc/leafnet_f32.hip): torch layouts, BatchNorms folded in double, no bf16 anywhere.  A ResNet trunk (3x3 only, as
     before) gets the first descriptor and azmi_net_create; a dense trunk (kernel sizes 1 / 3 / 5 / 7, its extra head convolutions
-    included) the second one (NetDesc2C) and azmi_net_create2."""
+    included) the second one (NetDesc2C) and azmi_net_create2, and so does every net with trunk_norm="layer", trunk_act="crelu" or
+    pi_fc_layers > 0, either trunk (the image of those: csrc/leafnet_f32.hip, "variants").  A batch / relu net without the FC stack
+    gets byte for byte the image it always got."""
     spec = net.spec
     Cin, H, W = spec.in_shape
     if not ((spec.kernel_size == 3 or spec.dense_net) and spec.head_pool):
@@ -200,11 +234,21 @@ def fold_fp32(net):
         a, b = (t.cpu() for t in bn_affine(bn))
         return _f32(sd[wname] * a[:, None, None, None]) + _f32(b)
 
-    if not spec.dense_net:
-        blob += conv_bn("conv1.weight", net.bn1)
-    for i, blk in enumerate(net.conv_layers):   # both kinds of block: bn1's affine as it is, bn2 folded into conv1, conv2 raw
-        a1, b1 = (t.cpu() for t in bn_affine(blk.bn1))
-        blob += _f32(a1) + _f32(b1) + conv_bn(f"conv_layers.{i}.conv1.weight", blk.bn2) + _f32(sd[f"conv_layers.{i}.conv2.weight"])
+    def conv_gn(wname, gname):      # layer norm folds into nothing: the raw weight, then the norm's weight and bias
+        return _f32(sd[wname]) + _f32(sd[gname + ".weight"]) + _f32(sd[gname + ".bias"])
+
+    if spec.trunk_norm == "layer":  # g1 b1 | W1 | g2 b2 | W2 (crelu: the weights have their 2 * Cin input channels as they are)
+        if not spec.dense_net:
+            blob += conv_gn("conv1.weight", "bn1")
+        for i in range(spec.depth):
+            pre = f"conv_layers.{i}."
+            blob += _f32(sd[pre + "bn1.weight"]) + _f32(sd[pre + "bn1.bias"]) + conv_gn(pre + "conv1.weight", pre + "bn2") + _f32(sd[pre + "conv2.weight"])
+    else:
+        if not spec.dense_net:
+            blob += conv_bn("conv1.weight", net.bn1)
+        for i, blk in enumerate(net.conv_layers):   # both kinds of block: bn1's affine as it is, bn2 folded into conv1, conv2 raw
+            a1, b1 = (t.cpu() for t in bn_affine(blk.bn1))
+            blob += _f32(a1) + _f32(b1) + conv_bn(f"conv_layers.{i}.conv1.weight", blk.bn2) + _f32(sd[f"conv_layers.{i}.conv2.weight"])
     blob += conv_bn("v_conv.weight", net.v_bn)
     for i in range(spec.v_head_convs):
         blob += conv_bn(f"v_extra_convs.{3 * i}.weight", net.v_extra_convs[3 * i + 1])
@@ -224,11 +268,16 @@ def fold_fp32(net):
                 blob += _f32(sd[k])
     else:
         blob += _f32(sd["pi_fc1.weight"]) + _f32(sd["pi_fc1.bias"])
+        if spec.pi_fc_layers > 0:
+            for l in range(spec.pi_fc_layers - 1):
+                blob += _f32(sd[f"pi_fc_extra.{2 * l}.weight"]) + _f32(sd[f"pi_fc_extra.{2 * l}.bias"])
+            blob += _f32(sd["pi_fc_out.weight"]) + _f32(sd["pi_fc_out.bias"])
     desc = NetDescC(Cin, H, W, spec.num_channels, spec.depth, spec.kernel_size, spec.head_channels, spec.v_fc_hidden, spec.num_moves,
                     spec.num_players, spec.v_head_convs, spec.pi_head_convs, spec.v_fc_layers, pc, 1,
-                    spec.pi_fc_hidden if (pc and spec.num_moves > pc * H * W) else 0)
-    if spec.dense_net:
-        desc = NetDesc2C(desc, 1)
+                    spec.pi_fc_hidden if ((pc and spec.num_moves > pc * H * W) or spec.pi_fc_layers > 0) else 0)
+    if spec.dense_net or is_variant(spec):
+        desc = NetDesc2C(desc, int(spec.dense_net))
+        desc.trunk_norm, desc.trunk_act, desc.pi_fc_layers = int(spec.trunk_norm == "layer"), int(spec.trunk_act == "crelu"), spec.pi_fc_layers
     assert len(blob) == blob_bytes(desc), (len(blob), blob_bytes(desc))
     return desc, bytes(blob)
 
@@ -246,12 +295,17 @@ def fold_dense(net):
                W1 frag[roundup32(C_i)/32][ceil(4G/16)] (rows = bn2-scaled conv1, k = input channel) |
                W2: per tap (dy, dx) row-major frag[ceil(4G/32)][1] (rows = the G outputs, rows >= G zero; k = bottleneck channel)
       heads    bh[64] f32 | Wh frag[CFP/32][4] (rows 0-31 = v_conv * v_bn, rows 32-63 = pi_conv * pi_bn)
-      v_fc1 W[Hd][32] b[Hd] | v_fc2 W[P+1][Hd] b[P+1] | pi_fc1 W[M][32*42] b[M]   (f32, torch layouts)"""
+      v_fc1 W[Hd][32] b[Hd] | v_fc2 W[P+1][Hd] b[P+1] | pi_fc1 W[M][32*42] b[M]   (f32, torch layouts)
+    trunk_norm="layer" (the kernel's LAYER instance; trunk_act relu, no policy FC stack): nothing folds -
+      block i  g1[CFP] b1[CFP] (bn1's weight and bias, zero behind C_i) g2[64] b2[64] (bn2's, zero behind 4G) f32 | W1 (raw rows) | W2"""
     spec = net.spec
     Cin, H, W = spec.in_shape
     G, D, K = spec.num_channels, spec.depth, spec.kernel_size
     tail = "; use precision='fp32' for other shapes"
     # the bounds of azmi_net_create2 (csrc/leafnet.hip dense_refusal), with its messages
+    layer = spec.trunk_norm == "layer"
+    if spec.trunk_act != "relu" or spec.pi_fc_layers > 0:   # (crelu would double K beyond the LDS plan; no tile has the policy FC stack)
+        raise RuntimeError("dense leaf net kernel: trunk_act='relu' and pi_fc_layers=0 only; use precision='fp32' for crelu and the policy FC stack")
     if spec.policy_shape is not None or (H, W) != (6, 7):
         raise RuntimeError("dense leaf net kernel covers the 6x7 board with the flat policy head" + tail)
     if K not in (3, 5):
@@ -273,10 +327,16 @@ def fold_dense(net):
     blob = bytearray()
     for i, blk in enumerate(net.conv_layers):
         Ci = Cin + G * i
-        a1, b1 = (t.cpu() for t in bn_affine(blk.bn1))
-        a2, b2 = (t.cpu() for t in bn_affine(blk.bn2))
-        blob += _f32(_pad(a1, CFP)) + _f32(_pad(b1, CFP)) + _f32(_pad(b2, 64))
-        blob += _frags(_pad(sd[f"conv_layers.{i}.conv1.weight"][:, :, 0, 0] * a2[:, None], M1, _up(Ci, 32)).numpy())
+        if layer:
+            pre = f"conv_layers.{i}."
+            blob += _f32(_pad(sd[pre + "bn1.weight"], CFP)) + _f32(_pad(sd[pre + "bn1.bias"], CFP))
+            blob += _f32(_pad(sd[pre + "bn2.weight"], 64)) + _f32(_pad(sd[pre + "bn2.bias"], 64))
+            blob += _frags(_pad(sd[pre + "conv1.weight"][:, :, 0, 0], M1, _up(Ci, 32)).numpy())
+        else:
+            a1, b1 = (t.cpu() for t in bn_affine(blk.bn1))
+            a2, b2 = (t.cpu() for t in bn_affine(blk.bn2))
+            blob += _f32(_pad(a1, CFP)) + _f32(_pad(b1, CFP)) + _f32(_pad(b2, 64))
+            blob += _frags(_pad(sd[f"conv_layers.{i}.conv1.weight"][:, :, 0, 0] * a2[:, None], M1, _up(Ci, 32)).numpy())
         w2 = sd[f"conv_layers.{i}.conv2.weight"]                     # [G][4G][K][K]
         for dy in range(K):
             for dx in range(K):
@@ -288,6 +348,7 @@ def fold_dense(net):
     blob += _f32(sd["v_fc1.weight"]) + _f32(sd["v_fc1.bias"]) + _f32(sd["v_fc2.weight"]) + _f32(sd["v_fc2.bias"])
     blob += _f32(sd["pi_fc1.weight"]) + _f32(sd["pi_fc1.bias"])
     desc = NetDesc2C(NetDescC(Cin, H, W, G, D, K, 32, spec.v_fc_hidden, spec.num_moves, spec.num_players, 0, 0, 1, 0, 0, 0), 1)
+    desc.trunk_norm = int(layer)
     assert len(blob) == blob_bytes(desc), (len(blob), blob_bytes(desc))
     return desc, bytes(blob)
 
@@ -312,13 +373,20 @@ def fold(net, precision="bf16"):
     """LeafNet (reference NNArch parameter names) -> (NetDescC or NetDesc2C, blob bytes).  precision: "bf16" (bf16 MFMA operands),
     "bf16x3" (weights and activations as bf16 high + low parts, three MFMAs per product - the 1e-5 tier on the matrix cores; the
     Connect4 family and, since round 4, the spatial-head nets) or "fp32" (plain fp32 kernels, any shape).  A dense trunk
-    (spec.dense_net) has the "bf16" tile of fold_dense and "fp32"."""
+    (spec.dense_net) has the "bf16" tile of fold_dense and "fp32".  trunk_norm="layer", trunk_act="crelu" and pi_fc_layers > 0
+    have "fp32"; a dense trunk with trunk_norm="layer" alone also has the "bf16" tile; everything else raises RuntimeError naming
+    precision='fp32'."""
     if precision == "fp32":
         return fold_fp32(net)
     spec = net.spec
     x3 = precision == "bf16x3"
     if precision not in ("bf16", "bf16x3"):
         raise ValueError("precision must be 'bf16', 'bf16x3' or 'fp32'")
+    tile_layer = spec.dense_net and not x3 and spec.trunk_norm == "layer" and spec.trunk_act == "relu" and spec.pi_fc_layers == 0
+    if is_variant(spec) and not tile_layer:    # azmi_net_create2's refusal (csrc/leafnet.hip kVariantOnTile), before anything is laid out
+        raise RuntimeError("the matrix-core tiles cover trunk_act='relu' and pi_fc_layers=0, with trunk_norm='batch' or, on the dense "
+                           "Connect4 tile (precision 'bf16'), 'layer'; use precision='fp32' for the other layer-norm nets, crelu and "
+                           "the policy FC stack")
     if spec.dense_net:
         if x3:
             raise RuntimeError("dense leaf net: no bf16x3 tier; the 1e-5 tier of dense nets is precision='fp32'")

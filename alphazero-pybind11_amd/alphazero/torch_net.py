@@ -11,9 +11,14 @@
 
 Covered: both trunks - the ResNet one (`dense_net=False`, what BASELINE.json's configs use) and the DenseNet one
 (`dense_net=True`, the reference's `TrainConfig` default: no stem, `conv_layers.{i}` = DenseBlock with bn_size 4) - with
-`trunk_norm="batch"`, `trunk_act="relu"`, any odd `kernel_size` in 1..7 (the HIP tiers: 3, and 1 / 5 / 7 on dense trunks), the value head and the flat / spatial policy heads.
-NOT covered (a spec cannot say them): `trunk_norm="layer"`, `trunk_act="crelu"`, `pi_fc_layers > 0`; `head_pool=False` builds
-in torch but no HIP tier takes it.
+`trunk_norm` "batch" or "layer" (`nn.GroupNorm(1, C)`: per-sample statistics over (C, H, W); the heads keep BatchNorm),
+`trunk_act` "relu" or "crelu" (`cat([relu(x), relu(-x)])`: the convolution behind it has twice the input channels), any odd
+`kernel_size` in 1..7 (the HIP tiers: 3, and 1 / 5 / 7 on dense trunks), the value head, the flat policy head with or without
+its FC stack (`pi_fc_layers`: pi_fc1 - ReLU - pi_fc_extra - pi_fc_out) and the spatial policy head.  The eight norm x activation x
+trunk combinations all run on the fp32 tier (csrc/leafnet_f32.hip); of the matrix-core tiles the dense Connect4 one also takes
+`trunk_norm="layer"` (csrc/leafnet_dense.h), the others keep batch / relu / no FC stack.
+NOT covered: `head_pool=False` builds in torch but no HIP tier takes it; a spatial head has no FC stack (the reference's
+`spatial_policy="auto"` falls back to the flat head then: here the caller leaves `policy_shape` out).
 """
 from dataclasses import dataclass
 
@@ -38,10 +43,21 @@ class NetSpec:
     policy_shape: tuple = None  # POLICY_SHAPE (C, H, W) -> spatial head (neural_net.py:390-427)
     pi_fc_hidden: int = -1   # -1 -> head_channels * 8; hidden width of pi_global (spatial head with global actions)
     dense_net: bool = False  # NNArgs.dense_net: DenseNet trunk, num_channels = the growth rate (neural_net.py:302-338)
+    trunk_norm: str = "batch"   # NNArgs.trunk_norm: "batch" or "layer" = GroupNorm(1, C) on every trunk norm (neural_net.py:166-180)
+    trunk_act: str = "relu"     # NNArgs.trunk_act: "relu" or "crelu" (neural_net.py:183-208)
+    pi_fc_layers: int = 0       # NNArgs.pi_fc_layers: hidden layers (width pi_fc_hidden) of the flat policy head (neural_net.py:431-442)
 
     def __post_init__(self):
         if self.kernel_size not in (1, 3, 5, 7):
             raise ValueError("kernel_size must be an odd value in 1..7")
+        if self.trunk_norm not in ("batch", "layer"):
+            raise ValueError(f"trunk_norm must be 'batch' or 'layer', got {self.trunk_norm!r}")
+        if self.trunk_act not in ("relu", "crelu"):
+            raise ValueError(f"trunk_act must be 'relu' or 'crelu', got {self.trunk_act!r}")
+        if self.pi_fc_layers < 0:
+            raise ValueError("pi_fc_layers must be >= 0")
+        if self.pi_fc_layers > 0 and self.policy_shape is not None:
+            raise ValueError("pi_fc_layers > 0 is the flat policy head's FC stack: leave policy_shape out")
         if self.v_fc_hidden == -1:
             self.v_fc_hidden = self.head_channels * 8
         if self.pi_fc_hidden == -1:
@@ -52,15 +68,29 @@ def _conv(cin, cout, k):
     return nn.Conv2d(cin, cout, kernel_size=k, stride=1, padding="same", bias=False)  # neural_net.py:147-155
 
 
+def _norm(ch, kind):  # neural_net.py:166-180
+    return nn.GroupNorm(1, ch) if kind == "layer" else nn.BatchNorm2d(ch)
+
+
+class CReLU(nn.Module):  # neural_net.py:183-194
+    def forward(self, x):
+        return torch.cat([torch.relu(x), torch.relu(-x)], dim=1)
+
+
+def _act(ch, kind):
+    """(activation, channels behind it)  neural_net.py:197-208"""
+    return (CReLU(), 2 * ch) if kind == "crelu" else (nn.ReLU(inplace=True), ch)
+
+
 class ResidualBlock(nn.Module):  # neural_net.py:233-263 (no downsample)
-    def __init__(self, ch, k):
+    def __init__(self, ch, k, norm="batch", act="relu"):
         super().__init__()
-        self.bn1 = nn.BatchNorm2d(ch)
-        self.relu1 = nn.ReLU(inplace=True)
-        self.conv1 = _conv(ch, ch, k)
-        self.bn2 = nn.BatchNorm2d(ch)
-        self.relu2 = nn.ReLU(inplace=True)
-        self.conv2 = _conv(ch, ch, k)
+        self.bn1 = _norm(ch, norm)
+        self.relu1, c1 = _act(ch, act)
+        self.conv1 = _conv(c1, ch, k)
+        self.bn2 = _norm(ch, norm)
+        self.relu2, c2 = _act(ch, act)
+        self.conv2 = _conv(c2, ch, k)
 
     def forward(self, x):
         out = self.conv1(self.relu1(self.bn1(x)))
@@ -69,14 +99,14 @@ class ResidualBlock(nn.Module):  # neural_net.py:233-263 (no downsample)
 
 
 class DenseBlock(nn.Module):  # neural_net.py:211-230
-    def __init__(self, cin, growth, bn_size=4, k=3):
+    def __init__(self, cin, growth, bn_size=4, k=3, norm="batch", act="relu"):
         super().__init__()
-        self.bn1 = nn.BatchNorm2d(cin)
-        self.relu1 = nn.ReLU(inplace=True)
-        self.conv1 = _conv(cin, growth * bn_size, 1)
-        self.bn2 = nn.BatchNorm2d(growth * bn_size)
-        self.relu2 = nn.ReLU(inplace=True)
-        self.conv2 = _conv(growth * bn_size, growth, k)
+        self.bn1 = _norm(cin, norm)
+        self.relu1, c1 = _act(cin, act)
+        self.conv1 = _conv(c1, growth * bn_size, 1)
+        self.bn2 = _norm(growth * bn_size, norm)
+        self.relu2, c2 = _act(growth * bn_size, act)
+        self.conv2 = _conv(c2, growth, k)
 
     def forward(self, x):
         out = self.conv1(self.relu1(self.bn1(x)))
@@ -90,13 +120,14 @@ class LeafNet(nn.Module):
         self.spec = spec
         C, H, W = spec.in_shape
         ch, HC, k = spec.num_channels, spec.head_channels, spec.kernel_size
+        norm, act = spec.trunk_norm, spec.trunk_act
         if spec.dense_net:   # no stem (neural_net.py:302-306); the heads read every feature (:332-335)
-            self.conv_layers = nn.Sequential(*[DenseBlock(C + ch * i, ch, 4, k) for i in range(spec.depth)])
+            self.conv_layers = nn.Sequential(*[DenseBlock(C + ch * i, ch, 4, k, norm, act) for i in range(spec.depth)])
             trunk_out = C + ch * spec.depth
         else:
             self.conv1 = _conv(C, ch, k)
-            self.bn1 = nn.BatchNorm2d(ch)
-            self.conv_layers = nn.Sequential(*[ResidualBlock(ch, k) for _ in range(spec.depth)])
+            self.bn1 = _norm(ch, norm)
+            self.conv_layers = nn.Sequential(*[ResidualBlock(ch, k, norm, act) for _ in range(spec.depth)])
             trunk_out = ch
         self.v_conv = _conv(trunk_out, HC, 1)
         self.pi_conv = _conv(trunk_out, HC, 1)
@@ -137,7 +168,16 @@ class LeafNet(nn.Module):
                                                nn.Linear(spec.pi_fc_hidden, self.num_global_actions), nn.LayerNorm(self.num_global_actions))
         else:
             self.pi_flatten = nn.Flatten()
-            self.pi_fc1 = nn.Linear(H * W * HC, spec.num_moves)
+            if spec.pi_fc_layers > 0:   # neural_net.py:431-442
+                self.pi_fc1 = nn.Linear(H * W * HC, spec.pi_fc_hidden)
+                if spec.pi_fc_layers > 1:
+                    extra = []
+                    for _ in range(spec.pi_fc_layers - 1):
+                        extra += [nn.Linear(spec.pi_fc_hidden, spec.pi_fc_hidden), nn.ReLU(inplace=True)]
+                    self.pi_fc_extra = nn.Sequential(*extra)
+                self.pi_fc_out = nn.Linear(spec.pi_fc_hidden, spec.num_moves)
+            else:
+                self.pi_fc1 = nn.Linear(H * W * HC, spec.num_moves)
 
     def forward(self, s):  # neural_net.py:448-510 — returns LOG-probabilities like the reference
         if not self.spec.dense_net:
@@ -161,6 +201,11 @@ class LeafNet(nn.Module):
                 flat = self.pi_flatten(self.pi_pool(pi) if self.pi_pool is not None else pi)
                 sp = torch.cat([sp, self.pi_global(flat)], dim=1)
             pi = sp
+        elif self.spec.pi_fc_layers > 0:   # neural_net.py:497-504
+            pi = torch.relu(self.pi_fc1(self.pi_flatten(pi)))
+            if hasattr(self, "pi_fc_extra"):
+                pi = self.pi_fc_extra(pi)
+            pi = self.pi_fc_out(pi)
         else:
             pi = self.pi_fc1(self.pi_flatten(pi))
         return v, torch.log_softmax(pi, dim=1)
@@ -224,7 +269,8 @@ def stargambit_spec(depth=4, channels=64, head_channels=64):
 
 def random_init(spec, seed=0, randomize_bn=True):
     """Random-init net of the named architecture (no checkpoint / dataset is reachable here).
-    BatchNorm statistics and affine parameters are randomised too so that BN folding is exercised."""
+    BatchNorm statistics and affine parameters are randomised too so that BN folding is exercised, and the trunk's
+    GroupNorm weights and biases (trunk_norm="layer") in the same way: an identity affine hides a dropped one."""
     torch.manual_seed(seed)
     net = LeafNet(spec)
     if randomize_bn:
@@ -235,6 +281,9 @@ def random_init(spec, seed=0, randomize_bn=True):
                 m.running_var.copy_(torch.rand(m.num_features, generator=g) * 1.0 + 0.5)
                 m.weight.data.copy_(torch.rand(m.num_features, generator=g) * 0.8 + 0.6)
                 m.bias.data.copy_(torch.randn(m.num_features, generator=g) * 0.1)
+            elif isinstance(m, nn.GroupNorm):
+                m.weight.data.copy_(torch.rand(m.num_channels, generator=g) * 0.8 + 0.6)
+                m.bias.data.copy_(torch.randn(m.num_channels, generator=g) * 0.1)
     return net.eval()
 
 

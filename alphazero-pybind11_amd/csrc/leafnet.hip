@@ -59,6 +59,7 @@ struct azmi_net {
   bool f32_last_stream_set = false;
   bool spatial = false;      // spatial policy head (Tafl family, StarGambit): sp::k_leafnet_sp
   bool dense = false;        // DenseNet trunk on the matrix cores (dense Connect4 family): dn::k_leafnet_dense
+  bool dense_layer = false;  // ... its trunk_norm = layer instance (k_leafnet_dense<true>)
   dn::DnDesc dd{};
   dn::DnPtrs dp{};
   sp::SpDesc sd{};
@@ -135,10 +136,10 @@ const char* dense_refusal(const azmi_net_desc* d) {
     return "dense leaf net kernel: head sizes out of range (v_hidden: a multiple of 16, at most 256; 1..3 players; 1..16 moves); use precision='fp32' for other shapes";
   return nullptr;
 }
-size_t dense_blob_bytes(const azmi_net_desc* d) {
+size_t dense_blob_bytes(const azmi_net_desc* d, bool layer = false) {
   const dn::DnDesc dd = dense_desc(d);
   size_t n = 0;
-  for (int i = 0; i < dd.depth; ++i) n += dn::block_bytes(dd, i);
+  for (int i = 0; i < dd.depth; ++i) n += dn::block_bytes(dd, i, layer);
   n += dn::HEADCH * 4 + static_cast<size_t>(dd.CFP / 32) * 4 * WFRAG_BYTES;
   n += (static_cast<size_t>(dd.v_hidden) * dn::HC1 + dd.v_hidden) * 4;
   n += (static_cast<size_t>(dd.num_players + 1) * dd.v_hidden + dd.num_players + 1) * 4;
@@ -149,6 +150,30 @@ bool reserved_zero(const azmi_net_desc2* d) {
   for (int32_t r : d->reserved) if (r != 0) return false;
   return true;
 }
+// The words behind dense_net: NULL when they are in range, else what is not
+const char* variant_refusal(const azmi_net_desc2* d) {
+  if (d->trunk_norm != 0 && d->trunk_norm != 1) return "azmi_net_desc2: trunk_norm must be 0 (batch) or 1 (layer)";
+  if (d->trunk_act != 0 && d->trunk_act != 1) return "azmi_net_desc2: trunk_act must be 0 (relu) or 1 (crelu)";
+  if (d->pi_fc_layers < 0) return "azmi_net_desc2: pi_fc_layers must be >= 0";
+  if (d->pi_fc_layers > 0 && d->base.policy_channels > 0) return "azmi_net_desc2: pi_fc_layers > 0 is the flat policy head's FC stack (policy_channels must be 0)";
+  if (d->pi_fc_layers > 0 && d->base.pi_hidden < 1) return "azmi_net_desc2: pi_fc_layers > 0 needs pi_hidden (the stack's width)";
+  return nullptr;
+}
+bool is_variant(const azmi_net_desc2* d) { return d->trunk_norm != 0 || d->trunk_act != 0 || d->pi_fc_layers != 0; }
+azmi_f32::Variant f32_variant(const azmi_net_desc2* d) {
+  azmi_f32::Variant v;
+  v.trunk_norm = d->trunk_norm; v.trunk_act = d->trunk_act; v.pi_fc_layers = d->pi_fc_layers;
+  return v;
+}
+// The one variant a matrix-core tile takes: the dense tile's layer-norm instance (trunk_act relu, no policy FC stack).  The ResNet
+// tiles are tuned around the folded BatchNorms, the dense tile's LDS plan has no room for crelu's doubled K, and no tile has
+// the policy FC stack
+bool tile_layer(const azmi_net_desc2* d) {
+  return d->dense_net == 1 && d->base.precision == 0 && d->trunk_norm == 1 && d->trunk_act == 0 && d->pi_fc_layers == 0;
+}
+const char* kVariantOnTile = "the matrix-core tiles cover trunk_act='relu' and pi_fc_layers=0, with trunk_norm='batch' or, on the dense "
+                             "Connect4 tile (precision 'bf16'), 'layer'; use precision='fp32' for the other layer-norm nets, crelu and "
+                             "the policy FC stack";
 // what a batch row is made of, whichever implementation stands behind the net
 void net_dims(const azmi_net* net, uint32_t* chw, uint32_t* p1, uint32_t* m) {
   if (net->f32) azmi_f32::dims(net->f32, chw, p1, m);
@@ -191,10 +216,11 @@ size_t azmi_net_blob_bytes(const azmi_net_desc* d) {
   return n;
 }
 
-static int f32_create(const azmi_net_desc* d, bool dense, const void* blob, size_t blob_bytes, int device, azmi_net** out) {
+static int f32_create(const azmi_net_desc* d, bool dense, const void* blob, size_t blob_bytes, int device, azmi_net** out,
+                      azmi_f32::Variant var = azmi_f32::Variant{}) {
   const char* msg = "";
   void* impl = nullptr;
-  const int rc = azmi_f32::create(d, dense, blob, blob_bytes, device, &impl, &msg);
+  const int rc = azmi_f32::create(d, dense, blob, blob_bytes, device, &impl, &msg, var);
   if (rc != AZMI_OK) return nfail(rc, "%s", msg);
   auto net = new azmi_net();
   net->device = device; net->f32 = impl;
@@ -320,7 +346,9 @@ int azmi_net_create(const azmi_net_desc* d, const void* blob, size_t blob_bytes,
 }
 
 size_t azmi_net_blob_bytes2(const azmi_net_desc2* d) {
-  if (!d || !reserved_zero(d)) return 0;
+  if (!d || !reserved_zero(d) || variant_refusal(d)) return 0;
+  if (tile_layer(d)) return !dense_refusal(&d->base) ? dense_blob_bytes(&d->base, true) : 0;
+  if (is_variant(d)) return d->base.precision == 1 && (d->dense_net == 0 || d->dense_net == 1) ? azmi_f32::blob_bytes(&d->base, d->dense_net == 1, f32_variant(d)) : 0;
   if (!d->dense_net) return azmi_net_blob_bytes(&d->base);
   if (d->base.precision == 1) return azmi_f32::blob_bytes(&d->base, true);
   return d->base.precision == 0 && !dense_refusal(&d->base) ? dense_blob_bytes(&d->base) : 0;
@@ -330,18 +358,24 @@ int azmi_net_create2(const azmi_net_desc2* d2, const void* blob, size_t blob_byt
   if (!d2 || !blob || !out) return nfail(AZMI_ERR_INVALID, "null argument");
   if (!reserved_zero(d2)) return nfail(AZMI_ERR_INVALID, "azmi_net_desc2: reserved words must be zero");
   if (d2->dense_net != 0 && d2->dense_net != 1) return nfail(AZMI_ERR_INVALID, "azmi_net_desc2: dense_net must be 0 or 1");
+  if (const char* why = variant_refusal(d2)) return nfail(AZMI_ERR_INVALID, "%s", why);
   const azmi_net_desc* d = &d2->base;
+  const bool layer = tile_layer(d2);
+  if (is_variant(d2) && !layer) {      // either trunk, the fp32 tier
+    if (d->precision != 1) return nfail(AZMI_ERR_INVALID, "%s", kVariantOnTile);
+    return f32_create(d, d2->dense_net == 1, blob, blob_bytes, device, out, f32_variant(d2));
+  }
   if (!d2->dense_net) return azmi_net_create(d, blob, blob_bytes, device, out);      // the old entry, with everything it refuses
   if (d->precision == 1) return f32_create(d, true, blob, blob_bytes, device, out);
   if (d->precision == 2) return nfail(AZMI_ERR_INVALID, "dense leaf net: no bf16x3 tier; the 1e-5 tier of dense nets is precision='fp32'");
   if (d->precision != 0) return nfail(AZMI_ERR_INVALID, "precision must be 0 (bf16 MFMA) or 1 (fp32) for a dense net");
   if (const char* why = dense_refusal(d)) return nfail(AZMI_ERR_INVALID, "%s", why);
-  if (blob_bytes != dense_blob_bytes(d)) return nfail(AZMI_ERR_INVALID, "weight blob is %zu bytes, expected %zu", blob_bytes, dense_blob_bytes(d));
+  if (blob_bytes != dense_blob_bytes(d, layer)) return nfail(AZMI_ERR_INVALID, "weight blob is %zu bytes, expected %zu", blob_bytes, dense_blob_bytes(d, layer));
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return nfail(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
   if (hipSetDevice(device) != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "hipSetDevice failed");
   auto net = new azmi_net();
-  net->device = device; net->dense = true;
+  net->device = device; net->dense = true; net->dense_layer = layer;
   net->dd = dense_desc(d);
   if (hipMalloc(&net->blob, blob_bytes) != hipSuccess) { delete net; return nfail(AZMI_ERR_OOM, "hipMalloc(weights) failed"); }
   if (hipMemcpy(net->blob, blob, blob_bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(net->blob); delete net; return nfail(AZMI_ERR_NO_DEVICE, "weight upload failed"); }
@@ -351,7 +385,7 @@ int azmi_net_create2(const azmi_net_desc2* d2, const void* blob, size_t blob_byt
   dn::DnPtrs& dp = net->dp;
   const dn::DnDesc& dd = net->dd;
   dp.blocks = p;
-  for (int i = 0; i < dd.depth; ++i) p += dn::block_bytes(dd, i);
+  for (int i = 0; i < dd.depth; ++i) p += dn::block_bytes(dd, i, layer);
   dp.head_b = f32p(dn::HEADCH);
   dp.head_w = p; p += static_cast<size_t>(dd.CFP / 32) * 4 * WFRAG_BYTES;
   dp.v_fc1_w = f32p(static_cast<size_t>(dd.v_hidden) * dn::HC1); dp.v_fc1_b = f32p(dd.v_hidden);
@@ -359,8 +393,8 @@ int azmi_net_create2(const azmi_net_desc2* d2, const void* blob, size_t blob_byt
   dp.pi_fc_w = f32p(static_cast<size_t>(dd.num_moves) * dn::HC1 * dn::PIX); dp.pi_fc_b = f32p(dd.num_moves);
   net->lds_bytes = dn::lds_bytes(dd);
   // the kernel is shared by every dense net of the process: the attribute is what the widest accepted net asks for
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dn::k_leafnet_dense), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          static_cast<int>(dn::TBW * dn::board_lds(dn::MAX_CF))) != hipSuccess) {
+  if (hipFuncSetAttribute(layer ? reinterpret_cast<const void*>(&dn::k_leafnet_dense<true>) : reinterpret_cast<const void*>(&dn::k_leafnet_dense<false>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(dn::TBW * dn::board_lds(dn::MAX_CF))) != hipSuccess) {
     (void)hipFree(net->blob); delete net;
     return nfail(AZMI_ERR_NO_DEVICE, "cannot reserve %zu bytes of LDS", net->lds_bytes);
   }
@@ -407,7 +441,8 @@ static void c4_launch(azmi_net* net, const float* canon, float* v, float* pi, ui
 static int dense_forward(azmi_net* net, const float* canon, float* v, float* pi, uint32_t rows_max, const uint32_t* rows, const uint32_t* row_count,
                          hipStream_t st) {
   const uint32_t tiles = (rows_max + dn::TBW - 1) / dn::TBW;
-  dn::k_leafnet_dense<<<tiles, dn::NTH, net->lds_bytes, st>>>(net->dd, net->dp, canon, v, pi, rows_max, rows, row_count);
+  if (net->dense_layer) dn::k_leafnet_dense<true><<<tiles, dn::NTH, net->lds_bytes, st>>>(net->dd, net->dp, canon, v, pi, rows_max, rows, row_count);
+  else dn::k_leafnet_dense<false><<<tiles, dn::NTH, net->lds_bytes, st>>>(net->dd, net->dp, canon, v, pi, rows_max, rows, row_count);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "k_leafnet_dense launch: %s", hipGetErrorString(e));
   return AZMI_OK;

@@ -31,6 +31,19 @@
 //   block i  a1[CFP] b1[CFP] c1[64] f32 | W1 frag[roundup32(C_i)/32 ks][ceil(4G/16) mt] | W2 frag[K*K taps][ceil(4G/32) ks]
 //   heads    bh[64] f32 | Wh frag[CFP/32 ks][4 mt]
 //   v_fc1 W[Hd][32] b[Hd] | v_fc2 W[P+1][Hd] b[P+1] | pi_fc1 W[M][32*42] b[M]    (f32, torch layouts)
+//
+// LAYER instance (trunk_norm = "layer": bn1 / bn2 are nn.GroupNorm(1, C), neural_net.py:166-180; trunk_act relu).  The statistics
+// are per board and one wavefront owns one board, so both reductions are wave-local (lane sums, then a 6-step butterfly), in fp32,
+// two passes each - the mean, then the variance AROUND it - and need no LDS of their own:
+//   bn1 of block i  over the raw fp32 features feat[p][c], p < 42, c < C_i: the channels C_i..roundup32(C_i) of the k-steps and the
+//                   row's tail are not read.  step 1 becomes B = bf16(relu(g1[c] * ((x - mean) * inv) + b1[c])): the normalised value
+//                   is formed in fp32 before the only rounding (padded g1 = b1 = 0 keep the padded channels 0).
+//   bn2             over the 1x1's fp32 accumulators, rows m < 4G (rows 4G.. of the 16-row tiles are left out) x the 42 real pixel
+//                   columns (the six repeated columns 42..47 are left out), before anything is rounded; step 2 becomes
+//                   mid[p][m] = bf16(relu(g2[m] * ((acc - mean) * inv) + b2[m])) with g2 = b2 = 0 in rows >= 4G.
+// inv = 1 / sqrt(var + 1e-5): a constant tensor gives 1 / sqrt(eps) and finite outputs (an idle wavefront runs on zeros).
+// Image of a block: g1[CFP] b1[CFP] g2[64] b2[64] f32 | W1 (raw rows) | W2 - 256 bytes more than the batch one; the rest is the same.
+// The batch instance is the kernel it was (profiles/leafnet_dense_layer_identity.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,8 +77,8 @@ struct DnPtrs {            // device pointers into the folded weight image
 __host__ __device__ constexpr int round_up(int x, int m) { return (x + m - 1) / m * m; }
 __host__ __device__ inline int feat_pitch(int cfp) { return cfp + 4; }                              // floats per pixel
 __host__ __device__ inline size_t board_lds(int cfp) { return static_cast<size_t>(PIX) * feat_pitch(cfp) * 4 + MID_BYTES + VEC_FLOATS * 4; }
-__host__ __device__ inline size_t block_bytes(const DnDesc& d, int i) {
-  return (2 * static_cast<size_t>(d.CFP) + 64) * 4 +
+__host__ __device__ inline size_t block_bytes(const DnDesc& d, int i, bool layer = false) {
+  return (2 * static_cast<size_t>(d.CFP) + (layer ? 128 : 64)) * 4 +
          (static_cast<size_t>(round_up(d.C_in + d.G * i, 32) / 32) * round_up(4 * d.G, 16) / 16 +
           static_cast<size_t>(d.K) * d.K * (round_up(4 * d.G, 32) / 32)) * WFRAG_BYTES;
 }
@@ -77,6 +90,7 @@ __device__ __forceinline__ bf16x8 ldg_frag(const uint8_t* frag, int lane) {
 
 // rows / row_count (may be NULL): the eval list - board g of the launch is slot rows[g] while g < *row_count, and is not
 // evaluated (nothing read, nothing written) from there on; without a list board g is row g while g < batch
+template <bool LAYER>
 __global__ __launch_bounds__(NTH) void k_leafnet_dense(DnDesc d, DnPtrs w, const float* __restrict__ canon, float* __restrict__ v_out,
                                                        float* __restrict__ pi_out, uint32_t batch, const uint32_t* __restrict__ rows,
                                                        const uint32_t* __restrict__ row_count) {
@@ -111,7 +125,7 @@ __global__ __launch_bounds__(NTH) void k_leafnet_dense(DnDesc d, DnPtrs w, const
   }
   // B fragments of one k-step of a 1x1 convolution over feat: channels 32*ks + 8*q .. + 7 of the lane's pixels, through
   // relu(a * x + b) when a != nullptr
-  auto feat_frags = [&](int ks, const float* a, const float* b, bf16x8* out) {
+  auto feat_frags = [&](int ks, const float* a, const float* b, bf16x8* out, float mean = 0.0f, float inv = 1.0f) {
     const int c0 = 32 * ks + 8 * q;
     float sa[8], sb[8];
     if (a) {
@@ -124,7 +138,8 @@ __global__ __launch_bounds__(NTH) void k_leafnet_dense(DnDesc d, DnPtrs w, const
       const f32x4 x0 = *reinterpret_cast<const f32x4*>(f), x1 = *reinterpret_cast<const f32x4*>(f + 4);
       for (int j = 0; j < 8; ++j) {
         float x = j < 4 ? x0[j] : x1[j - 4];
-        if (a) x = fmaxf(sa[j] * x + sb[j], 0.0f);
+        if constexpr (LAYER) { if (a) x = fmaxf(sa[j] * ((x - mean) * inv) + sb[j], 0.0f); }
+        else if (a) x = fmaxf(sa[j] * x + sb[j], 0.0f);
         out[nt][j] = static_cast<__bf16>(x);
       }
     }
@@ -136,15 +151,27 @@ __global__ __launch_bounds__(NTH) void k_leafnet_dense(DnDesc d, DnPtrs w, const
     const int Ci = d.C_in + d.G * i, KS1 = round_up(Ci, 32) / 32;
     const float* a1 = reinterpret_cast<const float*>(blk);
     const float* b1 = a1 + d.CFP;
-    const float* c1 = b1 + d.CFP;
-    const uint8_t* w1 = reinterpret_cast<const uint8_t*>(c1 + 64);
+    const float* c1 = b1 + d.CFP;                                // LAYER: g2[64], then b2[64]
+    const uint8_t* w1 = reinterpret_cast<const uint8_t*>(c1 + (LAYER ? 128 : 64));
+    float mean1 = 0.0f, inv1 = 1.0f;
+    if constexpr (LAYER) {  // bn1: the C_i raw features of the 42 pixels, nothing of the padding behind them
+      const float cnt = static_cast<float>(PIX * Ci);
+      float s = 0.0f;
+      for (int p = 0; p < PIX; ++p) for (int c = lane; c < Ci; c += 64) s += feat[p * FP + c];
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+      mean1 = s / cnt;
+      float qq = 0.0f;
+      for (int p = 0; p < PIX; ++p) for (int c = lane; c < Ci; c += 64) { const float dx = feat[p * FP + c] - mean1; qq += dx * dx; }
+      for (int off = 32; off > 0; off >>= 1) qq += __shfl_xor(qq, off, 64);
+      inv1 = 1.0f / sqrtf(qq / cnt + 1e-5f);
+    }
     const uint8_t* w2 = w1 + static_cast<size_t>(KS1) * MT1 * WFRAG_BYTES;
     {  // bottleneck 1x1: mid = bf16(relu(W1 act(feat) + c1))
       f32x4 acc[4][3];
       for (int mt = 0; mt < 4; ++mt) for (int nt = 0; nt < 3; ++nt) acc[mt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       for (int ks = 0; ks < KS1; ++ks) {
         bf16x8 b[3];
-        feat_frags(ks, a1, b1, b);
+        feat_frags(ks, a1, b1, b, mean1, inv1);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
           if (mt < MT1) {
@@ -153,15 +180,48 @@ __global__ __launch_bounds__(NTH) void k_leafnet_dense(DnDesc d, DnPtrs w, const
           }
         }
       }
+      float mean2 = 0.0f, inv2 = 1.0f;
+      if constexpr (LAYER) {  // bn2: the accumulators of rows < 4G and real pixel columns, before the epilogue rounds
+        const int M4 = 4 * d.G;
+        const float cnt = static_cast<float>(M4 * PIX);
+        // 0 / 1 weights in registers, not branches: an element counts where it is a real row (16 mt + 4 q + r < 4G, that is
+        // 4 mt + q < G for every r; tiles mt >= MT1 fail it) and a real pixel
+        float wt[4][3];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+          for (int nt = 0; nt < 3; ++nt) wt[mt][nt] = (4 * mt + q < d.G && nt * 16 + col < PIX) ? 1.0f : 0.0f;
+        float s = 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+          for (int nt = 0; nt < 3; ++nt)
+            for (int r = 0; r < 4; ++r) s += wt[mt][nt] * acc[mt][nt][r];
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        mean2 = s / cnt;
+        float qq = 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+          for (int nt = 0; nt < 3; ++nt)
+            for (int r = 0; r < 4; ++r) {
+              const float dx = acc[mt][nt][r] - mean2;
+              qq += wt[mt][nt] * (dx * dx);
+            }
+        for (int off = 32; off > 0; off >>= 1) qq += __shfl_xor(qq, off, 64);
+        inv2 = 1.0f / sqrtf(qq / cnt + 1e-5f);
+      }
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
         if (mt < MT1) {
           const int m0 = 16 * mt + 4 * q;                      // D: row = 4 * (lane >> 4) + r, column = lane & 15
-          const f32x4 bias = *reinterpret_cast<const f32x4*>(c1 + m0);
+          const f32x4 bias = *reinterpret_cast<const f32x4*>(c1 + (LAYER ? 64 : 0) + m0);
+          f32x4 gain = f32x4{1.0f, 1.0f, 1.0f, 1.0f};
+          if constexpr (LAYER) gain = *reinterpret_cast<const f32x4*>(c1 + m0);
           for (int nt = 0; nt < 3; ++nt) {
             if (nt * 16 + col < PIX) {
               bf16x4 o;
-              for (int r = 0; r < 4; ++r) o[r] = static_cast<__bf16>(fmaxf(acc[mt][nt][r] + bias[r], 0.0f));
+              for (int r = 0; r < 4; ++r) {
+                if constexpr (LAYER) o[r] = static_cast<__bf16>(fmaxf(gain[r] * ((acc[mt][nt][r] - mean2) * inv2) + bias[r], 0.0f));
+                else o[r] = static_cast<__bf16>(fmaxf(acc[mt][nt][r] + bias[r], 0.0f));
+              }
               *reinterpret_cast<bf16x4*>(mid + cell[nt] * MP + m0) = o;
             }
           }
@@ -190,7 +250,7 @@ __global__ __launch_bounds__(NTH) void k_leafnet_dense(DnDesc d, DnPtrs w, const
             if (4 * q + r < d.G) feat[px[nt] * FP + Ci + 4 * q + r] = acc[nt][r];
     }
     __syncthreads();
-    blk += block_bytes(d, i);
+    blk += block_bytes(d, i, LAYER);
   }
 
   {  // heads' 1x1 over every raw feature: hbuf[m][p] = relu(Wh feat + bh)   (mid is dead: the last block's reads are behind the barrier)

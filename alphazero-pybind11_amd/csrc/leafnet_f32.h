@@ -9,9 +9,12 @@
 namespace azmi_f32 {
 // dense: DenseNet trunk (azmi_net_desc2::dense_net), d->channels = the growth rate.  Bounds: kernel_size 3 (a dense trunk: 1 / 3 / 5 / 7), pooled
 // heads, any widths and depth (a dense trunk: depth >= 1); everything else is refused by name.
-size_t blob_bytes(const azmi_net_desc* d, bool dense);
+// Variant: the words of azmi_net_desc2 behind dense_net - trunk_norm (0 batch, 1 layer = GroupNorm(1, C)), trunk_act (0 relu, 1 crelu),
+// pi_fc_layers (hidden layers of the flat policy head, d->pi_hidden wide).  All zero: the image and the launches of the first descriptor.
+struct Variant { int trunk_norm = 0, trunk_act = 0, pi_fc_layers = 0; };
+size_t blob_bytes(const azmi_net_desc* d, bool dense, Variant var = Variant{});
 // returns AZMI_OK or a negative status; *err receives a static/thread-local message
-int create(const azmi_net_desc* d, bool dense, const void* blob, size_t bytes, int device, void** impl, const char** err);
+int create(const azmi_net_desc* d, bool dense, const void* blob, size_t bytes, int device, void** impl, const char** err, Variant var = Variant{});
 int forward(void* impl, const float* canon, float* v, float* pi, uint32_t batch, void* stream, const char** err);
 int reserve(void* impl, uint32_t batch, const char** err);
 void destroy(void* impl);

@@ -753,10 +753,27 @@ int azmi_net_create(const azmi_net_desc* desc, const void* blob, size_t blob_byt
  *                   precision 2, is AZMI_ERR_INVALID with a message naming precision='fp32'.
  *                   precision 1: any dense shape (every head the fp32 path has), kernel_size 1, 3, 5 or 7 for the trunk and the
  *                   extra head convolutions.
+ *   trunk_norm      0 = nn.BatchNorm2d on every trunk norm (folded on the host), 1 = "layer": nn.GroupNorm(1, C) (NNArgs.trunk_norm,
+ *                   neural_net.py:166-180) - mean and biased variance per sample over (C, H, W), eps 1e-5, then a per-channel weight
+ *                   and bias; the ResNet stem's norm and bn1 / bn2 of every block.  The heads keep their folded BatchNorms.
+ *   trunk_act       0 = ReLU, 1 = "crelu": cat(relu(x), relu(-x)) (NNArgs.trunk_act, neural_net.py:183-208) in front of both
+ *                   convolutions of every block, whose weights then have twice the input channels.
+ *   pi_fc_layers    L >= 0 (NNArgs.pi_fc_layers, neural_net.py:431-442; flat policy head only: policy_channels must be 0): L > 0
+ *                   puts Linear(HC*H*W, pi_hidden) - ReLU - (L-1) x (Linear(pi_hidden, pi_hidden) - ReLU) -
+ *                   Linear(pi_hidden, num_moves) in place of the single projection; base.pi_hidden carries its width.
+ *                   With any of these three set, dense_net = 0 does NOT forward to azmi_net_create: the second entry handles the
+ *                   ResNet trunk itself.  They run on precision 1 (every combination, both trunks, all policy heads; image in
+ *                   csrc/leafnet_f32.hip).  On the matrix cores: dense_net = 1, precision 0, trunk_norm = 1 with trunk_act = 0 and
+ *                   pi_fc_layers = 0 is the layer-norm instance of the dense Connect4 tile (csrc/leafnet_dense.h; the batch
+ *                   instance's bounds; per-board statistics by wave-local reductions).  Everything else on precision 0 / 2 is
+ *                   AZMI_ERR_INVALID with a message naming precision='fp32': the ResNet tiles are built around folded BatchNorms,
+ *                   the dense tile's LDS plan has no room for crelu's doubled K, and pi_fc_layers > 0 is REFUSED on every tile (the
+ *                   dense tile was not given the fp32 stack behind its heads).  A value out of range is AZMI_ERR_INVALID.
+ *                   All three zero: both entries behave exactly as before these words had names.
  *   reserved        must be zero (AZMI_ERR_INVALID otherwise; blob_bytes2 returns 0).
  * A dense net runs everywhere an azmi_net does except the asynchronous pipeline, which hard-wires the Connect4 ResNet tile:
  * azmi_pipeline_supported(_groups) return 0 with it and azmi_run_pipeline(_groups) refuse it. */
-typedef struct azmi_net_desc2 { azmi_net_desc base; int32_t dense_net; int32_t reserved[7]; } azmi_net_desc2;
+typedef struct azmi_net_desc2 { azmi_net_desc base; int32_t dense_net; int32_t trunk_norm, trunk_act, pi_fc_layers; int32_t reserved[4]; } azmi_net_desc2;
 size_t azmi_net_blob_bytes2(const azmi_net_desc2* desc);
 int azmi_net_create2(const azmi_net_desc2* desc, const void* blob, size_t blob_bytes, int device, azmi_net** out);
 void azmi_net_destroy(azmi_net* net);
