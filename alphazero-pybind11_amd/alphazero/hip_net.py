@@ -60,7 +60,7 @@ class NetDesc2C(C.Structure):
 
 def is_variant(spec):
     """what only the second descriptor can say: layer norm, crelu, the policy FC stack.  The fp32 tier runs them all; the dense
-    Connect4 tile has a layer-norm instance (relu, no FC stack), no other tile takes any."""
+    Connect4 tile has a layer-norm instance (relu, no FC stack), no other tile - the dense spatial one included - takes any."""
     return spec.trunk_norm != "batch" or spec.trunk_act != "relu" or spec.pi_fc_layers > 0
 
 
@@ -353,6 +353,77 @@ def fold_dense(net):
     return desc, bytes(blob)
 
 
+def fold_dense_spatial(net):
+    """The dense spatial-head family on the matrix cores (csrc/leafnet_dense_sp.h; bf16 operands): the single-variant StarGambit
+    configs and their neighbours - 7x7, 11x11 or 13x13, spatial policy head with up to 32 channels and up to 32 global actions,
+    kernel_size 3 or 5, growth G <= 16, C_in + G*depth <= 128, head_channels 32.  The blocks are laid out exactly as fold_dense
+    lays them out (the same fragments, the same exact zeros in every padding).  The heads' 1x1 has split operands:
+      heads    bh[64] f32 | frag[CFP/32][4] of the bf16 high parts of Wh | frag[CFP/32][4] of the low parts (Wh - high, in bf16)
+    and behind it, all f32:
+      v_fc1 W[Hd][32] b[Hd] | v_fc2 W[P+1][Hd] b[P+1] | pi_conv2 W[32][32] b[32] (pi_bn2 folded; rows >= policy channels zero)
+      with global actions: pi_global.0 W[Hp][32] b[Hp] | pi_global.2 W[NG][Hp] b[NG] | LayerNorm g[NG] b[NG]   (torch layouts)"""
+    spec = net.spec
+    Cin, H, W = spec.in_shape
+    G, D, K = spec.num_channels, spec.depth, spec.kernel_size
+    tail = "; use precision='fp32' for other shapes"
+    # the bounds of azmi_net_create2 (csrc/leafnet.hip dense_sp_refusal), with its messages
+    if spec.trunk_act != "relu" or spec.pi_fc_layers > 0:
+        raise RuntimeError("dense leaf net kernel: trunk_act='relu' and pi_fc_layers=0 only; use precision='fp32' for crelu and the policy FC stack")
+    if spec.trunk_norm != "batch":
+        raise RuntimeError("dense spatial leaf net kernel: trunk_norm='batch' only (the layer-norm instance is the dense Connect4 tile's); "
+                           "use precision='fp32' for layer-norm nets")
+    pc = spec.policy_shape[0]
+    NG = spec.num_moves - pc * H * W
+    if (H, W) not in ((7, 7), (11, 11), (13, 13)):
+        raise RuntimeError("dense spatial leaf net kernel covers 7x7, 11x11 and 13x13 boards" + tail)
+    if K not in (3, 5):
+        raise RuntimeError("dense spatial leaf net kernel: kernel_size 3 or 5" + tail)
+    if not 1 <= G <= 16:
+        raise RuntimeError("dense spatial leaf net kernel: growth rate (channels) 1..16" + tail)
+    if D < 1 or Cin < 1:
+        raise RuntimeError("dense spatial leaf net kernel: at least one block and one input plane" + tail)
+    if Cin + G * D > 128:
+        raise RuntimeError("dense spatial leaf net kernel: in_channels + channels * depth <= 128" + tail)
+    if not (spec.head_channels == 32 and spec.head_pool and spec.v_head_convs == 0 and spec.pi_head_convs == 0 and spec.v_fc_layers == 1):
+        raise RuntimeError("dense spatial leaf net kernel: 32 head channels, pooled heads, no extra head convolutions, one value FC layer" + tail)
+    if not (1 <= pc <= 32 and 0 <= NG <= 32):
+        raise RuntimeError("dense spatial leaf net kernel: policy channels 1..32, 0..32 global actions" + tail)
+    Hp = spec.pi_fc_hidden if NG > 0 else 0
+    if NG > 0 and not (16 <= Hp <= 256 and Hp % 16 == 0):
+        raise RuntimeError("dense spatial leaf net kernel: pi_hidden must be a multiple of 16 in 16..256 with global actions" + tail)
+    if not (16 <= spec.v_fc_hidden <= 256 and spec.v_fc_hidden % 16 == 0 and 1 <= spec.num_players <= 3):
+        raise RuntimeError("dense spatial leaf net kernel: head sizes out of range (v_hidden: a multiple of 16, at most 256; 1..3 players)" + tail)
+    sd = {k: v.detach().double().cpu() for k, v in net.state_dict().items()}
+    CF = Cin + G * D
+    CFP, M1, K2 = _up(CF, 32), _up(4 * G, 16), _up(4 * G, 32)
+    blob = bytearray()
+    for i, blk in enumerate(net.conv_layers):
+        Ci = Cin + G * i
+        a1, b1 = (t.cpu() for t in bn_affine(blk.bn1))
+        a2, b2 = (t.cpu() for t in bn_affine(blk.bn2))
+        blob += _f32(_pad(a1, CFP)) + _f32(_pad(b1, CFP)) + _f32(_pad(b2, 64))
+        blob += _frags(_pad(sd[f"conv_layers.{i}.conv1.weight"][:, :, 0, 0] * a2[:, None], M1, _up(Ci, 32)).numpy())
+        w2 = sd[f"conv_layers.{i}.conv2.weight"]                     # [G][4G][K][K]
+        for dy in range(K):
+            for dx in range(K):
+                blob += _frags(_pad(w2[:, :, dy, dx], 16, K2).numpy())
+    av, bv = (t.cpu() for t in bn_affine(net.v_bn))
+    ap, bp = (t.cpu() for t in bn_affine(net.pi_bn))
+    wh = torch.cat([sd["v_conv.weight"][:, :, 0, 0] * av[:, None], sd["pi_conv.weight"][:, :, 0, 0] * ap[:, None]], 0)
+    wh = _pad(wh, 64, CFP)
+    wh_hi = wh.float().to(torch.bfloat16).double()
+    blob += _f32(torch.cat([bv, bp])) + _frags(wh_hi.numpy()) + _frags((wh - wh_hi).numpy())
+    blob += _f32(sd["v_fc1.weight"]) + _f32(sd["v_fc1.bias"]) + _f32(sd["v_fc2.weight"]) + _f32(sd["v_fc2.bias"])
+    a2, b2 = (t.cpu() for t in bn_affine(net.pi_bn2))
+    blob += _f32(_pad(sd["pi_conv2.weight"][:, :, 0, 0] * a2[:, None], 32, 32)) + _f32(_pad(b2, 32))
+    if NG > 0:
+        for k in ("pi_global.0.weight", "pi_global.0.bias", "pi_global.2.weight", "pi_global.2.bias", "pi_global.3.weight", "pi_global.3.bias"):
+            blob += _f32(sd[k])
+    desc = NetDesc2C(NetDescC(Cin, H, W, G, D, K, 32, spec.v_fc_hidden, spec.num_moves, spec.num_players, 0, 0, 1, pc, 0, Hp), 1)
+    assert len(blob) == blob_bytes(desc), (len(blob), blob_bytes(desc))
+    return desc, bytes(blob)
+
+
 def _split_frags(wmat, passes=("hi", "hi", "lo")):
     """wmat [64][K] (K = 64 * taps) -> the bf16x3 weight stream of one convolution: per tap (two k-steps = one 8 KB chunk) the
     high parts' fragments, the high parts' again, the low parts' (w = hi + lo; csrc/leafnet_c4.h SPLIT: the three chunks meet
@@ -373,7 +444,8 @@ def fold(net, precision="bf16"):
     """LeafNet (reference NNArch parameter names) -> (NetDescC or NetDesc2C, blob bytes).  precision: "bf16" (bf16 MFMA operands),
     "bf16x3" (weights and activations as bf16 high + low parts, three MFMAs per product - the 1e-5 tier on the matrix cores; the
     Connect4 family and, since round 4, the spatial-head nets) or "fp32" (plain fp32 kernels, any shape).  A dense trunk
-    (spec.dense_net) has the "bf16" tile of fold_dense and "fp32".  trunk_norm="layer", trunk_act="crelu" and pi_fc_layers > 0
+    (spec.dense_net) has the "bf16" tiles of fold_dense (6x7, flat policy head) and fold_dense_spatial (7x7 / 11x11 / 13x13, spatial
+    policy head) and "fp32".  trunk_norm="layer", trunk_act="crelu" and pi_fc_layers > 0
     have "fp32"; a dense trunk with trunk_norm="layer" alone also has the "bf16" tile; everything else raises RuntimeError naming
     precision='fp32'."""
     if precision == "fp32":
@@ -390,6 +462,8 @@ def fold(net, precision="bf16"):
     if spec.dense_net:
         if x3:
             raise RuntimeError("dense leaf net: no bf16x3 tier; the 1e-5 tier of dense nets is precision='fp32'")
+        if spec.policy_shape is not None and tuple(spec.in_shape[1:]) != (6, 7):   # (a spatial head ON 6x7: the Connect4 tile's refusal)
+            return fold_dense_spatial(net)
         return fold_dense(net)
     if spec.policy_shape is not None:
         return fold_spatial(net, x3)

@@ -16,7 +16,9 @@ Covered: both trunks - the ResNet one (`dense_net=False`, what BASELINE.json's c
 `kernel_size` in 1..7 (the HIP tiers: 3, and 1 / 5 / 7 on dense trunks), the value head, the flat policy head with or without
 its FC stack (`pi_fc_layers`: pi_fc1 - ReLU - pi_fc_extra - pi_fc_out) and the spatial policy head.  The eight norm x activation x
 trunk combinations all run on the fp32 tier (csrc/leafnet_f32.hip); of the matrix-core tiles the dense Connect4 one also takes
-`trunk_norm="layer"` (csrc/leafnet_dense.h), the others keep batch / relu / no FC stack.
+`trunk_norm="layer"` (csrc/leafnet_dense.h), the others keep batch / relu / no FC stack.  A dense trunk has two bf16 tiles: the
+Connect4 family (6x7, flat policy head) and the spatial-head family on 7x7 / 11x11 / 13x13 (csrc/leafnet_dense_sp.h:
+`stargambit_dense_spec()` on the unified canvas, `stargambit_variant_dense_spec(v)` in the four single-variant games' own shapes).
 NOT covered: `head_pool=False` builds in torch but no HIP tier takes it; a spatial head has no FC stack (the reference's
 `spatial_policy="auto"` falls back to the flat head then: here the caller leaves `policy_shape` out).
 """
@@ -239,6 +241,17 @@ def stargambit_dense_spec(depth=4, channels=16, kernel_size=3, head_channels=32)
     spatial head over the 13 x 13 canvas + 19 global actions."""
     return NetSpec(in_shape=(36, 13, 13), num_moves=1709, num_players=2, num_channels=channels, depth=depth,
                    kernel_size=kernel_size, head_channels=head_channels, policy_shape=(10, 13, 13), dense_net=True)
+
+
+def stargambit_variant_dense_spec(variant, depth=4, channels=16, kernel_size=3, head_channels=32):
+    """configs/star_gambit_{skirmish,showdown,clash,battle}.yaml (variant 0..3) in the game's OWN shapes
+    (games.StarGambit{Skirmish,Showdown,Clash,Battle}GS): 32 planes on 11 x 11 (variants 0-2) or 13 x 13 (Battle), the dense
+    default, spatial head with 10 channels + 19 global actions."""
+    if variant not in (0, 1, 2, 3):
+        raise ValueError("variant must be 0 (Skirmish), 1 (Showdown), 2 (Clash) or 3 (Battle)")
+    d = 13 if variant == 3 else 11
+    return NetSpec(in_shape=(32, d, d), num_moves=10 * d * d + 19, num_players=2, num_channels=channels, depth=depth,
+                   kernel_size=kernel_size, head_channels=head_channels, policy_shape=(10, d, d), dense_net=True)
 
 
 def tawlbwrdd_spec(depth=4):

@@ -18,7 +18,9 @@
 //   * leafnet_sp.h - the spatial-policy-head nets (Tafl family, StarGambit).
 // and a third for the reference's DEFAULT trunk (dense_net, azmi_net_create2):
 //   * leafnet_dense.h - the dense Connect4 family (6x7, 3x3 / 5x5, flat policy head): one wavefront per board, every raw
-//     feature in LDS.
+//     feature in LDS;
+//   * leafnet_dense_sp.h - the dense spatial-head family (7x7 / 11x11 / 13x13, the single-variant StarGambit configs): one
+//     workgroup per board.
 // This file is the host side behind azmi_net_* (include/azmi.h): validation of the descriptor, the weight image on the
 // device, launches.  The fp32 correctness path lives in leafnet_f32.hip.
 #include <hip/hip_runtime.h>
@@ -37,6 +39,7 @@
 #include "leafnet_c4.h"
 #include "leafnet_sp.h"
 #include "leafnet_dense.h"
+#include "leafnet_dense_sp.h"
 
 namespace {
 
@@ -60,8 +63,12 @@ struct azmi_net {
   bool spatial = false;      // spatial policy head (Tafl family, StarGambit): sp::k_leafnet_sp
   bool dense = false;        // DenseNet trunk on the matrix cores (dense Connect4 family): dn::k_leafnet_dense
   bool dense_layer = false;  // ... its trunk_norm = layer instance (k_leafnet_dense<true>)
+  bool dense_sp = false;     // ... the dense spatial-head family: dsp::k_leafnet_dense_sp (dense stays false)
   dn::DnDesc dd{};
   dn::DnPtrs dp{};
+  dsp::DspDesc xd{};
+  dsp::DspPtrs xp{};
+  int x_board = 0, x_k = 0;  // ... its instance: board edge (7 / 11 / 13) and kernel size (3 / 5)
   sp::SpDesc sd{};
   sp::SpPtrs sp{};
   uint32_t sp_tbw = 0;       // boards per workgroup of the instantiated tile
@@ -136,6 +143,65 @@ const char* dense_refusal(const azmi_net_desc* d) {
     return "dense leaf net kernel: head sizes out of range (v_hidden: a multiple of 16, at most 256; 1..3 players; 1..16 moves); use precision='fp32' for other shapes";
   return nullptr;
 }
+// Which dense tile a bf16 descriptor is for: the spatial one takes every spatial head off the 6x7 board (a spatial head ON 6x7 is
+// refused by the Connect4 tile's own words, as it always was)
+bool dense_sp_family(const azmi_net_desc* d) { return d->policy_channels > 0 && !(d->height == dn::BH && d->width == dn::BW); }
+int dense_sp_globals(const azmi_net_desc* d) { return d->num_moves - d->policy_channels * d->height * d->width; }
+// The bounds of the dense spatial tile (leafnet_dense_sp.h), stated once: NULL when `d` is inside them, else what is outside
+const char* dense_sp_refusal(const azmi_net_desc* d) {
+  const bool board = d->height == d->width && (d->height == 7 || d->height == 11 || d->height == 13);
+  if (!board) return "dense spatial leaf net kernel covers 7x7, 11x11 and 13x13 boards; use precision='fp32' for other shapes";
+  if (d->kernel_size != 3 && d->kernel_size != 5) return "dense spatial leaf net kernel: kernel_size 3 or 5; use precision='fp32' for other shapes";
+  if (d->channels < 1 || d->channels > dn::MAX_G) return "dense spatial leaf net kernel: growth rate (channels) 1..16; use precision='fp32' for other shapes";
+  if (d->depth < 1 || d->in_channels < 1) return "dense spatial leaf net kernel: at least one block and one input plane; use precision='fp32' for other shapes";
+  if (static_cast<long long>(d->in_channels) + static_cast<long long>(d->channels) * d->depth > dn::MAX_CF)
+    return "dense spatial leaf net kernel: in_channels + channels * depth <= 128; use precision='fp32' for other shapes";
+  if (d->head_channels != dsp::HC1 || d->v_head_convs != 0 || d->pi_head_convs != 0 || d->v_fc_layers != 1)
+    return "dense spatial leaf net kernel: 32 head channels, no extra head convolutions, one value FC layer; use precision='fp32' for other shapes";
+  if (d->policy_channels < 1 || d->policy_channels > dsp::MAX_PC || dense_sp_globals(d) < 0 || dense_sp_globals(d) > dsp::MAX_NG)
+    return "dense spatial leaf net kernel: policy channels 1..32, 0..32 global actions; use precision='fp32' for other shapes";
+  if (dense_sp_globals(d) > 0 && (d->pi_hidden < 16 || d->pi_hidden > dsp::MAX_HID || d->pi_hidden % 16))
+    return "dense spatial leaf net kernel: pi_hidden must be a multiple of 16 in 16..256 with global actions; use precision='fp32' for other shapes";
+  if (d->v_hidden < 16 || d->v_hidden > dsp::MAX_HID || d->v_hidden % 16 || d->num_players < 1 || d->num_players > 3)
+    return "dense spatial leaf net kernel: head sizes out of range (v_hidden: a multiple of 16, at most 256; 1..3 players); use precision='fp32' for other shapes";
+  return nullptr;
+}
+const char* kLayerOnDenseSp = "dense spatial leaf net kernel: trunk_norm='batch' only (the layer-norm instance is the dense Connect4 tile's); "
+                              "use precision='fp32' for layer-norm nets";
+dsp::DspDesc dense_sp_desc(const azmi_net_desc* d) {
+  const int cf = d->in_channels + d->channels * d->depth, ng = dense_sp_globals(d);
+  return dsp::DspDesc{d->in_channels, d->channels, d->depth, cf, dn::round_up(cf, 32), d->num_moves, d->num_players, d->v_hidden,
+                      d->policy_channels, ng, ng > 0 ? d->pi_hidden : 0};
+}
+size_t dense_sp_blob_bytes(const azmi_net_desc* d) {
+  const dn::DnDesc dd = dense_desc(d);
+  const size_t Hd = d->v_hidden, P1 = d->num_players + 1, ng = dense_sp_globals(d), Hp = d->pi_hidden;
+  size_t n = 0;
+  for (int i = 0; i < dd.depth; ++i) n += dn::block_bytes(dd, i);
+  n += dsp::HEADCH * 4 + 2 * static_cast<size_t>(dd.CFP / 32) * 4 * WFRAG_BYTES;      // (high and low parts)
+  n += (Hd * dsp::HC1 + Hd + P1 * Hd + P1) * 4;
+  n += (static_cast<size_t>(dsp::MAX_PC) * dsp::HC1 + dsp::MAX_PC) * 4;
+  if (ng > 0) n += (Hp * dsp::HC1 + Hp + ng * Hp + 3 * ng) * 4;
+  return n;
+}
+size_t dense_sp_lds(const azmi_net_desc* d, int cfp) {
+  return d->height == 7 ? dsp::Geo7::lds_bytes(cfp) : d->height == 11 ? dsp::Geo11::lds_bytes(cfp) : dsp::Geo13::lds_bytes(cfp);
+}
+template <typename GEO>
+const void* dense_sp_kernel_of(int k) {
+  return k == 3 ? reinterpret_cast<const void*>(&dsp::k_leafnet_dense_sp<GEO, 3>) : reinterpret_cast<const void*>(&dsp::k_leafnet_dense_sp<GEO, 5>);
+}
+const void* dense_sp_kernel(const azmi_net_desc* d) {
+  return d->height == 7 ? dense_sp_kernel_of<dsp::Geo7>(d->kernel_size)
+                        : d->height == 11 ? dense_sp_kernel_of<dsp::Geo11>(d->kernel_size) : dense_sp_kernel_of<dsp::Geo13>(d->kernel_size);
+}
+template <typename GEO>
+void dense_sp_launch(azmi_net* net, const float* canon, float* v, float* pi, uint32_t rows_max, const uint32_t* rows, const uint32_t* row_count,
+                     hipStream_t st) {
+  const uint32_t tiles = (rows_max + dsp::TBW - 1) / dsp::TBW;
+  if (net->x_k == 3) dsp::k_leafnet_dense_sp<GEO, 3><<<tiles, dsp::NTH, net->lds_bytes, st>>>(net->xd, net->xp, canon, v, pi, rows_max, rows, row_count);
+  else dsp::k_leafnet_dense_sp<GEO, 5><<<tiles, dsp::NTH, net->lds_bytes, st>>>(net->xd, net->xp, canon, v, pi, rows_max, rows, row_count);
+}
 size_t dense_blob_bytes(const azmi_net_desc* d, bool layer = false) {
   const dn::DnDesc dd = dense_desc(d);
   size_t n = 0;
@@ -179,6 +245,7 @@ void net_dims(const azmi_net* net, uint32_t* chw, uint32_t* p1, uint32_t* m) {
   if (net->f32) azmi_f32::dims(net->f32, chw, p1, m);
   else if (net->spatial) { *chw = net->sd.C_in * net->sd.H * net->sd.W; *p1 = net->sd.num_players + 1; *m = net->sd.num_moves; }
   else if (net->dense) { *chw = net->dd.C_in * dn::PIX; *p1 = net->dd.num_players + 1; *m = net->dd.num_moves; }
+  else if (net->dense_sp) { *chw = net->xd.C_in * net->x_board * net->x_board; *p1 = net->xd.num_players + 1; *m = net->xd.num_moves; }
   else { *chw = net->nd.C_in * net->nd.H * net->nd.W; *p1 = net->nd.num_players + 1; *m = net->nd.num_moves; }
 }
 // weight image of a spatial net (alphazero/hip_net.py fold_spatial): the chunk stream | the fp32 parameters of the tower and
@@ -345,13 +412,56 @@ int azmi_net_create(const azmi_net_desc* d, const void* blob, size_t blob_bytes,
   return AZMI_OK;
 }
 
+// the dense spatial-head family (leafnet_dense_sp.h): precision 0, batch / relu words already checked by the caller
+static int dense_sp_create(const azmi_net_desc* d, const void* blob, size_t blob_bytes, int device, azmi_net** out) {
+  if (const char* why = dense_sp_refusal(d)) return nfail(AZMI_ERR_INVALID, "%s", why);
+  if (blob_bytes != dense_sp_blob_bytes(d)) return nfail(AZMI_ERR_INVALID, "weight blob is %zu bytes, expected %zu", blob_bytes, dense_sp_blob_bytes(d));
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return nfail(AZMI_ERR_NO_DEVICE, "no HIP device: libazmi has no CPU path");
+  if (hipSetDevice(device) != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "hipSetDevice failed");
+  auto net = new azmi_net();
+  net->device = device; net->dense_sp = true;
+  net->xd = dense_sp_desc(d);
+  net->x_board = d->height; net->x_k = d->kernel_size;
+  if (hipMalloc(&net->blob, blob_bytes) != hipSuccess) { delete net; return nfail(AZMI_ERR_OOM, "hipMalloc(weights) failed"); }
+  if (hipMemcpy(net->blob, blob, blob_bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(net->blob); delete net; return nfail(AZMI_ERR_NO_DEVICE, "weight upload failed"); }
+  net->blob_bytes = blob_bytes;
+  const uint8_t* p = static_cast<const uint8_t*>(net->blob);
+  auto f32p = [&](size_t count) { const float* q = reinterpret_cast<const float*>(p); p += count * 4; return q; };
+  const dn::DnDesc dd = dense_desc(d);
+  const dsp::DspDesc& xd = net->xd;
+  dsp::DspPtrs& xp = net->xp;
+  xp.blocks = p;
+  for (int i = 0; i < dd.depth; ++i) p += dn::block_bytes(dd, i);
+  xp.head_b = f32p(dsp::HEADCH);
+  xp.head_w = p; p += 2 * static_cast<size_t>(dd.CFP / 32) * 4 * WFRAG_BYTES;
+  xp.v_fc1_w = f32p(static_cast<size_t>(xd.v_hidden) * dsp::HC1); xp.v_fc1_b = f32p(xd.v_hidden);
+  xp.v_fc2_w = f32p(static_cast<size_t>(xd.num_players + 1) * xd.v_hidden); xp.v_fc2_b = f32p(xd.num_players + 1);
+  xp.pol_w = f32p(dsp::MAX_PC * dsp::HC1); xp.pol_b = f32p(dsp::MAX_PC);
+  if (xd.num_global > 0) {
+    xp.pg1_w = f32p(static_cast<size_t>(xd.pi_hidden) * dsp::HC1); xp.pg1_b = f32p(xd.pi_hidden);
+    xp.pg2_w = f32p(static_cast<size_t>(xd.num_global) * xd.pi_hidden); xp.pg2_b = f32p(xd.num_global);
+    xp.pg_ln_g = f32p(xd.num_global); xp.pg_ln_b = f32p(xd.num_global);
+  }
+  net->lds_bytes = dense_sp_lds(d, xd.CFP);
+  // an instance is shared by every net of its board and kernel size: the attribute is what the widest accepted net asks for
+  if (hipFuncSetAttribute(dense_sp_kernel(d), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(dense_sp_lds(d, dn::MAX_CF))) != hipSuccess) {
+    (void)hipFree(net->blob); delete net;
+    return nfail(AZMI_ERR_NO_DEVICE, "cannot reserve %zu bytes of LDS", net->lds_bytes);
+  }
+  *out = net;
+  return AZMI_OK;
+}
+
 size_t azmi_net_blob_bytes2(const azmi_net_desc2* d) {
   if (!d || !reserved_zero(d) || variant_refusal(d)) return 0;
-  if (tile_layer(d)) return !dense_refusal(&d->base) ? dense_blob_bytes(&d->base, true) : 0;
+  if (tile_layer(d)) return !dense_sp_family(&d->base) && !dense_refusal(&d->base) ? dense_blob_bytes(&d->base, true) : 0;
   if (is_variant(d)) return d->base.precision == 1 && (d->dense_net == 0 || d->dense_net == 1) ? azmi_f32::blob_bytes(&d->base, d->dense_net == 1, f32_variant(d)) : 0;
   if (!d->dense_net) return azmi_net_blob_bytes(&d->base);
   if (d->base.precision == 1) return azmi_f32::blob_bytes(&d->base, true);
-  return d->base.precision == 0 && !dense_refusal(&d->base) ? dense_blob_bytes(&d->base) : 0;
+  if (d->base.precision != 0) return 0;
+  if (dense_sp_family(&d->base)) return !dense_sp_refusal(&d->base) ? dense_sp_blob_bytes(&d->base) : 0;
+  return !dense_refusal(&d->base) ? dense_blob_bytes(&d->base) : 0;
 }
 
 int azmi_net_create2(const azmi_net_desc2* d2, const void* blob, size_t blob_bytes, int device, azmi_net** out) {
@@ -369,6 +479,10 @@ int azmi_net_create2(const azmi_net_desc2* d2, const void* blob, size_t blob_byt
   if (d->precision == 1) return f32_create(d, true, blob, blob_bytes, device, out);
   if (d->precision == 2) return nfail(AZMI_ERR_INVALID, "dense leaf net: no bf16x3 tier; the 1e-5 tier of dense nets is precision='fp32'");
   if (d->precision != 0) return nfail(AZMI_ERR_INVALID, "precision must be 0 (bf16 MFMA) or 1 (fp32) for a dense net");
+  if (dense_sp_family(d)) {
+    if (layer) return nfail(AZMI_ERR_INVALID, "%s", kLayerOnDenseSp);
+    return dense_sp_create(d, blob, blob_bytes, device, out);
+  }
   if (const char* why = dense_refusal(d)) return nfail(AZMI_ERR_INVALID, "%s", why);
   if (blob_bytes != dense_blob_bytes(d, layer)) return nfail(AZMI_ERR_INVALID, "weight blob is %zu bytes, expected %zu", blob_bytes, dense_blob_bytes(d, layer));
   int ndev = 0;
@@ -409,7 +523,7 @@ void azmi_net_destroy(azmi_net* net) {
     net->free_scratch();
     azmi_f32::destroy(net->f32); delete net; return;
   }
-  // spatial, dense and Connect4 tiles alike: the weight image and the per-stream scratch
+  // spatial, both dense and Connect4 tiles alike: the weight image and the per-stream scratch
   (void)hipSetDevice(net->device);
   (void)hipFree(net->blob);
   net->free_scratch();
@@ -445,6 +559,15 @@ static int dense_forward(azmi_net* net, const float* canon, float* v, float* pi,
   else dn::k_leafnet_dense<false><<<tiles, dn::NTH, net->lds_bytes, st>>>(net->dd, net->dp, canon, v, pi, rows_max, rows, row_count);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "k_leafnet_dense launch: %s", hipGetErrorString(e));
+  return AZMI_OK;
+}
+static int dense_sp_forward(azmi_net* net, const float* canon, float* v, float* pi, uint32_t rows_max, const uint32_t* rows, const uint32_t* row_count,
+                            hipStream_t st) {
+  if (net->x_board == 7) dense_sp_launch<dsp::Geo7>(net, canon, v, pi, rows_max, rows, row_count, st);
+  else if (net->x_board == 11) dense_sp_launch<dsp::Geo11>(net, canon, v, pi, rows_max, rows, row_count, st);
+  else dense_sp_launch<dsp::Geo13>(net, canon, v, pi, rows_max, rows, row_count, st);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "k_leafnet_dense_sp launch: %s", hipGetErrorString(e));
   return AZMI_OK;
 }
 static int reserve_pool(azmi_net* net, void* stream, uint32_t batch) {
@@ -502,7 +625,7 @@ static int spatial_forward(azmi_net* net, const float* dev_canonical, float* dev
 int azmi_net_reserve_stream(azmi_net* net, void* stream, uint32_t max_rows) {
   if (!net) return nfail(AZMI_ERR_INVALID, "null argument");
   if (net->spatial) return reserve_pool(net, stream, max_rows);
-  return AZMI_OK;      // fp32 (sized by its first forward), dense and Connect4 tiles: nothing per stream
+  return AZMI_OK;      // fp32 (sized by its first forward), both dense tiles and the Connect4 tiles: nothing per stream
 }
 int azmi_net_forward(azmi_net* net, const float* dev_canonical, float* dev_v, float* dev_pi, uint32_t batch, void* stream) {
   return net_forward_live(net, dev_canonical, dev_v, dev_pi, batch, stream, nullptr);
@@ -523,6 +646,7 @@ static int net_forward_live(azmi_net* net, const float* dev_canonical, float* de
   }
   if (net->spatial) return spatial_forward(net, dev_canonical, dev_v, dev_pi, batch, stream, nullptr, nullptr);
   if (net->dense) return dense_forward(net, dev_canonical, dev_v, dev_pi, batch, nullptr, nullptr, static_cast<hipStream_t>(stream));
+  if (net->dense_sp) return dense_sp_forward(net, dev_canonical, dev_v, dev_pi, batch, nullptr, nullptr, static_cast<hipStream_t>(stream));
   c4_launch(net, dev_canonical, dev_v, dev_pi, batch, nullptr, nullptr, static_cast<hipStream_t>(stream));
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return nfail(AZMI_ERR_NO_DEVICE, "k_leafnet launch: %s", hipGetErrorString(e));
@@ -537,6 +661,7 @@ int azmi_net_forward_rows(azmi_net* net, const float* dev_canonical, float* dev_
   // play_manager.cc:577-597).  The MFMA kernels read and write through the list themselves; workgroups past the count exit.
   if (net->spatial) return spatial_forward(net, dev_canonical, dev_v, dev_pi, max_rows, stream, dev_rows, dev_row_count);
   if (net->dense) return dense_forward(net, dev_canonical, dev_v, dev_pi, max_rows, dev_rows, dev_row_count, static_cast<hipStream_t>(stream));
+  if (net->dense_sp) return dense_sp_forward(net, dev_canonical, dev_v, dev_pi, max_rows, dev_rows, dev_row_count, static_cast<hipStream_t>(stream));
   if (net->f32) {
     // the fp32 kernels take a dense batch: gather the listed rows, evaluate, scatter the answers back
     uint32_t chw, p1, m;
@@ -613,7 +738,7 @@ void azmi_net_eval_host(const float* canonical, uint32_t n, float* v, float* pi,
 }
 
 int azmi_net_c4_view_get(const azmi_net* net, azmi_net_c4_view* out) {
-  if (!net || !out || net->f32 || net->spatial || net->dense) return 0;    // (a dense net never reaches c4_launch or the pipeline)
+  if (!net || !out || net->f32 || net->spatial || net->dense || net->dense_sp) return 0;    // (a dense net never reaches c4_launch or the pipeline)
   out->nd = net->nd; out->np = net->np; out->x3 = net->x3 ? 1 : 0;
   out->lds_bytes = net->x3 ? c4::TileBigX3::LDS_BYTES : c4::TileSmall::LDS_BYTES;   // (bf16: the engine's fused launch runs the small tile)
   return 1;

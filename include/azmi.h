@@ -749,8 +749,11 @@ int azmi_net_create(const azmi_net_desc* desc, const void* blob, size_t blob_byt
  *                   precision 0: one matrix-core kernel for the dense Connect4 family (csrc/leafnet_dense.h) - 6x7, flat policy
  *                   head, kernel_size 3 or 5, 1 <= channels <= 16, depth >= 1, in_channels + channels * depth <= 128,
  *                   head_channels 32, no extra head convolutions, v_fc_layers 1, v_hidden a multiple of 16 up to 256,
- *                   num_players <= 3, num_moves <= 16; narrower widths are zero-padded by fold().  Everything else, and
- *                   precision 2, is AZMI_ERR_INVALID with a message naming precision='fp32'.
+ *                   num_players <= 3, num_moves <= 16; narrower widths are zero-padded by fold().  And a second one for the dense
+ *                   spatial-head family (csrc/leafnet_dense_sp.h: the single-variant StarGambit configs) - policy_channels 1..32 on
+ *                   7x7, 11x11 or 13x13, 0..32 global actions (pi_hidden a multiple of 16 in 16..256 with them), the same trunk
+ *                   and value-head bounds, trunk_norm 0 only.  Everything else, and precision 2, is AZMI_ERR_INVALID with a
+ *                   message naming precision='fp32'.
  *                   precision 1: any dense shape (every head the fp32 path has), kernel_size 1, 3, 5 or 7 for the trunk and the
  *                   extra head convolutions.
  *   trunk_norm      0 = nn.BatchNorm2d on every trunk norm (folded on the host), 1 = "layer": nn.GroupNorm(1, C) (NNArgs.trunk_norm,
