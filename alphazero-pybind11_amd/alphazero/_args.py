@@ -22,6 +22,13 @@ def seed64(x, what):
     return integer(x, f"{what}: seed must be an integer in [0, 2^64), got {x!r}", 0, (1 << 64) - 1)
 
 
+def unit_fraction(x, text):
+    """x: an int, float or numpy real, never a bool, with 0 < x <= 1 (a NaN fails both) -> float(x)"""
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not (0 < x <= 1):
+        raise RuntimeError(text)
+    return float(x)
+
+
 def number(x, text, positive=False):
     """x: a finite int, float or numpy real, never a bool, x >= 0 (positive: x > 0) -> float(x)"""
     if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x < 0 or (positive and not x > 0):

@@ -120,6 +120,13 @@ class SampleMetricsRecordC(C.Structure):      # azmi_sample_metrics_record
                 ("invalid", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+WINDOW_MAX_SEGMENTS = 64        # AZMI_WINDOW_MAX_SEGMENTS
+
+
+class SelectRecordC(C.Structure):      # azmi_select_record
+    _fields_ = [("threshold_key", C.c_double), ("selected", C.c_uint64), ("nan_rows", C.c_uint32), ("first_bad_row", C.c_uint32)]
+
+
 # every symbol include/azmi.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _PP = C.POINTER
@@ -202,6 +209,10 @@ SYMBOLS = {
     "azmi_sample_plane_argmax": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                            _VP, C.c_int, _VP]),
     "azmi_sample_metrics_reduce": (C.c_int, [_VP, C.c_uint64, C.c_uint32, _VP, C.c_uint32, _PP(SampleMetricsRecordC), C.c_int, _VP]),
+    "azmi_samples_reservoir_keys": (C.c_int, [_VP, _VP, C.c_uint32, C.c_double, C.c_double, C.c_uint64, _VP, _VP, C.c_int, _VP]),
+    "azmi_samples_select_top": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, _PP(SelectRecordC), C.c_int, _VP]),
+    "azmi_samples_window_gather": (C.c_int, [_PP(_VP), _PP(C.c_uint64), C.c_uint32, C.c_uint32, _VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                             _VP, C.c_int, _VP]),
     "azmi_pm_net_forward": (C.c_int, [_VP, _VP, _VP]),
     "azmi_pm_net_forward_group": (C.c_int, [_VP, C.c_uint32, _VP, _VP]),
     "azmi_pm_groups": (C.c_int, [_VP, _PP(C.c_uint32), _PP(C.c_uint32)]),

@@ -10,19 +10,24 @@ the package does not import it.
 Second half (azmi_sample_metrics / azmi_sample_plane_argmax / azmi_sample_metrics_reduce, csrc/sample_metrics_kernels.h): the
 per-row policy and value diagnostics of a net against the samples - sample_metrics, plane_argmax - and the two consumers the
 reference has for them: eval_metrics (network_pareto.eval_loss, network_pareto.py:652-738) and analyze_samples
-(game_runner._analyze_iteration_variants, game_runner.py:2509-2627)."""
+(game_runner._analyze_iteration_variants, game_runner.py:2509-2627).
+
+Third part (azmi_samples_reservoir_keys / azmi_samples_select_top / azmi_samples_window_gather, csrc/samples_window_kernels.h): the
+history window and the recency-weighted reservoir that training reads - reservoir_keys, select_top, window_batches and the
+SampleWindow that holds them together (calc_hist_size, update_reservoir and train, game_runner.py:955-1008, 1701-1869, 1289-1345)."""
 import ctypes as C
 import enum
 
 import numpy as np
 
-from . import _args
-from ._capi import lib, ResampleRecordC, SampleMetricsRecordC
+from . import _args, _rng
+from ._capi import lib, ResampleRecordC, SampleMetricsRecordC, SelectRecordC, WINDOW_MAX_SEGMENTS
 
 MAX_ROWS = 1 << 30
 MAX_ENTRIES = 1 << 20
 MAX_BUCKETS = 8
 MAX_PLANES = 16
+_GOLDEN = 0x9E3779B97F4A7C15
 
 
 class Metric(enum.IntEnum):
@@ -662,3 +667,306 @@ def analyze_samples(samples, net, cv=1.0, batch_rows=65536, buckets=None, names=
             continue
         out[name] = {k: cols[Metric[k.upper()]][mask] for k in ANALYSIS_KEYS}
     return out
+
+
+# ---- the history window and the reservoir: reservoir_keys, select_top, window_batches, SampleWindow ---------------------------------
+def _check_vector(what, name, x, want):
+    if len(x.shape) != 1:
+        raise RuntimeError(f"{what}: {name} must be one-dimensional, got shape {tuple(x.shape)}")
+    _check_rows(what, int(x.shape[0]))
+    _check_dtype(what, name, x, want)
+    return int(x.shape[0])
+
+
+def reservoir_keys(iters, iteration, decay, seed, row_ids=None, with_bits=False, device=0, stream=None):
+    """The keys of a weighted sample without replacement (azmi_samples_reservoir_keys; the weights of game_runner.py:1845-1846):
+
+        key_i = log(u_i) / w_i,   w_i = decay ** max(0, iteration - iters[i])
+        u_i = m_i * 2^-53,   m_i = ((mix64(seed + 0x9E3779B97F4A7C15 * (id_i + 1)) >> 12) << 1) | 1
+
+    `iters`: int32 [n], the iteration every row came from; id_i = row_ids[i] (uint64 / int64 [n]) or i.  The k largest keys
+    (select_top) draw k rows with the distribution of torch.multinomial(w, k, replacement=False), not with its stream.  A weight
+    that underflows to 0 gives -inf.  -> float64 [n] (with_bits: (keys, m) with m uint64 / int64 [n]), numpy for numpy (staged on
+    `device`), CUDA tensors for CUDA tensors (on `stream`, no synchronisation).  n == 0 touches no device."""
+    what = "reservoir_keys"
+    named = [("iters", iters)] + ([] if row_ids is None else [("row_ids", row_ids)])
+    kind = _kind(what, named)
+    n = _check_vector(what, "iters", iters, "int32")
+    if row_ids is not None and (_check_vector(what, "row_ids", row_ids, ("uint64", "int64")) != n):
+        raise RuntimeError(f"{what}: row_ids must hold one id per row ({n}), got shape {tuple(row_ids.shape)}")
+    iteration = _args.number(iteration, f"{what}: iteration must be a finite number >= 0, got {iteration!r}")
+    decay = _args.unit_fraction(decay, f"{what}: decay must be a number in (0, 1], got {decay!r}")
+    seed = _args.seed64(seed, what)
+    if kind == "numpy":
+        device = _args.device_index(device, what)
+        if n == 0:
+            return (np.zeros(0, np.float64), np.zeros(0, np.uint64)) if with_bits else np.zeros(0, np.float64)
+        iters = _stage(iters, device)
+        row_ids = None if row_ids is None else _stage(row_ids.view(np.int64), device)
+    import torch
+    keys = _empty(n, torch.float64, iters.device, stream)
+    bits = _empty(n, torch.int64, iters.device, stream) if with_bits else None
+    if n:
+        _call(lib.azmi_samples_reservoir_keys(iters.data_ptr(), None if row_ids is None else row_ids.data_ptr(), n, iteration, decay, seed,
+                                              keys.data_ptr(), None if bits is None else bits.data_ptr(), iters.device.index,
+                                              _stream_of(iters.device, stream)))
+    if kind == "numpy":
+        keys = keys.cpu().numpy()
+        return (keys, bits.cpu().numpy().view(np.uint64)) if with_bits else keys
+    return (keys, bits) if with_bits else keys
+
+
+def select_top(keys, k, device=0, stream=None):
+    """The rows of the k largest of the float64 `keys` [n], in ASCENDING ROW ORDER (azmi_samples_select_top): among equal keys the
+    lower rows win, -0.0 counts as +0.0, -inf loses to every finite key: np.sort(np.argsort(-keys, kind="stable")[:k]).  A radix
+    select and an ordered compaction on the device, no sort; the result does not depend on scheduling.
+    -> (index int64 [k], {"selected": k, "threshold_key": the smallest chosen key, "first_bad_row": None}).  One synchronisation,
+    the record.  Raises RuntimeError naming the first row whose key is NaN.  k == 0 touches no device."""
+    what = "select_top"
+    kind = _kind(what, (("keys", keys),))
+    n = _check_vector(what, "keys", keys, "float64")
+    k = _args.integer(k, f"{what}: k must be an integer in [0, n = {n}], got {k!r}", 0, n)
+    if kind == "numpy":
+        device = _args.device_index(device, what)
+        if k == 0:
+            return np.zeros(0, np.int64), {"selected": 0, "threshold_key": None, "first_bad_row": None}
+        keys = _stage(keys, device)
+    import torch
+    index = _empty(k, torch.int64, keys.device, stream)
+    if k == 0:
+        return index, {"selected": 0, "threshold_key": None, "first_bad_row": None}
+    rec = SelectRecordC()
+    _call(lib.azmi_samples_select_top(keys.data_ptr(), n, k, index.data_ptr(), C.byref(rec), keys.device.index, _stream_of(keys.device, stream)))
+    if rec.nan_rows:
+        raise RuntimeError(f"{what}: {rec.nan_rows} of {n} keys are NaN, the first at row {rec.first_bad_row} (first_bad_row)")
+    record = {"selected": int(rec.selected), "threshold_key": float(rec.threshold_key), "first_bad_row": None}
+    return (index.cpu().numpy() if kind == "numpy" else index), record
+
+
+def _row_shapes(what, c, v, pi):
+    return tuple(c.shape[1:]), tuple(v.shape[1:]), tuple(pi.shape[1:])
+
+
+def _check_segments(what, segments):
+    """the checks of a window: a sequence of at most 64 (canonical, v, pi) triples of one kind, one device and one row shape
+    -> (kind, [(canonical [n, C, H, W], v [n, V], pi [n, M])], [n])"""
+    try:
+        segments = list(segments)
+    except TypeError:
+        raise RuntimeError(f"{what}: segments must be a sequence of (canonical, v, pi) triples, got {type(segments).__name__}") from None
+    if len(segments) > WINDOW_MAX_SEGMENTS:
+        raise RuntimeError(f"{what}: at most {WINDOW_MAX_SEGMENTS} segments, got {len(segments)}")
+    kinds, out, rows, shapes, named_all = set(), [], [], None, []
+    for s, seg in enumerate(segments):
+        try:
+            canonical, v, pi = seg
+        except (TypeError, ValueError):
+            raise RuntimeError(f"{what}: segments[{s}] must be the (canonical, v, pi) triple") from None
+        named = ((f"segments[{s}].canonical", canonical), (f"segments[{s}].v", v), (f"segments[{s}].pi", pi))
+        named_all.extend(named)
+        kinds.add(_kind(what, named))
+        cs, vs, ps = tuple(canonical.shape), tuple(v.shape), tuple(pi.shape)
+        if len(cs) != 4 or len(vs) != 2 or len(ps) != 2:
+            raise RuntimeError(f"{what}: segments[{s}]: canonical [n, C, H, W], v [n, V] and pi [n, M] are wanted, got shapes {cs}, {vs}, {ps}")
+        if not cs[0] == vs[0] == ps[0]:
+            raise RuntimeError(f"{what}: segments[{s}]: canonical, v and pi must hold one row per sample, got {cs[0]}, {vs[0]} and {ps[0]} rows")
+        _check_rows(what, cs[0])
+        for name, x in named:
+            _check_dtype(what, name, x, "float32")
+            row = int(np.prod(x.shape[1:], dtype=np.int64))
+            if row < 1 or row * 4 >= 1 << 26:
+                raise RuntimeError(f"{what}: {name}: a row of {row} elements: rows hold 1 to 2^24 - 1 float32")
+        if shapes is None:
+            shapes = (cs[1:], vs[1:], ps[1:])
+        elif shapes != (cs[1:], vs[1:], ps[1:]):
+            raise RuntimeError(f"{what}: segments[{s}]: rows of shapes {cs[1:]}, {vs[1:]}, {ps[1:]} in a window of {shapes[0]}, {shapes[1]}, {shapes[2]}")
+        out.append((canonical, v, pi))
+        rows.append(int(cs[0]))
+    if len(kinds) > 1:
+        raise RuntimeError(f"{what}: numpy arrays and tensors are mixed among the segments")
+    kind = kinds.pop() if kinds else "numpy"
+    if kind == "torch" and len({str(x.device) for _, x in named_all}) > 1:
+        raise RuntimeError(f"{what}: the segments are on different devices")
+    return kind, out, rows
+
+
+def _window_gather(arrays_t, rows_list, index_t, seed, pass_index, first, rows, stream):
+    """azmi_samples_window_gather over the segments `arrays_t` of one row array -> the gathered tensor [rows, ...]"""
+    x0 = arrays_t[0]
+    out = _empty((rows,) + tuple(x0.shape[1:]), x0.dtype, x0.device, stream)
+    if rows == 0:
+        return out
+    ns = len(arrays_t)
+    ptrs = (C.c_void_p * ns)(*[x.data_ptr() if n else None for x, n in zip(arrays_t, rows_list)])
+    counts = (C.c_uint64 * ns)(*rows_list)
+    row_bytes = int(np.prod(x0.shape[1:], dtype=np.int64)) * x0.element_size()
+    _call(lib.azmi_samples_window_gather(ptrs, counts, ns, row_bytes, None if index_t is None else index_t.data_ptr(), seed, pass_index, first,
+                                         rows, out.data_ptr(), x0.device.index, _stream_of(x0.device, stream)))
+    return out
+
+
+def _pass_batches(segs_t, rows_list, batch_rows, seed, pass_index, first, batches, stream):
+    """the batches of one pass over CUDA segments: one launch per array and batch, no synchronisation"""
+    total, b = sum(rows_list), 0
+    while first < total and (batches is None or b < batches):
+        rows = min(batch_rows, total - first)
+        yield tuple(_window_gather([seg[a] for seg in segs_t], rows_list, None, seed, pass_index, first, rows, stream) for a in range(3))
+        first += rows
+        b += 1
+
+
+def window_batches(segments, batch_rows, seed, pass_index=0, first=0, batches=None, device=0, stream=None):
+    """One shuffled pass over a window of samples, cut into training batches that mix the segments (azmi_samples_window_gather; the
+    pass of StreamingCompressedDataset that train() consumes, game_runner.py:1289-1345, 1923-2009).  `segments`: up to 64
+    (canonical, v, pi) triples, one per iteration, read as their concatenation of `total` rows.  Batch b holds the rows
+    perm(first + b * batch_rows + j), j < batch_rows, perm the bijection of [0, total) keyed by (seed, pass_index) that DESIGN.md
+    8.5.2 states; the last batch of the pass is short.  `batches`: stop after that many (None: the whole pass from `first`).
+    -> a generator of (canonical, v, pi) batches, numpy for numpy (the segments are staged on `device` once), CUDA tensors for CUDA
+    tensors (on `stream`): one launch per array and batch, no synchronisation.  The arguments are checked at the call, not at the
+    first batch."""
+    what = "window_batches"
+    kind, segs, rows_list = _check_segments(what, segments)
+    batch_rows = _args.integer(batch_rows, f"{what}: batch_rows must be an integer in [1, 2^30], got {batch_rows!r}", 1, MAX_ROWS)
+    seed = _args.seed64(seed, what)
+    pass_index = _args.integer(pass_index, f"{what}: pass_index must be an integer in [0, 2^63), got {pass_index!r}", 0, (1 << 63) - 1)
+    total = sum(rows_list)
+    first = _args.integer(first, f"{what}: first must be a row of the window, an integer in [0, {total}], got {first!r}", 0, total)
+    if batches is not None:
+        batches = _args.integer(batches, f"{what}: batches must be None or an integer >= 0, got {batches!r}", 0)
+    if kind == "numpy":
+        device = _args.device_index(device, what)
+
+    def run():
+        if first >= total or batches == 0:
+            return
+        segs_t = [tuple(_stage(x, device) for x in seg) for seg in segs] if kind == "numpy" else segs
+        for batch in _pass_batches(segs_t, rows_list, batch_rows, seed, pass_index, first, batches, stream):
+            yield tuple(x.cpu().numpy() for x in batch) if kind == "numpy" else batch
+    return run()
+
+
+class SampleWindow:
+    """The history window and the recency-weighted reservoir of the reference's training loop, kept in HBM (calc_hist_size,
+    game_runner.py:955-1008; update_reservoir, :1701-1869; train, :1289-1345): the last `hist_size` iterations as they were appended,
+    the iterations that left the window in staging, and ONE reservoir chunk of at most `reservoir_rows` rows that update_reservoir
+    merges the staging into with weights decay ** age.  The reference's n_chunks, chunks_per_update and file rotation bound host RAM
+    and have no counterpart here.  Row ids are (iteration << 32) | row, the draw of an update is keyed by
+    mix64(seed + 0x9E3779B97F4A7C15 * (iteration + 1)): a run is a function of `seed` and the samples."""
+
+    def __init__(self, hist_size, reservoir_rows, decay, seed, update_interval=1, device=0):
+        what = "SampleWindow"
+        self.hist_size = _args.integer(hist_size, f"{what}: hist_size must be an integer >= 1, got {hist_size!r}", 1)
+        self.reservoir_rows = _args.integer(reservoir_rows, f"{what}: reservoir_rows must be an integer in [0, 2^30], got {reservoir_rows!r}", 0, MAX_ROWS)
+        self.decay = _args.unit_fraction(decay, f"{what}: decay must be a number in (0, 1], got {decay!r}")
+        self.seed = _args.seed64(seed, what)
+        self.update_interval = _args.integer(update_interval, f"{what}: update_interval must be an integer >= 1, got {update_interval!r}", 1)
+        self.device = _args.device_index(device, what)
+        self._window = []          # [(iteration, (canonical, v, pi))], ascending
+        self._staged = []          # the same: evicted, not yet merged
+        self._reservoir = None     # (canonical, v, pi, iterations int32, row ids int64)
+        self._shapes = None
+        self._newest_merged = -1   # the newest iteration that went into the reservoir
+        self._evicted = 0
+        self._syncs = 0
+        self.last_update = None    # what the last merging update_reservoir saw: its pool and its choice
+
+    def append(self, iteration, samples):
+        """Keep the (canonical, v, pi) of `iteration` (CUDA tensors are kept as they are, numpy arrays are staged on the window's device);
+        the iterations at or below iteration - hist_size move to staging."""
+        what = "SampleWindow.append"
+        iteration = _args.integer(iteration, f"{what}: iteration must be an integer in [0, 2^31), got {iteration!r}", 0, (1 << 31) - 1)
+        kind, n, c, v, pi = _check_samples(what, samples, 1)
+        newest = max([t for t, _ in self._window + self._staged] + [self._newest_merged])
+        if iteration <= newest:
+            raise RuntimeError(f"{what}: iterations are appended in ascending order, got {iteration} after {newest}")
+        shapes = _row_shapes(what, c, v, pi)
+        if self._shapes is not None and shapes != self._shapes:
+            raise RuntimeError(f"{what}: rows of shapes {shapes} in a window of {self._shapes}")
+        if kind == "numpy":
+            c, v, pi = _stage(c, self.device), _stage(v, self.device), _stage(pi, self.device)
+        elif c.device.index != self.device:
+            raise RuntimeError(f"{what}: the samples are on {c.device}, the window on device {self.device}")
+        self._shapes = shapes
+        self._window.append((iteration, (c, v, pi)))
+        while self._window and self._window[0][0] <= iteration - self.hist_size:
+            self._staged.append(self._window.pop(0))
+            self._evicted += 1
+
+    def update_reservoir(self, iteration):
+        """The merge of update_reservoir (game_runner.py:1815-1859) on one chunk: pool = reservoir + staging; while the pool has at
+        most reservoir_rows rows it IS the new reservoir (the fill phase), otherwise the rows of the reservoir_rows largest
+        reservoir_keys are kept, in pool order (select_top: the one synchronisation).  One gather per array.  Does nothing when
+        iteration is no multiple of update_interval or nothing is staged.  -> the rows of the reservoir."""
+        what = "SampleWindow.update_reservoir"
+        iteration = _args.integer(iteration, f"{what}: iteration must be an integer in [0, 2^31), got {iteration!r}", 0, (1 << 31) - 1)
+        if iteration % self.update_interval or not self._staged:
+            return self.stats()["reservoir_rows"]
+        import torch
+        dev = torch.device("cuda", self.device)
+        pool = ([(None, self._reservoir[:3])] if self._reservoir is not None else []) + self._staged
+        if len(pool) > WINDOW_MAX_SEGMENTS:
+            raise RuntimeError(f"{what}: {len(self._staged)} staged iterations: a pool holds at most {WINDOW_MAX_SEGMENTS} segments; "
+                               "call update_reservoir more often")
+        rows_list = [int(seg[0].shape[0]) for _, seg in pool]
+        n = sum(rows_list)
+        _check_rows(what, n)
+        iters = [self._reservoir[3]] if self._reservoir is not None else []
+        ids = [self._reservoir[4]] if self._reservoir is not None else []
+        for t, seg in self._staged:
+            rows = int(seg[0].shape[0])
+            iters.append(torch.full((rows,), t, dtype=torch.int32, device=dev))
+            ids.append(torch.arange(rows, dtype=torch.int64, device=dev) + (t << 32))
+        iters, ids = torch.cat(iters), torch.cat(ids)
+        self._newest_merged = max(self._newest_merged, self._staged[-1][0])
+        self._staged = []
+        if n == 0 or self.reservoir_rows == 0:
+            return self.stats()["reservoir_rows"]
+        keys = None
+        if n > self.reservoir_rows:
+            keys = reservoir_keys(iters, iteration, self.decay, _rng.mix64((self.seed + _GOLDEN * (iteration + 1)) & _rng.MASK64), row_ids=ids)
+            index, _ = select_top(keys, self.reservoir_rows)
+            self._syncs += 1
+        else:
+            index = torch.arange(n, dtype=torch.int64, device=dev)
+        k = int(index.shape[0])
+        kept = [_window_gather([seg[a] for _, seg in pool], rows_list, index, 0, 0, 0, k, None) for a in range(3)]
+        kept += [_window_gather([x], [n], index, 0, 0, 0, k, None) for x in (iters, ids)]
+        self._reservoir = tuple(kept)
+        self.last_update = {"iteration": iteration, "pool_rows": n, "pool_iterations": iters, "pool_row_ids": ids, "keys": keys, "index": index}
+        return k
+
+    def segments(self):
+        """the (canonical, v, pi) triples batches() reads: the window's iterations in ascending order, then the reservoir"""
+        return [seg for _, seg in self._window] + ([self._reservoir[:3]] if self._reservoir is not None else [])
+
+    def batches(self, batch_rows, sample_rate=1.0, pass_seed=0):
+        """train()'s step budget (game_runner.py:1314-1317): ceil(average_generation / batch_rows * sample_rate) batches, where
+        average_generation is the window's rows over its iterations, cut from shuffled passes over window + reservoir
+        (window_batches; pass p is keyed by (pass_seed, p), a pass ends with a short batch and the next one begins).  -> a
+        generator of (canonical, v, pi) CUDA batches; no synchronisation."""
+        what = "SampleWindow.batches"
+        batch_rows = _args.integer(batch_rows, f"{what}: batch_rows must be an integer in [1, 2^30], got {batch_rows!r}", 1, MAX_ROWS)
+        sample_rate = _args.number(sample_rate, f"{what}: sample_rate must be a finite number >= 0, got {sample_rate!r}")
+        pass_seed = _args.seed64(pass_seed, what)
+        segs = self.segments()
+        if len(segs) > WINDOW_MAX_SEGMENTS:
+            raise RuntimeError(f"{what}: the window and the reservoir are {len(segs)} segments: at most {WINDOW_MAX_SEGMENTS}")
+        rows_list = [int(seg[0].shape[0]) for seg in segs]
+        window_rows = sum(rows_list[:len(self._window)])
+        count = int(np.ceil(window_rows / len(self._window) / batch_rows * sample_rate)) if self._window else 0
+
+        def run():
+            left, p = count, 0
+            while left > 0 and sum(rows_list) > 0:
+                for batch in _pass_batches(segs, rows_list, batch_rows, pass_seed, p, 0, left, None):
+                    left -= 1
+                    yield batch
+                p += 1
+        return run()
+
+    def stats(self):
+        return {"window_rows": sum(int(seg[0].shape[0]) for _, seg in self._window),
+                "reservoir_rows": 0 if self._reservoir is None else int(self._reservoir[0].shape[0]),
+                "staged_rows": sum(int(seg[0].shape[0]) for _, seg in self._staged),
+                "window_iterations": [t for t, _ in self._window],
+                "evicted_iterations": self._evicted, "host_syncs": self._syncs}

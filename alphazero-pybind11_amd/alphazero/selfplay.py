@@ -206,7 +206,16 @@ def process_samples(game, samples, net, seed, **kwargs):
     return resample_by_surprise(samples, net, seed, **kwargs)
 
 
-UNIFIED_VARIANT_NAMES = ("skirmish", "showdown", "clash", "battle")      # game_runner.py:37
+def training_batches(window, batch_rows, sample_rate=1.0, pass_seed=0):
+    """The batches train() takes from the history window and the reservoir (game_runner.py:1289-1345): SampleWindow.batches of
+    `window`, ceil(average_generation / batch_rows * sample_rate) (canonical, v, pi) CUDA batches cut from shuffled passes."""
+    from .samples import SampleWindow
+    if not isinstance(window, SampleWindow):
+        raise RuntimeError(f"training_batches: window must be a SampleWindow, got {type(window).__name__}")
+    return window.batches(batch_rows, sample_rate=sample_rate, pass_seed=pass_seed)
+
+
+UNIFIED_VARIANT_NAMES =("skirmish", "showdown", "clash", "battle")      # game_runner.py:37
 
 
 def variant_buckets(game, canonical, **kwargs):

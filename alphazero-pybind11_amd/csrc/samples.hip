@@ -3,8 +3,12 @@
 // once, to hand back its record (the caller needs rows_out to size the gather's outputs).
 // Likewise the per-row diagnostics of sample_metrics_kernels.h: azmi_sample_metrics and azmi_sample_plane_argmax are one
 // asynchronous launch each, azmi_sample_metrics_reduce synchronises once for its record.
+// And the history window and the reservoir of samples_window_kernels.h: azmi_samples_reservoir_keys and
+// azmi_samples_window_gather are one asynchronous launch each, azmi_samples_select_top synchronises once for its record.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <mutex>
 #include <string>
@@ -14,6 +18,7 @@
 #include "host_error.h"
 #include "samples_kernels.h"
 #include "sample_metrics_kernels.h"
+#include "samples_window_kernels.h"
 #include "samples_layout.h"
 
 namespace {
@@ -22,6 +27,8 @@ using namespace azmi;
 static_assert(sizeof(ResampleRecord) == sizeof(azmi_resample_record), "azmi_resample_record is the device record");
 static_assert(sizeof(SampleMetricsRecord) == sizeof(azmi_sample_metrics_record), "azmi_sample_metrics_record is the device record");
 static_assert(kSampleMetricColumns == AZMI_SAMPLE_METRIC_COLUMNS && kMetricMaxBuckets == AZMI_SAMPLE_METRIC_MAX_BUCKETS, "the header's sizes");
+static_assert(offsetof(SelectState, prefix) == sizeof(azmi_select_record), "azmi_select_record is the head of the device state");
+static_assert(kWindowMaxSegments == AZMI_WINDOW_MAX_SEGMENTS, "the header's sizes");
 
 thread_local std::string g_samples_err;
 
@@ -59,6 +66,7 @@ std::mutex g_plan_mutex;
 DevBlock g_plan_scratch[kPlanMaxDevices];
 
 DevBlock g_metrics_scratch[kPlanMaxDevices];      // the same for azmi_sample_metrics_reduce, under the same mutex
+DevBlock g_select_scratch[kPlanMaxDevices];       // and for azmi_samples_select_top
 
 uint32_t tiles_of(uint32_t n) { return (n + kPlanBlock - 1) / kPlanBlock; }
 
@@ -275,6 +283,117 @@ int azmi_sample_metrics_reduce(const double* dev_cols, uint64_t col_stride, uint
     for (uint32_t c = 0; c < kSampleMetricColumns; ++c) host_record_out->total[c] = host_record_out->sum[0][c];
   }
   return AZMI_OK;
+}
+
+// ---- the history window and the reservoir (samples_window_kernels.h) --------------------------------------------------------------
+int azmi_samples_reservoir_keys(const int32_t* dev_iters, const uint64_t* dev_row_ids, uint32_t n, double iteration, double decay,
+                                uint64_t seed, double* dev_keys_out, uint64_t* dev_bits_out, int device, void* stream) {
+  if (n > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "azmi_samples_reservoir_keys: n = %u: at most %u rows", n, kPlanMaxRows);
+  if (!std::isfinite(iteration)) return sfail(AZMI_ERR_INVALID, "azmi_samples_reservoir_keys: iteration must be finite, got %g", iteration);
+  if (!(decay > 0.0 && decay <= 1.0)) return sfail(AZMI_ERR_INVALID, "azmi_samples_reservoir_keys: decay must be in (0, 1], got %g", decay);
+  if (n == 0) return AZMI_OK;
+  if (!dev_iters || !dev_keys_out) return sfail(AZMI_ERR_INVALID, "azmi_samples_reservoir_keys: null argument");
+  DeviceScope scope;
+  int rc = scope.enter("azmi_samples_reservoir_keys", device); if (rc) return rc;
+  k_reservoir_keys<<<(n + kKeyThreads - 1) / kKeyThreads, kKeyThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      dev_iters, dev_row_ids, n, iteration, decay, seed, dev_keys_out, dev_bits_out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : hip_fail("k_reservoir_keys", e);
+}
+
+int azmi_samples_select_top(const double* dev_keys, uint32_t n, uint32_t k, int64_t* dev_index_out, azmi_select_record* host_record_out,
+                            int device, void* stream) {
+  if (!host_record_out) return sfail(AZMI_ERR_INVALID, "azmi_samples_select_top: null argument");
+  *host_record_out = azmi_select_record{0.0, 0, 0, kPlanNone};
+  if (n > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "azmi_samples_select_top: n = %u: at most %u rows", n, kPlanMaxRows);
+  if (k > n) return sfail(AZMI_ERR_INVALID, "azmi_samples_select_top: k = %u of n = %u keys", k, n);
+  if (k == 0) return AZMI_OK;
+  if (!dev_keys || !dev_index_out) return sfail(AZMI_ERR_INVALID, "azmi_samples_select_top: null argument");
+  if (device >= kPlanMaxDevices) return sfail(AZMI_ERR_INVALID, "azmi_samples_select_top: device %d: at most %d devices", device, kPlanMaxDevices);
+  DeviceScope scope;
+  int rc = scope.enter("azmi_samples_select_top", device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t t0 = tiles_of(n), t1 = tiles_of(t0);      // t1 <= 1024: the level above it is one tile
+  SelectScratch<SelectState> ss;
+  BlockCut size;
+  cut_select_scratch(size, ss, t0, t1);
+  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  DevBlock& sc = g_select_scratch[device];
+  hipError_t e = sc.reserve(size.off);      // allocates on the first call on this device, or for a larger n than any before
+  if (e != hipSuccess) return hip_fail("azmi_samples_select_top", e);
+  BlockCut cut(sc.p);
+  cut_select_scratch(cut, ss, t0, t1);
+  e = hipMemsetAsync(ss.st, 0, sizeof *ss.st, st);
+  if (e == hipSuccess) e = hipMemsetAsync(&ss.st->first_bad_row, 0xFF, 4, st);
+  if (e == hipSuccess) {
+    uint32_t blocks = (n + kSelectThreads - 1) / kSelectThreads;
+    blocks = blocks < kSelectMaxBlocks ? blocks : kSelectMaxBlocks;
+    for (uint32_t pass = 0; pass < kSelectPasses; ++pass) {
+      k_select_hist<<<blocks, kSelectThreads, 0, st>>>(dev_keys, n, ss.st, pass);
+      k_select_pick<<<1, 64, 0, st>>>(ss.st, pass, k);
+    }
+    // the chosen rows in ascending order: the tile counts, their scan level by level (as the plan's offsets), the write
+    if (t0 > 1) {
+      k_select_tiles<<<t0, kPlanBlock, 0, st>>>(dev_keys, n, ss.st, ss.tot0);
+      k_plan_scan<<<t1, kPlanBlock, 0, st>>>(ss.tot0, t0, t1 == 1 ? ss.top : ss.tot1);
+      if (t1 > 1) {
+        k_plan_scan<<<1, kPlanBlock, 0, st>>>(ss.tot1, t1, ss.top);
+        k_plan_add<<<t1, kPlanBlock, 0, st>>>(ss.tot0, t0, ss.tot1);
+      }
+    }
+    k_select_write<<<t0, kPlanBlock, 0, st>>>(dev_keys, n, ss.st, t0 > 1 ? ss.tot0 : nullptr, k, dev_index_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_record_out, ss.st, sizeof *host_record_out, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);      // the one synchronisation; always: what was queued uses the block the next call reuses
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail("azmi_samples_select_top", e);
+  return AZMI_OK;
+}
+
+int azmi_samples_window_gather(const void* const* dev_segments, const uint64_t* segment_rows, uint32_t n_segments, uint32_t row_bytes,
+                               const int64_t* dev_index, uint64_t seed, uint64_t pass_index, uint64_t first, uint32_t rows, void* dev_out,
+                               int device, void* stream) {
+  const char* what = "azmi_samples_window_gather";
+  if (n_segments == 0 || n_segments > kWindowMaxSegments)
+    return sfail(AZMI_ERR_INVALID, "%s: %u segments: 1 to %u per call", what, n_segments, kWindowMaxSegments);
+  if (!dev_segments || !segment_rows) return sfail(AZMI_ERR_INVALID, "%s: null argument", what);
+  if (row_bytes == 0 || row_bytes % 4u || row_bytes >= (1u << 26))
+    return sfail(AZMI_ERR_INVALID, "%s: a row of %u bytes: rows are whole dwords below 64 MiB", what, row_bytes);
+  if (rows > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "%s: rows = %u: at most %u rows per call", what, rows, kPlanMaxRows);
+  WindowSegments seg{};
+  WindowPerm pm{};
+  bool vec = row_bytes % 16u == 0 && reinterpret_cast<uintptr_t>(dev_out) % 16u == 0;
+  uint64_t total = 0;
+  for (uint32_t s = 0; s < n_segments; ++s) {
+    if (segment_rows[s] > (1ull << 40) || total + segment_rows[s] > (1ull << 40))
+      return sfail(AZMI_ERR_INVALID, "%s: segment %u: the window holds at most 2^40 rows", what, s);
+    if (segment_rows[s] && !dev_segments[s]) return sfail(AZMI_ERR_INVALID, "%s: segment %u: null argument", what, s);
+    if (reinterpret_cast<uintptr_t>(dev_segments[s]) % 4u) return sfail(AZMI_ERR_INVALID, "%s: segment %u: the arrays are dword-aligned", what, s);
+    if (segment_rows[s] && reinterpret_cast<uintptr_t>(dev_segments[s]) % 16u) vec = false;
+    seg.base[s] = dev_segments[s];
+    seg.start[s] = total;
+    total += segment_rows[s];
+  }
+  seg.count = n_segments;
+  if (first > total || rows > total - first)
+    return sfail(AZMI_ERR_INVALID, "%s: rows %llu .. %llu + %u of a window of %llu rows", what, static_cast<unsigned long long>(first),
+                 static_cast<unsigned long long>(first), rows, static_cast<unsigned long long>(total));
+  if (rows == 0) return AZMI_OK;
+  if (!dev_out || reinterpret_cast<uintptr_t>(dev_out) % 4u) return sfail(AZMI_ERR_INVALID, "%s: dev_out: null or not dword-aligned", what);
+  pm.total = total;
+  pm.bits = 2;
+  while (pm.bits < 41 && (1ull << pm.bits) < total) ++pm.bits;
+  const uint64_t k0 = mix64(seed + 0x9E3779B97F4A7C15ULL * (pass_index + 1));
+  for (uint32_t r = 0; r < kFeistelRounds; ++r) pm.key[r] = mix64(k0 + 0x9E3779B97F4A7C15ULL * (r + 1));
+  DeviceScope scope;
+  int rc = scope.enter(what, device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t grid = (rows + kWindowThreads - 1) / kWindowThreads;
+  if (vec) k_window_gather<uint4><<<grid, kWindowThreads, 0, st>>>(seg, pm, dev_index, first, rows, row_bytes / 16u, static_cast<uint4*>(dev_out));
+  else k_window_gather<uint32_t><<<grid, kWindowThreads, 0, st>>>(seg, pm, dev_index, first, rows, row_bytes / 4u, static_cast<uint32_t*>(dev_out));
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : hip_fail("k_window_gather", e);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// The two scratch blocks of samples.hip, each cut from one allocation (block_cut.h).  The record types are template parameters so
+// The scratch blocks of samples.hip, each cut from one allocation (block_cut.h).  The record types are template parameters so
 // that this header stays plain C++: samples.hip cuts with the device records of samples_kernels.h / sample_metrics_kernels.h,
 // whose sizes are those of the C records of include/azmi.h.
 #pragma once
@@ -34,6 +34,21 @@ void cut_metrics_scratch(BlockCut& c, MetricsScratch<Rec>& m, size_t pairs, size
   m.rec = c.take<Rec>(1);
   m.sum0 = c.take<double>(pairs * t0);
   m.sum1 = c.take<double>(pairs * t1);
+}
+
+// azmi_samples_select_top: the state (record, prefix, histograms) | the tile totals of the compaction's scan (u64): t0 tiles of
+// rows, t1 tiles of tiles, one word for the total above them
+template <class State>
+struct SelectScratch {
+  State* st;
+  uint64_t *tot0, *tot1, *top;
+};
+template <class State>
+void cut_select_scratch(BlockCut& c, SelectScratch<State>& s, size_t t0, size_t t1) {
+  s.st = c.take<State>(1);
+  s.tot0 = c.take<uint64_t>(t0);
+  s.tot1 = c.take<uint64_t>(t1);
+  s.top = c.take<uint64_t>(1);
 }
 
 }  // namespace azmi

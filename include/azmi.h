@@ -397,6 +397,55 @@ int azmi_sample_plane_argmax(const float* dev_canonical, uint32_t n, uint32_t C,
 int azmi_sample_metrics_reduce(const double* dev_cols, uint64_t col_stride, uint32_t n, const uint8_t* dev_bucket, uint32_t n_buckets,
                                azmi_sample_metrics_record* host_record_out, int device, void* stream);
 
+/* ---- the history window and the recency-weighted reservoir on the device (csrc/samples_window_kernels.h).  The
+ *      conventions of the two blocks above: DEVICE pointers, `stream` a HIP stream or NULL, the message of a failed call in
+ *      azmi_samples_last_error(), argument errors are AZMI_ERR_INVALID before any device call, at most 2^30 rows per call, an empty
+ *      call touches no device, the thread's current device is left as it was.
+ *   samples_reservoir_keys  replaces `ages = (iteration - pool_iters).clamp(min=0); weights = decay ** ages` and the draw of
+ *                    torch.multinomial(weights, k, replacement=False) (game_runner.py:1845-1849): dev_keys_out[i] (f64) =
+ *                      log(u_i) / w_i,   w_i = decay ** max(0, iteration - dev_iters[i])   (dev_iters: i32 [n])
+ *                      u_i = m_i * 2^-53,  m_i = ((mix64(seed + 0x9E3779B97F4A7C15 * (id_i + 1)) >> 12) << 1) | 1   (mod 2^64)
+ *                    id_i = dev_row_ids[i] (u64 [n]) or i when that is NULL.  u_i is strictly inside (0, 1), so a key is negative
+ *                    and finite unless w_i underflows to 0, which gives -inf; decay == 1 gives log(u_i).  The k LARGEST keys are a
+ *                    sample of k rows without replacement with probabilities proportional to w (successive sampling: the
+ *                    distribution of torch.multinomial, not its stream).  dev_bits_out (u64 [n], may be NULL) receives m_i.
+ *                    decay outside (0, 1] or a non-finite iteration is AZMI_ERR_INVALID.  One launch, asynchronous.
+ *   samples_select_top  replaces the selection of torch.multinomial and the fancy index `pool[selected]` it feeds
+ *                    (game_runner.py:1847-1855): dev_index_out (i64 [k]) = the rows of the k largest of the n f64 keys, in
+ *                    ASCENDING ROW ORDER; among equal keys the lower rows win; -0.0 counts as +0.0; -inf loses to every finite
+ *                    key.  A radix select over the order-preserving 64-bit image of the keys (8 histogram passes of 8 bits) and an
+ *                    ordered compaction: no sort, and a result that does not depend on scheduling.  The record: selected (= k),
+ *                    threshold_key (the smallest chosen key), nan_rows / first_bad_row (the rows that are NaN and the first of
+ *                    them, 0xFFFFFFFF for none; with a NaN the index list is unspecified but every entry is < n).  k > n is
+ *                    AZMI_ERR_INVALID; k == 0 touches no device.  Synchronises `stream` once, to hand back the record; the scratch
+ *                    block is kept per device.
+ *   samples_window_gather  replaces the shuffled, cross-file-mixed pass of StreamingCompressedDataset (game_runner.py:1923-2009) that
+ *                    train() cuts into batches (game_runner.py:1289-1345), and the row gather of update_reservoir:
+ *                      out[j] = window[p],  p = perm(first + j),  j < rows
+ *                    over a window of n_segments <= 64 arrays dev_segments[s] of segment_rows[s] rows (HOST arrays; a segment may
+ *                    be empty) of row_bytes bytes (whole dwords, < 64 MiB), read as their concatenation; total <= 2^40 rows,
+ *                    first + rows <= total.  perm is a bijection of [0, total) computed per row, no table and no sort: a Feistel
+ *                    network of 6 rounds over b = max(2, ceil(log2 total)) bits, halves of b / 2 and b - b / 2 bits that swap every
+ *                    round, x = (R << wl) | (L ^ (mix64(R + key_r) & (2^wl - 1))), key_r = mix64(k0 + 0x9E3779B97F4A7C15 * (r + 1)),
+ *                    k0 = mix64(seed + 0x9E3779B97F4A7C15 * (pass_index + 1)), repeated until the value is < total.  With dev_index
+ *                    (i64, at least first + rows entries) p = dev_index[first + j] instead (an entry outside the window reads its
+ *                    last row).  Rows move as 16-byte accesses when row_bytes and every base address are multiples of 16, as
+ *                    dwords otherwise.  One launch, asynchronous. */
+#define AZMI_WINDOW_MAX_SEGMENTS 64
+typedef struct azmi_select_record {
+  double threshold_key;
+  uint64_t selected;
+  uint32_t nan_rows;
+  uint32_t first_bad_row;
+} azmi_select_record;
+int azmi_samples_reservoir_keys(const int32_t* dev_iters, const uint64_t* dev_row_ids, uint32_t n, double iteration, double decay,
+                                uint64_t seed, double* dev_keys_out, uint64_t* dev_bits_out, int device, void* stream);
+int azmi_samples_select_top(const double* dev_keys, uint32_t n, uint32_t k, int64_t* dev_index_out, azmi_select_record* host_record_out,
+                            int device, void* stream);
+int azmi_samples_window_gather(const void* const* dev_segments, const uint64_t* segment_rows, uint32_t n_segments, uint32_t row_bytes,
+                               const int64_t* dev_index, uint64_t seed, uint64_t pass_index, uint64_t first, uint32_t rows, void* dev_out,
+                               int device, void* stream);
+
 /* ---- the stand-alone MCTS class (py_wrapper.cc:192-220, mcts.h:50-200): one search tree driven call by call.
  * All five games.  A GameState argument is passed as start position (`init`, NULL = initial position, else the
  * game's serialized image as in azmi_game_replay_from) + the moves played from it.  The object owns one pcg32
