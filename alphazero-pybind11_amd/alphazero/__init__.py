@@ -34,7 +34,7 @@ from .drivers import (run_rounds, run_rounds_groups, pipeline_supported, pipelin
                       _tracy_zone_begin, _tracy_zone_end, _tracy_set_thread_name)
 from . import samples
 from .samples import (sample_loss, resample_plan, resample_rows, resample_by_surprise, iteration_losses, sample_metrics, plane_argmax,
-                      eval_metrics, analyze_samples, reservoir_keys, select_top, window_batches, SampleWindow)
+                      eval_metrics, analyze_samples, reservoir_keys, select_top, window_batches, SampleWindow, feature_rank, effective_rank)
 
 
 def __getattr__(name):  # torch-dependent pieces are imported on first use

@@ -127,6 +127,13 @@ class SelectRecordC(C.Structure):      # azmi_select_record
     _fields_ = [("threshold_key", C.c_double), ("selected", C.c_uint64), ("nan_rows", C.c_uint32), ("first_bad_row", C.c_uint32)]
 
 
+FEATURE_RANK_MAX_CHANNELS = 2048      # AZMI_FEATURE_RANK_MAX_CHANNELS
+
+
+class FeatureRankRecordC(C.Structure):      # azmi_feature_rank_record
+    _fields_ = [("trace", C.c_double), ("frob2", C.c_double), ("rank", C.c_double), ("n", C.c_uint32), ("channels", C.c_uint32)]
+
+
 # every symbol include/azmi.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _PP = C.POINTER
@@ -213,6 +220,9 @@ SYMBOLS = {
     "azmi_samples_select_top": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, _PP(SelectRecordC), C.c_int, _VP]),
     "azmi_samples_window_gather": (C.c_int, [_PP(_VP), _PP(C.c_uint64), C.c_uint32, C.c_uint32, _VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                              _VP, C.c_int, _VP]),
+    "azmi_samples_feature_rank": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, _VP, _PP(FeatureRankRecordC), C.c_int, _VP]),
+    "azmi_net_trunk_channels": (C.c_int, [_VP, _PP(C.c_uint32)]),
+    "azmi_net_trunk_features": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP]),
     "azmi_pm_net_forward": (C.c_int, [_VP, _VP, _VP]),
     "azmi_pm_net_forward_group": (C.c_int, [_VP, C.c_uint32, _VP, _VP]),
     "azmi_pm_groups": (C.c_int, [_VP, _PP(C.c_uint32), _PP(C.c_uint32)]),

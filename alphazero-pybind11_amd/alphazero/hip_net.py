@@ -525,6 +525,7 @@ class HipLeafNet:
         (hi + lo bf16 parts, three MFMAs per product; Connect4 family): the 1e-5 tier on the matrix cores; "fp32" = plain fp32
         kernels for any shape."""
         self.desc, blob = fold(net, precision)
+        self.precision, self.device = precision, int(device)
         self._blob = blob
         h = C.c_void_p()
         create = lib.azmi_net_create2 if isinstance(self.desc, NetDesc2C) else lib.azmi_net_create    # dense trunk
@@ -565,6 +566,42 @@ class HipLeafNet:
                                        row_count.data_ptr(), int(max_rows), C.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(lib.azmi_net_last_error().decode())
+
+    @property
+    def trunk_channels(self):
+        """CF, the channels of the trunk's output (azmi_net_trunk_channels): num_channels for a ResNet trunk, in_channels +
+        num_channels * depth for a dense one, whose features begin with the input planes.  precision="fp32" only: every other tier
+        raises RuntimeError naming precision='fp32'."""
+        cf = C.c_uint32()
+        if lib.azmi_net_trunk_channels(self._h, C.byref(cf)) != 0:
+            raise RuntimeError(lib.azmi_net_last_error().decode())
+        return int(cf.value)
+
+    def trunk_features(self, canonical, out=None, stream=None):
+        """The pooled trunk activations NNWrapper.effective_rank reads (neural_net.py:848-866: the output of nnet.conv_layers, then
+        mean(dim=(2, 3))): the stem and trunk launches of forward(), nothing of the heads, and one pooling launch
+        (azmi_net_trunk_features).  canonical: contiguous float32 CUDA tensor [n, C, H, W]; -> float32 [n, trunk_channels] (`out`, or
+        a new tensor), enqueued on `stream` (a raw HIP stream handle, default the current one) with no synchronisation.  A row's bits
+        do not depend on n or on its place in the batch.  precision="fp32" only: every other tier raises RuntimeError naming
+        precision='fp32', before any launch."""
+        what = "trunk_features"
+        cf = self.trunk_channels
+        if not (hasattr(canonical, "is_cuda") and canonical.is_cuda):
+            raise RuntimeError(f"{what}: canonical must be a CUDA tensor, got {type(canonical).__name__}")
+        shape = (self.desc.in_channels, self.desc.height, self.desc.width)
+        if canonical.dtype != torch.float32 or not canonical.is_contiguous() or tuple(canonical.shape[1:]) != shape or canonical.dim() != 4:
+            raise RuntimeError(f"{what}: canonical must be a contiguous float32 [n, {shape[0]}, {shape[1]}, {shape[2]}] tensor, got "
+                               f"{'contiguous' if canonical.is_contiguous() else 'non-contiguous'} {canonical.dtype} {tuple(canonical.shape)}")
+        n = int(canonical.shape[0])
+        if out is None:
+            out = torch.empty((n, cf), dtype=torch.float32, device=canonical.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, cf) and out.device == canonical.device):
+            raise RuntimeError(f"{what}: out must be a contiguous float32 [{n}, {cf}] tensor on {canonical.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        if stream is None:
+            stream = torch.cuda.current_stream(canonical.device).cuda_stream
+        if lib.azmi_net_trunk_features(self._h, canonical.data_ptr(), out.data_ptr(), n, C.c_void_p(int(stream))) != 0:
+            raise RuntimeError(lib.azmi_net_last_error().decode())
+        return out
 
     def process(self, canonical):
         """NNWrapper.process signature: returns (v, pi) probabilities as new float32 tensors."""

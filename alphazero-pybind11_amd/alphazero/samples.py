@@ -14,14 +14,18 @@ reference has for them: eval_metrics (network_pareto.eval_loss, network_pareto.p
 
 Third part (azmi_samples_reservoir_keys / azmi_samples_select_top / azmi_samples_window_gather, csrc/samples_window_kernels.h): the
 history window and the recency-weighted reservoir that training reads - reservoir_keys, select_top, window_batches and the
-SampleWindow that holds them together (calc_hist_size, update_reservoir and train, game_runner.py:955-1008, 1701-1869, 1289-1345)."""
+SampleWindow that holds them together (calc_hist_size, update_reservoir and train, game_runner.py:955-1008, 1701-1869, 1289-1345).
+
+Fourth part (azmi_samples_feature_rank, csrc/feature_rank_kernels.h; azmi_net_trunk_features, csrc/leafnet_f32.hip): feature_rank, the
+participation ratio of a feature matrix from its centred Gram matrix in float64, and effective_rank, NNWrapper.effective_rank
+(neural_net.py:826-873) over the pooled trunk features of an fp32 HipLeafNet."""
 import ctypes as C
 import enum
 
 import numpy as np
 
 from . import _args, _rng
-from ._capi import lib, ResampleRecordC, SampleMetricsRecordC, SelectRecordC, WINDOW_MAX_SEGMENTS
+from ._capi import lib, ResampleRecordC, SampleMetricsRecordC, SelectRecordC, WINDOW_MAX_SEGMENTS, FeatureRankRecordC, FEATURE_RANK_MAX_CHANNELS
 
 MAX_ROWS = 1 << 30
 MAX_ENTRIES = 1 << 20
@@ -964,9 +968,107 @@ class SampleWindow:
                 p += 1
         return run()
 
+    def newest(self):
+        """(iteration, (canonical, v, pi)) of the newest iteration in the window, None for an empty window"""
+        return self._window[-1] if self._window else None
+
     def stats(self):
         return {"window_rows": sum(int(seg[0].shape[0]) for _, seg in self._window),
                 "reservoir_rows": 0 if self._reservoir is None else int(self._reservoir[0].shape[0]),
                 "staged_rows": sum(int(seg[0].shape[0]) for _, seg in self._staged),
                 "window_iterations": [t for t, _ in self._window],
                 "evicted_iterations": self._evicted, "host_syncs": self._syncs}
+
+
+# ---- the participation ratio: feature_rank, effective_rank ------------------------------------------------------------------------
+def _check_features(what, features):
+    """-> (kind, n, C) of a contiguous float32 [n, C] array, 1 <= C <= 2048"""
+    kind = _kind(what, (("features", features),))
+    shape = tuple(features.shape)
+    if len(shape) != 2:
+        raise RuntimeError(f"{what}: features must be an [n, C] array, got shape {shape}")
+    n, Cn = int(shape[0]), int(shape[1])
+    _check_rows(what, n)
+    if not 1 <= Cn <= FEATURE_RANK_MAX_CHANNELS:
+        raise RuntimeError(f"{what}: C must be in [1, {FEATURE_RANK_MAX_CHANNELS}], got {Cn}")
+    _check_dtype(what, "features", features, "float32")
+    return kind, n, Cn
+
+
+def _rank_record(feats_t, mean_t, gram_t, stream):
+    """azmi_samples_feature_rank on a float32 CUDA tensor [n, C] -> the record"""
+    rec = FeatureRankRecordC()
+    _call(lib.azmi_samples_feature_rank(feats_t.data_ptr(), int(feats_t.shape[0]), int(feats_t.shape[1]), None if mean_t is None else mean_t.data_ptr(),
+                                        None if gram_t is None else gram_t.data_ptr(), C.byref(rec), feats_t.device.index,
+                                        _stream_of(feats_t.device, stream)))
+    return rec
+
+
+def feature_rank(features, return_gram=False, return_mean=False, device=0, stream=None):
+    """The participation ratio (sum s^2)^2 / sum s^4 of the singular values s of the column-centred `features` [n, C] (contiguous
+    float32, C <= 2048), the last lines of NNWrapper.effective_rank (neural_net.py:867-873), without the SVD: with G = Fc^T Fc the two
+    sums are tr G and the squared Frobenius norm of G (azmi_samples_feature_rank).  float64 on the float32 features, two passes
+    (the column means, then the centred products); every sum in an order fixed by (n, C), so two calls return the same bits.
+    -> {"rank", "trace" (= sum s^2), "frob2" (= sum s^4), "n", "channels"}, with return_mean "mean" (float64 [C]) and with
+    return_gram "gram" (float64 [C, C]): numpy for a numpy array (staged on `device`), CUDA tensors for a CUDA tensor (used in
+    place on `stream`).  frob2 == 0 exactly (one row, equal rows) gives rank 1.0; n == 0 gives NaN and touches no device.  One
+    synchronisation, the record."""
+    what = "feature_rank"
+    kind, n, Cn = _check_features(what, features)
+    if kind == "numpy":
+        device = _args.device_index(device, what)
+    if n == 0:
+        out = {"rank": float("nan"), "trace": 0.0, "frob2": 0.0, "n": 0, "channels": Cn}
+        if return_mean or return_gram:
+            nan = lambda shape: np.full(shape, np.nan, np.float64)
+            if kind == "torch":
+                import torch
+                nan = lambda shape: torch.full(shape, float("nan"), dtype=torch.float64, device=features.device)
+            if return_mean:
+                out["mean"] = nan((Cn,))
+            if return_gram:
+                out["gram"] = nan((Cn, Cn))
+        return out
+    feats = _stage(features, device) if kind == "numpy" else features
+    import torch
+    mean = _empty(Cn, torch.float64, feats.device, stream) if return_mean else None
+    gram = _empty((Cn, Cn), torch.float64, feats.device, stream) if return_gram else None
+    rec = _rank_record(feats, mean, gram, stream)
+    out = {"rank": float(rec.rank), "trace": float(rec.trace), "frob2": float(rec.frob2), "n": int(rec.n), "channels": int(rec.channels)}
+    if return_mean:
+        out["mean"] = mean.cpu().numpy() if kind == "numpy" else mean
+    if return_gram:
+        out["gram"] = gram.cpu().numpy() if kind == "numpy" else gram
+    return out
+
+
+def effective_rank(canonical, net, batch_rows=65536):
+    """NNWrapper.effective_rank(batch) (neural_net.py:826-873) on the device: the participation ratio of the pooled trunk
+    activations of `net` (a HipLeafNet of precision="fp32", the tier whose arithmetic is the reference's eager fp32 module) over
+    `canonical` [n, C, H, W] (contiguous float32; a numpy array is staged on the net's device, a CUDA tensor used in place).  The
+    net's trunk runs over chunks of `batch_rows` rows into one [n, trunk_channels] float32 array (HipLeafNet.trunk_features), one
+    feature_rank call follows.  -> a float in [1, trunk_channels]; NaN for None or an empty batch.  A HipLeafNet of another tier
+    raises RuntimeError naming precision='fp32'.  The chunking does not change the bits.  One synchronisation, the record."""
+    what = "effective_rank"
+    batch_rows = _args.integer(batch_rows, f"{what}: batch_rows must be an integer >= 1, got {batch_rows!r}", 1)
+    if canonical is None:
+        return float("nan")
+    kind = _kind(what, (("canonical", canonical),))
+    shape = tuple(canonical.shape)
+    if len(shape) != 4:
+        raise RuntimeError(f"{what}: canonical must be an [n, C, H, W] array, got shape {shape}")
+    n = int(shape[0])
+    _check_rows(what, n)
+    _check_dtype(what, "canonical", canonical, "float32")
+    if not hasattr(net, "trunk_features"):
+        raise RuntimeError(f"{what}: net must be a HipLeafNet, got {type(net).__name__}")
+    cf = net.trunk_channels      # (raises for every tier but fp32, before anything is staged or launched)
+    if n == 0:
+        return float("nan")
+    c = _stage(canonical, net.device) if kind == "numpy" else canonical
+    import torch
+    feats = torch.empty((n, cf), dtype=torch.float32, device=c.device)
+    for lo in range(0, n, batch_rows):
+        hi = min(n, lo + batch_rows)
+        net.trunk_features(c[lo:hi], out=feats[lo:hi])
+    return float(_rank_record(feats, None, None, None).rank)

@@ -215,6 +215,29 @@ def training_batches(window, batch_rows, sample_rate=1.0, pass_seed=0):
     return window.batches(batch_rows, sample_rate=sample_rate, pass_seed=pass_seed)
 
 
+def window_effective_rank(window, net, rows=512, seed=0):
+    """The effective-rank diagnostic game_runner tracks after every iteration (game_runner.py:4462-4491: _sample_recent_history_batch,
+    then NNWrapper.effective_rank; `effective_rank_enabled` with 512 positions by default): effective_rank of `net` (an fp32
+    HipLeafNet) over up to `rows` positions of the newest iteration in `window` (a SampleWindow) - all of them when it holds no more,
+    otherwise the first `rows` entries of the window's per-row permutation of that iteration keyed by (seed, pass 0), the rows
+    window_batches([newest], rows, seed, batches=1) yields.  -> a float; NaN for an empty window or an empty iteration."""
+    from . import _args
+    from .samples import SampleWindow, effective_rank, _window_gather
+    what = "window_effective_rank"
+    if not isinstance(window, SampleWindow):
+        raise RuntimeError(f"{what}: window must be a SampleWindow, got {type(window).__name__}")
+    rows = _args.integer(rows, f"{what}: rows must be an integer in [1, 2^30], got {rows!r}", 1, 1 << 30)
+    seed = _args.seed64(seed, what)
+    newest = window.newest()
+    if newest is None:
+        return effective_rank(None, net)
+    canonical = newest[1][0]
+    n = int(canonical.shape[0])
+    if n > rows:
+        canonical = _window_gather([canonical], [n], None, seed, 0, 0, rows, None)
+    return effective_rank(canonical, net)
+
+
 UNIFIED_VARIANT_NAMES =("skirmish", "showdown", "clash", "battle")      # game_runner.py:37
 
 

@@ -630,16 +630,39 @@ int azmi_net_reserve_stream(azmi_net* net, void* stream, uint32_t max_rows) {
 int azmi_net_forward(azmi_net* net, const float* dev_canonical, float* dev_v, float* dev_pi, uint32_t batch, void* stream) {
   return net_forward_live(net, dev_canonical, dev_v, dev_pi, batch, stream, nullptr);
 }
+// the fp32 path keeps ONE set of activation buffers per net: a forward on another stream first waits for the previous
+// one (a correctness path, not a throughput path)
+static void f32_take_buffers(azmi_net* net, void* stream) {
+  if (net->f32_last_stream_set && net->f32_last_stream != stream) (void)hipStreamSynchronize(static_cast<hipStream_t>(net->f32_last_stream));
+  net->f32_last_stream = stream; net->f32_last_stream_set = true;
+}
+// The trunk read-out exists where the trunk's output does: in the fp32 tier's activation buffer.  The matrix-core tiles keep
+// theirs in LDS and registers and are not touched
+static const char* kTrunkOnTile = "the trunk read-out (trunk_channels, trunk_features) runs on the fp32 tier only: the matrix-core tiles keep "
+                                  "their trunk activations on chip; build the net with precision='fp32'";
+int azmi_net_trunk_channels(azmi_net* net, uint32_t* cf) {
+  if (!net || !cf) return nfail(AZMI_ERR_INVALID, "null argument");
+  if (!net->f32) return nfail(AZMI_ERR_INVALID, "%s", kTrunkOnTile);
+  *cf = azmi_f32::trunk_channels(net->f32);
+  return AZMI_OK;
+}
+int azmi_net_trunk_features(azmi_net* net, const float* dev_canonical, float* dev_features, uint32_t batch, void* stream) {
+  if (!net) return nfail(AZMI_ERR_INVALID, "null argument");
+  if (!net->f32) return nfail(AZMI_ERR_INVALID, "%s", kTrunkOnTile);
+  if (batch == 0) return AZMI_OK;
+  if (!dev_canonical || !dev_features) return nfail(AZMI_ERR_INVALID, "null argument");
+  f32_take_buffers(net, stream);
+  const char* msg = "";
+  const int rc = azmi_f32::trunk_features(net->f32, dev_canonical, dev_features, batch, stream, &msg);
+  return rc == AZMI_OK ? rc : nfail(rc, "%s", msg);
+}
 // `live`: device-side count of real rows at the front of the batch (row-list evaluation), NULL = all of them
 static int net_forward_live(azmi_net* net, const float* dev_canonical, float* dev_v, float* dev_pi, uint32_t batch, void* stream,
                             const uint32_t* live) {
   if (!net || !dev_canonical || !dev_v || !dev_pi) return nfail(AZMI_ERR_INVALID, "null argument");
   if (batch == 0) return AZMI_OK;
   if (net->f32) {
-    // the fp32 path keeps ONE set of activation buffers per net: a forward on another stream first waits for the previous
-    // one (a correctness path, not a throughput path)
-    if (net->f32_last_stream_set && net->f32_last_stream != stream) (void)hipStreamSynchronize(static_cast<hipStream_t>(net->f32_last_stream));
-    net->f32_last_stream = stream; net->f32_last_stream_set = true;
+    f32_take_buffers(net, stream);
     const char* msg = "";
     const int rc = azmi_f32::forward(net->f32, dev_canonical, dev_v, dev_pi, batch, stream, &msg);
     return rc == AZMI_OK ? rc : nfail(rc, "%s", msg);

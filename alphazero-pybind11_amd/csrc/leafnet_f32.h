@@ -16,6 +16,10 @@ size_t blob_bytes(const azmi_net_desc* d, bool dense, Variant var = Variant{});
 // returns AZMI_OK or a negative status; *err receives a static/thread-local message
 int create(const azmi_net_desc* d, bool dense, const void* blob, size_t bytes, int device, void** impl, const char** err, Variant var = Variant{});
 int forward(void* impl, const float* canon, float* v, float* pi, uint32_t batch, void* stream, const char** err);
+// the trunk read-out: CF = the channels the heads read (a dense trunk: every feature, the input planes first), and
+// feat[b][c] = the mean over the H*W cells of the trunk's output - forward()'s stem and trunk launches, none of the heads'
+uint32_t trunk_channels(void* impl);
+int trunk_features(void* impl, const float* canon, float* feat, uint32_t batch, void* stream, const char** err);
 int reserve(void* impl, uint32_t batch, const char** err);
 void destroy(void* impl);
 void dims(void* impl, uint32_t* chw, uint32_t* p1, uint32_t* m);   // floats per canonical row, P+1, M

@@ -355,19 +355,30 @@ int create(const azmi_net_desc* d, bool dense, const void* blob, size_t bytes, i
   return AZMI_OK;
 }
 
-int forward(void* impl, const float* canon, float* v_out, float* pi_out, uint32_t B, void* stream, const char** err) {
-  auto* n = static_cast<Net*>(impl);
-  if (B > n->rows) { const int rc = reserve(n, B, err); if (rc != AZMI_OK) return rc; }
-  const azmi_net_desc& d = n->d;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int CH = d.channels, KK = d.kernel_size * d.kernel_size, CF = static_cast<int>(trunk_out(&d, n->dense));
-  const int H = d.height, W = d.width, HW = H * W, HC = d.head_channels, Hd = d.v_hidden, P1 = d.num_players + 1, M = d.num_moves;
-  const float* p = n->blob;
-  auto take = [&](size_t count) { const float* q = p; p += count; return q; };
+}  // namespace azmi_f32
+
+namespace {
+
+// One batch through the net: the launches forward() and trunk_features() share.  trunk() runs the stem and the trunk layer by layer
+// and leaves the output of nnet.conv_layers, [B][CF][HW], in `s` (t and u are free again); heads() reads it.
+struct Pass {
+  Net* n;
+  const azmi_net_desc& d;
+  const float* canon;
+  uint32_t B;
+  hipStream_t st;
+  const int CH, KK, CF, H, W, HW;
+  const float* p;            // the next weight of the blob
+  float *s, *t, *u;
+  Pass(Net* net, const float* canonical, uint32_t batch, void* stream)
+      : n(net), d(net->d), canon(canonical), B(batch), st(static_cast<hipStream_t>(stream)), CH(d.channels), KK(d.kernel_size * d.kernel_size),
+        CF(static_cast<int>(trunk_out(&d, net->dense))), H(d.height), W(d.width), HW(d.height * d.width), p(net->blob), s(net->buf[0]),
+        t(net->buf[1]), u(net->buf[2]) {}
+  const float* take(size_t count) { const float* q = p; p += count; return q; }
   // `at`: {channels per row of in, channels per row of out, first output channel}; the default is a dense [B][c][HW] on both sides
   struct At { int in_ctot, out_ctot, out_coff; };
-  auto convk = [&](const float* in, const float* w, const float* b, const float* pa, const float* pb, const float* res, float* out, int cin, int cout, int relu,
-                   At at = At{0, 0, 0}) {
+  void convk(const float* in, const float* w, const float* b, const float* pa, const float* pb, const float* res, float* out, int cin, int cout, int relu,
+             At at = At{0, 0, 0}) {
     if (at.in_ctot == 0) at = At{cin, cout, 0};
     const size_t total = static_cast<size_t>(B) * cout * HW;
     const uint32_t grid = static_cast<uint32_t>((total + 255) / 256);
@@ -377,20 +388,19 @@ int forward(void* impl, const float* canon, float* v_out, float* pi_out, uint32_
       case 5: k_conv<5><<<grid, 256, 0, st>>>(in, w, b, pa, pb, res, out, B, cin, cout, H, W, relu, at.in_ctot, at.out_ctot, at.out_coff); break;
       default: k_conv<7><<<grid, 256, 0, st>>>(in, w, b, pa, pb, res, out, B, cin, cout, H, W, relu, at.in_ctot, at.out_ctot, at.out_coff); break;
     }
-  };
-  auto conv1 = [&](const float* in, const float* w, const float* b, const float* pa, const float* pb, float* out, int cin, int cout, int relu, int in_ctot) {
+  }
+  void conv1(const float* in, const float* w, const float* b, const float* pa, const float* pb, float* out, int cin, int cout, int relu, int in_ctot) {
     const size_t total = static_cast<size_t>(B) * cout * HW;
     k_conv<1><<<static_cast<uint32_t>((total + 255) / 256), 256, 0, st>>>(in, w, b, pa, pb, nullptr, out, B, cin, cout, H, W, relu, in_ctot, cout, 0);
-  };
-  auto fc = [&](const float* in, const float* w, const float* b, float* out, int K, int N, int relu) {
+  }
+  void fc(const float* in, const float* w, const float* b, float* out, int K, int N, int relu) {
     const size_t total = static_cast<size_t>(B) * N;
     k_fc<<<static_cast<uint32_t>((total + 255) / 256), 256, 0, st>>>(in, w, b, out, B, K, N, relu);
-  };
-  float *s = n->buf[0], *t = n->buf[1], *u = n->buf[2];
-  const bool layer = n->var.trunk_norm != 0, crelu = n->var.trunk_act != 0;
+  }
   // a trunk convolution of a variant: act(norm(in)) through w (+ bias) (+ res); k = 1 or the net's kernel size
-  auto convv = [&](int k, const float* in, const float* w, const float* b, const float* g, const float* beta, const float* stats, const float* res,
-                   float* out, int cin, int cout, At at) {
+  void convv(int k, const float* in, const float* w, const float* b, const float* g, const float* beta, const float* stats, const float* res,
+             float* out, int cin, int cout, At at) {
+    const bool crelu = n->var.trunk_act != 0;
     const size_t total = static_cast<size_t>(B) * cout * HW;
     const uint32_t grid = static_cast<uint32_t>((total + 255) / 256);
 #define AZMI_CONV_V(KS) \
@@ -403,10 +413,16 @@ int forward(void* impl, const float* canon, float* v_out, float* pi_out, uint32_
       default: AZMI_CONV_V(7); break;
     }
 #undef AZMI_CONV_V
-  };
-  auto row_stats = [&](const float* in, int channels, int ctot) {   // over the first `channels` of rows that hold ctot
+  }
+  void row_stats(const float* in, int channels, int ctot) {   // over the first `channels` of rows that hold ctot
     k_row_stats<<<(B + 3) / 4, 256, 0, st>>>(in, n->stats, B, static_cast<uint32_t>(channels * HW), static_cast<size_t>(ctot) * HW);
-  };
+  }
+  void trunk();
+  void heads(float* v_out, float* pi_out);
+};
+
+void Pass::trunk() {
+  const bool layer = n->var.trunk_norm != 0, crelu = n->var.trunk_act != 0;
   const int A = crelu ? 2 : 1;
   if (!layer && !crelu) {      // the image and the launches of the first descriptor
     if (n->dense) {  // s = every feature [B][CF][HW]: the planes, then G channels per block
@@ -474,6 +490,10 @@ int forward(void* impl, const float* canon, float* v_out, float* pi_out, uint32_
       float* x = s; s = u; u = x;
     }
   }
+}
+
+void Pass::heads(float* v_out, float* pi_out) {
+  const int HC = d.head_channels, Hd = d.v_hidden, P1 = d.num_players + 1, M = d.num_moves;
   {  // value head
     const float* wv = take(static_cast<size_t>(HC) * CF); const float* bv = take(HC);
     conv1(s, wv, bv, nullptr, nullptr, t, CF, HC, 1, CF);
@@ -541,8 +561,37 @@ int forward(void* impl, const float* canon, float* v_out, float* pi_out, uint32_
       k_softmax<<<(B + 3) / 4, 256, 0, st>>>(n->small[0], pi_out, B, M, 0, 0);
     }
   }
+}
+
+}  // namespace
+
+namespace azmi_f32 {
+
+int forward(void* impl, const float* canon, float* v_out, float* pi_out, uint32_t B, void* stream, const char** err) {
+  auto* n = static_cast<Net*>(impl);
+  if (B > n->rows) { const int rc = reserve(n, B, err); if (rc != AZMI_OK) return rc; }
+  Pass pass(n, canon, B, stream);
+  pass.trunk();
+  pass.heads(v_out, pi_out);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(err, AZMI_ERR_NO_DEVICE, "fp32 leaf net launch", e);
+  return AZMI_OK;
+}
+
+uint32_t trunk_channels(void* impl) {
+  auto* n = static_cast<Net*>(impl);
+  return static_cast<uint32_t>(trunk_out(&n->d, n->dense));
+}
+
+int trunk_features(void* impl, const float* canon, float* feat_out, uint32_t B, void* stream, const char** err) {
+  auto* n = static_cast<Net*>(impl);
+  if (B > n->rows) { const int rc = reserve(n, B, err); if (rc != AZMI_OK) return rc; }
+  Pass pass(n, canon, B, stream);
+  pass.trunk();
+  // feats.mean(dim=(2, 3)): one thread per (row, channel) adds the HW cells in ascending order (k_avgpool, as the heads pool)
+  k_avgpool<<<static_cast<uint32_t>((static_cast<size_t>(B) * pass.CF + 255) / 256), 256, 0, pass.st>>>(pass.s, feat_out, B, pass.CF, pass.HW);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(err, AZMI_ERR_NO_DEVICE, "fp32 leaf net trunk launch", e);
   return AZMI_OK;
 }
 

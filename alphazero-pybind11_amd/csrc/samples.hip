@@ -5,6 +5,8 @@
 // asynchronous launch each, azmi_sample_metrics_reduce synchronises once for its record.
 // And the history window and the reservoir of samples_window_kernels.h: azmi_samples_reservoir_keys and
 // azmi_samples_window_gather are one asynchronous launch each, azmi_samples_select_top synchronises once for its record.
+// And the participation ratio of feature_rank_kernels.h: azmi_samples_feature_rank is five launches and synchronises once for its
+// record.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -19,6 +21,7 @@
 #include "samples_kernels.h"
 #include "sample_metrics_kernels.h"
 #include "samples_window_kernels.h"
+#include "feature_rank_kernels.h"
 #include "samples_layout.h"
 
 namespace {
@@ -29,6 +32,8 @@ static_assert(sizeof(SampleMetricsRecord) == sizeof(azmi_sample_metrics_record),
 static_assert(kSampleMetricColumns == AZMI_SAMPLE_METRIC_COLUMNS && kMetricMaxBuckets == AZMI_SAMPLE_METRIC_MAX_BUCKETS, "the header's sizes");
 static_assert(offsetof(SelectState, prefix) == sizeof(azmi_select_record), "azmi_select_record is the head of the device state");
 static_assert(kWindowMaxSegments == AZMI_WINDOW_MAX_SEGMENTS, "the header's sizes");
+static_assert(sizeof(FeatureRankRecord) == sizeof(azmi_feature_rank_record), "azmi_feature_rank_record is the device record");
+static_assert(kRankMaxChannels == AZMI_FEATURE_RANK_MAX_CHANNELS, "the header's sizes");
 
 thread_local std::string g_samples_err;
 
@@ -67,6 +72,7 @@ DevBlock g_plan_scratch[kPlanMaxDevices];
 
 DevBlock g_metrics_scratch[kPlanMaxDevices];      // the same for azmi_sample_metrics_reduce, under the same mutex
 DevBlock g_select_scratch[kPlanMaxDevices];       // and for azmi_samples_select_top
+DevBlock g_rank_scratch[kPlanMaxDevices];         // and for azmi_samples_feature_rank
 
 uint32_t tiles_of(uint32_t n) { return (n + kPlanBlock - 1) / kPlanBlock; }
 
@@ -394,6 +400,48 @@ int azmi_samples_window_gather(const void* const* dev_segments, const uint64_t* 
   else k_window_gather<uint32_t><<<grid, kWindowThreads, 0, st>>>(seg, pm, dev_index, first, rows, row_bytes / 4u, static_cast<uint32_t*>(dev_out));
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? AZMI_OK : hip_fail("k_window_gather", e);
+}
+
+// ---- the participation ratio of a feature matrix (feature_rank_kernels.h) ------------------------------------------------------------
+int azmi_samples_feature_rank(const float* dev_features, uint32_t n, uint32_t C, double* dev_mean_out, double* dev_gram_out,
+                              azmi_feature_rank_record* host_record_out, int device, void* stream) {
+  const char* what = "azmi_samples_feature_rank";
+  if (!host_record_out) return sfail(AZMI_ERR_INVALID, "%s: null argument", what);
+  *host_record_out = azmi_feature_rank_record{0.0, 0.0, std::nan(""), n, C};
+  if (n > kPlanMaxRows) return sfail(AZMI_ERR_INVALID, "%s: n = %u: at most %u rows", what, n, kPlanMaxRows);
+  if (C == 0 || C > kRankMaxChannels) return sfail(AZMI_ERR_INVALID, "%s: C = %u: 1 to %u channels", what, C, kRankMaxChannels);
+  if (n == 0) return AZMI_OK;      // (the reference: nan on an empty batch)
+  if (!dev_features) return sfail(AZMI_ERR_INVALID, "%s: null argument", what);
+  if (reinterpret_cast<uintptr_t>(dev_features) % 4u || reinterpret_cast<uintptr_t>(dev_mean_out) % 8u || reinterpret_cast<uintptr_t>(dev_gram_out) % 8u)
+    return sfail(AZMI_ERR_INVALID, "%s: the features are dword-aligned, the float64 outputs 8-byte aligned", what);
+  if (device >= kPlanMaxDevices) return sfail(AZMI_ERR_INVALID, "%s: device %d: at most %d devices", what, device, kPlanMaxDevices);
+  DeviceScope scope;
+  int rc = scope.enter(what, device); if (rc) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const RankPlan plan = rank_plan(n, C);
+  const uint32_t blocks = plan.pairs * (kRankTileCells / kRankThreads);
+  RankScratch<FeatureRankRecord> rs;
+  BlockCut size;
+  cut_rank_scratch(size, rs, C, plan.sum_slabs, size_t(plan.slabs) * plan.pairs * kRankTileCells, blocks);
+  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  DevBlock& sc = g_rank_scratch[device];
+  hipError_t e = sc.reserve(size.off);      // allocates on the first call on this device, or for a larger one than any before
+  if (e != hipSuccess) return hip_fail(what, e);
+  BlockCut cut(sc.p);
+  cut_rank_scratch(cut, rs, C, plan.sum_slabs, size_t(plan.slabs) * plan.pairs * kRankTileCells, blocks);
+  // pass one, the column means; pass two, the centred products per (tile pair, slab); the slabs summed, the trace and the norm
+  k_rank_colsum<<<dim3((C + 63) / 64, plan.sum_slabs), 64, 0, st>>>(dev_features, n, C, plan.sum_slab_rows, rs.col_part);
+  k_rank_mean<<<(C + kRankThreads - 1) / kRankThreads, kRankThreads, 0, st>>>(rs.col_part, plan.sum_slabs, C, n, rs.mean, dev_mean_out);
+  k_rank_gram<<<dim3(plan.pairs, plan.slabs), kRankThreads, 0, st>>>(dev_features, n, C, rs.mean, plan.tiles, plan.slab_rows, rs.gram_part);
+  k_rank_reduce<<<dim3(kRankTileCells / kRankThreads, plan.pairs), kRankThreads, 0, st>>>(rs.gram_part, plan.slabs, C, plan.tiles, dev_gram_out,
+                                                                                          rs.block_trace, rs.block_frob2);
+  k_rank_final<<<1, kRankThreads, 0, st>>>(rs.block_trace, rs.block_frob2, blocks, n, C, rs.rec);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(host_record_out, rs.rec, sizeof *host_record_out, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);      // the one synchronisation; always: what was queued uses the block the next call reuses
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return hip_fail(what, e);
+  return AZMI_OK;
 }
 
 }  // extern "C"

@@ -51,4 +51,23 @@ void cut_select_scratch(BlockCut& c, SelectScratch<State>& s, size_t t0, size_t 
   s.top = c.take<uint64_t>(1);
 }
 
+// azmi_samples_feature_rank: the record (32 bytes) | the Gram parts per (slab, tile pair), which the kernel stores 16 bytes at a
+// time and which therefore come first | the column means | the column sums per slab | the reduction's per-workgroup shares of the
+// trace and of the squared norm
+template <class Rec>
+struct RankScratch {
+  Rec* rec;
+  double *gram_part, *mean, *col_part, *block_trace, *block_frob2;
+};
+template <class Rec>
+void cut_rank_scratch(BlockCut& c, RankScratch<Rec>& r, size_t channels, size_t sum_slabs, size_t gram_cells, size_t blocks) {
+  static_assert(sizeof(Rec) % 16 == 0, "the Gram parts behind the record are 16-byte aligned");
+  r.rec = c.take<Rec>(1);
+  r.gram_part = c.take<double>(gram_cells);
+  r.mean = c.take<double>(channels);
+  r.col_part = c.take<double>(sum_slabs * channels);
+  r.block_trace = c.take<double>(blocks);
+  r.block_frob2 = c.take<double>(blocks);
+}
+
 }  // namespace azmi

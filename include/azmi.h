@@ -446,6 +446,25 @@ int azmi_samples_window_gather(const void* const* dev_segments, const uint64_t* 
                                const int64_t* dev_index, uint64_t seed, uint64_t pass_index, uint64_t first, uint32_t rows, void* dev_out,
                                int device, void* stream);
 
+/* ---- the participation ratio of a feature matrix (NNWrapper.effective_rank, neural_net.py:865-873; csrc/feature_rank_kernels.h,
+ *      DESIGN.md §8.5.3).  The conventions of the blocks above.  dev_features: [n][C] float32, 1 <= C <= 2048.  In float64: the column
+ *      means (a first pass), G = Fc^T Fc of the centred columns (a second pass; never S2 - S1 S1^T / n), trace = tr G = the sum of
+ *      the squared singular values of Fc, frob2 = |G|_F^2 = the sum of their fourth powers, rank = trace^2 / frob2 - the
+ *      reference's figure without an SVD.  frob2 == 0 exactly (one row, equal rows) gives rank 1.0, n == 0 gives NaN and touches no
+ *      device.  Every sum runs in an order fixed by (n, C): two calls return the same bits.  dev_mean_out ([C] float64) and
+ *      dev_gram_out ([C][C] float64, both triangles) may be NULL.  Five launches; synchronises `stream` once, to hand back the
+ *      record; the scratch block is kept per device. */
+#define AZMI_FEATURE_RANK_MAX_CHANNELS 2048
+typedef struct azmi_feature_rank_record {
+  double trace;
+  double frob2;
+  double rank;
+  uint32_t n;
+  uint32_t channels;
+} azmi_feature_rank_record;
+int azmi_samples_feature_rank(const float* dev_features, uint32_t n, uint32_t C, double* dev_mean_out, double* dev_gram_out,
+                              azmi_feature_rank_record* host_record_out, int device, void* stream);
+
 /* ---- the stand-alone MCTS class (py_wrapper.cc:192-220, mcts.h:50-200): one search tree driven call by call.
  * All five games.  A GameState argument is passed as start position (`init`, NULL = initial position, else the
  * game's serialized image as in azmi_game_replay_from) + the moves played from it.  The object owns one pcg32
@@ -835,6 +854,19 @@ int azmi_net_forward(azmi_net* net, const float* dev_canonical, float* dev_v, fl
  * leaf really needs the net (cache hits, terminal leaves and retired slots do not). */
 int azmi_net_forward_rows(azmi_net* net, const float* dev_canonical, float* dev_v, float* dev_pi, const uint32_t* dev_rows,
                           const uint32_t* dev_row_count, uint32_t max_rows, void* stream);
+/* The trunk read-out behind NNWrapper.effective_rank (neural_net.py:826-873: a forward hook on nnet.conv_layers, then
+ * feats.mean(dim=(2, 3))), on the fp32 tier, whose forward keeps the trunk's output [batch][CF][H*W] in a buffer of its own.
+ *   trunk_channels  *cf = CF: `channels` for a ResNet trunk, in_channels + channels * depth for a dense one (whose features
+ *                   begin with the input planes).
+ *   trunk_features  the stem and trunk launches of azmi_net_forward and nothing of the heads, then dev_features[b][c]
+ *                   (float32 [batch][CF]) = the mean of channel c over the H*W cells, added in ascending cell order by one thread:
+ *                   a row's bits do not depend on `batch` or on the row's place in it.  Stream-ordered, no synchronisation with
+ *                   the host (it shares the fp32 tier's activation buffers with azmi_net_forward: a call on another stream first
+ *                   waits for the previous one, as there).  batch == 0 touches no device.
+ * A net of another precision tier (the matrix-core tiles keep their trunk in LDS) fails both with AZMI_ERR_INVALID and a message
+ * naming precision='fp32', before any launch. */
+int azmi_net_trunk_channels(azmi_net* net, uint32_t* cf);
+int azmi_net_trunk_features(azmi_net* net, const float* dev_canonical, float* dev_features, uint32_t batch, void* stream);
 /* NNWrapper.process on HOST arrays (neural_net.py:800-823 behind game_runner.py:651-726's batcher -> gpu_loop -> result_worker):
  * canonical [n,C,H,W] -> v [n,P+1], pi [n,M]; copies in, runs the net, copies out, synchronously, on a stream and staging
  * buffers private to the calling thread (any number of host threads may call it at once).  The signature is that of a
