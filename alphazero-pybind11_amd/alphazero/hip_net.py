@@ -1,4 +1,4 @@
-"""Host side of the fused MFMA leaf net (csrc/leafnet.hip): BatchNorm folding, bf16 conversion and
+"""Host side of the fused MFMA leaf net (csrc/leafnet.hip and its family units leafnet_*_host.hip): BatchNorm folding, bf16 conversion and
 the MFMA-fragment weight layout, plus the ctypes wrapper `HipLeafNet`.
 
 Weight blob layout (little-endian, in this order; `frag` = [k-step][m-tile][lane 0..63][8 bf16] where
@@ -159,7 +159,7 @@ def fold_spatial(net, x3=False):
                            "channels, one extra conv per head); use precision='fp32' for other shapes")
     pc = spec.policy_shape[0]
     Hd, L, P1 = spec.v_fc_hidden, spec.v_fc_layers, spec.num_players + 1
-    # the bounds of azmi_net_create (csrc/leafnet.hip) that the paddings below rely on, with its messages
+    # the bounds of azmi_net_create (csrc/leafnet_sp_host.hip refusal) that the paddings below rely on, with its messages
     if pc > 32 or not 0 <= spec.num_moves - pc * H * W <= 32:
         raise RuntimeError("spatial head: policy channels <= 32, 0..32 global actions")
     if spec.num_moves > pc * H * W and (spec.pi_fc_hidden < 64 or spec.pi_fc_hidden > 1024 or spec.pi_fc_hidden % 64):
@@ -302,7 +302,7 @@ def fold_dense(net):
     Cin, H, W = spec.in_shape
     G, D, K = spec.num_channels, spec.depth, spec.kernel_size
     tail = "; use precision='fp32' for other shapes"
-    # the bounds of azmi_net_create2 (csrc/leafnet.hip dense_refusal), with its messages
+    # the bounds of azmi_net_create2 (csrc/leafnet_dense_host.hip refusal), with its messages
     layer = spec.trunk_norm == "layer"
     if spec.trunk_act != "relu" or spec.pi_fc_layers > 0:   # (crelu would double K beyond the LDS plan; no tile has the policy FC stack)
         raise RuntimeError("dense leaf net kernel: trunk_act='relu' and pi_fc_layers=0 only; use precision='fp32' for crelu and the policy FC stack")
@@ -366,7 +366,7 @@ def fold_dense_spatial(net):
     Cin, H, W = spec.in_shape
     G, D, K = spec.num_channels, spec.depth, spec.kernel_size
     tail = "; use precision='fp32' for other shapes"
-    # the bounds of azmi_net_create2 (csrc/leafnet.hip dense_sp_refusal), with its messages
+    # the bounds of azmi_net_create2 (csrc/leafnet_dense_sp_host.hip refusal), with its messages
     if spec.trunk_act != "relu" or spec.pi_fc_layers > 0:
         raise RuntimeError("dense leaf net kernel: trunk_act='relu' and pi_fc_layers=0 only; use precision='fp32' for crelu and the policy FC stack")
     if spec.trunk_norm != "batch":
@@ -455,7 +455,7 @@ def fold(net, precision="bf16"):
     if precision not in ("bf16", "bf16x3"):
         raise ValueError("precision must be 'bf16', 'bf16x3' or 'fp32'")
     tile_layer = spec.dense_net and not x3 and spec.trunk_norm == "layer" and spec.trunk_act == "relu" and spec.pi_fc_layers == 0
-    if is_variant(spec) and not tile_layer:    # azmi_net_create2's refusal (csrc/leafnet.hip kVariantOnTile), before anything is laid out
+    if is_variant(spec) and not tile_layer:    # azmi_net_create2's refusal (csrc/leafnet.hip resolve2, kVariantOnTile), before anything is laid out
         raise RuntimeError("the matrix-core tiles cover trunk_act='relu' and pi_fc_layers=0, with trunk_norm='batch' or, on the dense "
                            "Connect4 tile (precision 'bf16'), 'layer'; use precision='fp32' for the other layer-norm nets, crelu and "
                            "the policy FC stack")

@@ -12,8 +12,6 @@
 
 using namespace azmi;
 
-extern "C" int azmi_net_reserve_stream(struct azmi_net* net, void* stream, uint32_t max_rows);    // leafnet.hip (declared in leafnet_c4.h)
-
 int azmi_host_read_ctl(azmi_pm* pm, hipStream_t st, Control* out, bool settle) {
   if (settle) azmi_host_launch_settle(pm, st);
   AZMI_HIP_TRY(hipMemcpyAsync(out, pm->ar.ctl, sizeof(Control), hipMemcpyDeviceToHost, st));

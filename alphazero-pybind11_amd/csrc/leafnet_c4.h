@@ -1,5 +1,5 @@
-// Device code of the Connect4-family leaf net (k_leafnet_c4), shared by leafnet.hip (the plain launch behind azmi_net_forward*)
-// and engine.hip (the fused net + move-step launch of a split round).  See leafnet.hip for the architecture it restates.
+// Device code of the Connect4-family leaf net (k_leafnet_c4), shared by leafnet_c4_host.hip (the plain launch behind
+// azmi_net_forward*) and engine.hip (the fused net + move-step launch of a split round).  See leafnet.hip for the architecture it restates.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -749,7 +749,3 @@ __global__ __launch_bounds__(NTH, 2) void k_leafnet_c4(NetDesc nd, NetPtrs np, c
 }  // namespace c4
 
 }  // namespace azmi_net_dev
-
-// allocates the per-stream scratch a forward of up to `max_rows` rows on `stream` needs (a forward allocates it on first use,
-// which a stream capture does not allow); 0 = ok
-extern "C" int azmi_net_reserve_stream(struct azmi_net* net, void* stream, uint32_t max_rows);

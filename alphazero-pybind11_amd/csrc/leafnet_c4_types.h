@@ -27,7 +27,8 @@ struct NetPtrs {           // device pointers into the folded weight blob
 
 }  // namespace azmi_net_dev
 
-// the net object behind the C ABI (leafnet.hip owns it; engine.hip reads nd / np / lds_bytes for the fused launch)
+// the Connect4-family net behind the C ABI as its launches need it (leafnet_c4_host.hip fills it; engine.hip and the pipeline
+// read nd / np / lds_bytes for their fused launches)
 struct azmi_net_c4_view {
   azmi_net_dev::NetDesc nd;
   azmi_net_dev::NetPtrs np;
@@ -37,3 +38,6 @@ struct azmi_net_c4_view {
 // fills `out` when `net` is a Connect4-family net on the matrix cores (bf16, or bf16x3: out->x3 - the lock-step engine's fused
 // launch takes the bf16 tile only and checks the flag); returns 0 otherwise
 extern "C" int azmi_net_c4_view_get(const struct azmi_net* net, azmi_net_c4_view* out);
+// allocates the per-stream scratch a forward of up to `max_rows` rows on `stream` needs (a forward allocates it on first use,
+// which a stream capture does not allow); 0 = ok
+extern "C" int azmi_net_reserve_stream(struct azmi_net* net, void* stream, uint32_t max_rows);

@@ -884,7 +884,7 @@ __global__ __launch_bounds__(HFC_THREADS) void k_heads_fc(SpDesc nd, SpPtrs np, 
       }
     }
   }
-}   // (nets with global actions take the split form: leafnet.hip, fc_split)
+}   // (nets with global actions take the split form: leafnet_sp_host.hip, fc_split)
 
 }  // namespace sp
 }  // namespace azmi_net_dev

@@ -1,5 +1,5 @@
 """Shared by the tests of the dense spatial-head tile (csrc/leafnet_dense_sp.h, hip_net.fold_dense_spatial): the table of shapes
-at both ends of every bound `dense_sp_refusal` states (csrc/leafnet.hip), the shapes it must refuse with a fragment of the
+at both ends of every bound `refusal` states (csrc/leafnet_dense_sp_host.hip), the shapes it must refuse with a fragment of the
 message expected, and the nets with scaled output layers.
 
 Nets are one block deep with growth 8 on the 7x7 board unless the case is about something else; the fp64 forward of

@@ -1,5 +1,5 @@
 """No device needed: the host half of the dense spatial-head tile - hip_net.fold_dense_spatial, the validation of
-azmi_net_blob_bytes2 / azmi_net_create2 (dense_sp_refusal in csrc/leafnet.hip), which runs before any device call, and
+azmi_net_blob_bytes2 / azmi_net_create2 (refusal in csrc/leafnet_dense_sp_host.hip), which runs before any device call, and
 torch_net.stargambit_variant_dense_spec.
 """
 import ctypes as C
