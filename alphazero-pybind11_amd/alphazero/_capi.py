@@ -223,6 +223,8 @@ SYMBOLS = {
     "azmi_samples_feature_rank": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP, _VP, _PP(FeatureRankRecordC), C.c_int, _VP]),
     "azmi_net_trunk_channels": (C.c_int, [_VP, _PP(C.c_uint32)]),
     "azmi_net_trunk_features": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP]),
+    "azmi_net_refresh": (C.c_int, [_VP, _VP, C.c_uint32, _VP]),
+    "azmi_net_blob_read": (C.c_int, [_VP, _VP, C.c_size_t]),
     "azmi_pm_net_forward": (C.c_int, [_VP, _VP, _VP]),
     "azmi_pm_net_forward_group": (C.c_int, [_VP, C.c_uint32, _VP, _VP]),
     "azmi_pm_groups": (C.c_int, [_VP, _PP(C.c_uint32), _PP(C.c_uint32)]),

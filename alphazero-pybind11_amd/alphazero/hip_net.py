@@ -9,6 +9,7 @@ element j of lane l is  W[co = 16*mt + (l & 15)][k = 32*ks + 8*(l >> 4) + j]):
   v_fc1 W^T[32][hidden] b[hidden] | v_fc2 W[P+1][hidden] b[P+1]  (f32) | pi_fc1: per pixel p frag hi(W[m][c*HW+p]) frag lo | b[M] f32
 """
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import torch
@@ -85,6 +86,17 @@ lib.azmi_net_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
 lib.azmi_net_forward_rows.restype = C.c_int
 lib.azmi_net_forward_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
 lib.azmi_net_last_error.restype = C.c_char_p
+
+
+class NetParamC(C.Structure):
+    """azmi_net_param (include/azmi.h): one tensor of the table azmi_net_refresh reads."""
+    _fields_ = [("data", C.c_void_p), ("count", C.c_uint64), ("kind", C.c_uint32), ("reserved", C.c_uint32), ("eps", C.c_double)]
+
+
+lib.azmi_net_refresh.restype = C.c_int
+lib.azmi_net_refresh.argtypes = [C.c_void_p, C.POINTER(NetParamC), C.c_uint32, C.c_void_p]
+lib.azmi_net_blob_read.restype = C.c_int
+lib.azmi_net_blob_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
 
 
 def _bf16_bits(x):
@@ -517,6 +529,59 @@ def fold(net, precision="bf16"):
     return desc, bytes(blob)
 
 
+# AZMI_PARAM_* (include/azmi.h)
+PARAM_CONV_W, PARAM_BN_WEIGHT, PARAM_BN_BIAS, PARAM_BN_MEAN, PARAM_BN_VAR, PARAM_FC_W, PARAM_FC_B = range(7)
+_BN_TENSORS = (("weight", PARAM_BN_WEIGHT), ("bias", PARAM_BN_BIAS), ("running_mean", PARAM_BN_MEAN), ("running_var", PARAM_BN_VAR))
+
+
+def _refresh_family(spec, precision):
+    """Which of the two families HipLeafNet.refresh is built for a (spec, precision) belongs to: "resnet" (the Connect4 ResNet
+    flat-head tile, fold lines for "bf16" / "bf16x3") or "dense" (the dense Connect4 tile's batch-norm instance, fold_dense).  The
+    decision tree is fold()'s; every other family raises RuntimeError naming itself."""
+    if precision == "fp32":
+        other = "the fp32 tier"
+    elif precision not in ("bf16", "bf16x3"):
+        raise ValueError("precision must be 'bf16', 'bf16x3' or 'fp32'")
+    elif spec.dense_net and spec.policy_shape is not None and tuple(spec.in_shape[1:]) != (6, 7):
+        other = "the dense spatial-head tile"
+    elif spec.dense_net and spec.trunk_norm == "layer":
+        other = "the dense tile's layer-norm instance"
+    elif is_variant(spec):
+        other = "a layer-norm / crelu / policy-FC-stack net"
+    elif spec.dense_net:
+        return "dense"
+    elif spec.policy_shape is not None:
+        other = "the spatial-head tile"
+    else:
+        return "resnet"
+    raise RuntimeError(f"refresh is built for the Connect4 ResNet flat-head tile and the dense Connect4 tile (batch norm), not for {other}: "
+                       "build a new HipLeafNet from the trained model")
+
+
+def refresh_names(spec, precision="bf16"):
+    """The ordered tensor names (state_dict keys) of the table HipLeafNet.refresh hands to azmi_net_refresh: every tensor fold() /
+    fold_dense() reads for this family, each once - the table order of csrc/leafnet_c4_host.hip / leafnet_dense_host.hip
+    (refresh_plan).  Pure Python, no device.  Families refresh is not built for raise RuntimeError naming the family."""
+    family = _refresh_family(spec, precision)
+
+    def bn(prefix):
+        return [f"{prefix}.{t}" for t, _ in _BN_TENSORS]
+    names = (["conv1.weight"] + bn("bn1")) if family == "resnet" else []      # (a dense trunk has no stem)
+    for i in range(spec.depth):
+        pre = f"conv_layers.{i}."
+        names += bn(pre + "bn1") + [pre + "conv1.weight"] + bn(pre + "bn2") + [pre + "conv2.weight"]
+    names += ["v_conv.weight"] + bn("v_bn") + ["pi_conv.weight"] + bn("pi_bn")
+    return names + ["v_fc1.weight", "v_fc1.bias", "v_fc2.weight", "v_fc2.bias", "pi_fc1.weight", "pi_fc1.bias"]
+
+
+def _param_kind(module, tensor):
+    if isinstance(module, torch.nn.BatchNorm2d):
+        return dict(_BN_TENSORS)[tensor]
+    if isinstance(module, torch.nn.Linear):
+        return PARAM_FC_W if tensor == "weight" else PARAM_FC_B
+    return PARAM_CONV_W
+
+
 class HipLeafNet:
     """The fused MFMA kernel as an evaluator: forward(canonical, v_out, pi_out) on device tensors."""
 
@@ -526,6 +591,7 @@ class HipLeafNet:
         kernels for any shape."""
         self.desc, blob = fold(net, precision)
         self.precision, self.device = precision, int(device)
+        self.spec = dataclasses.replace(net.spec)      # what refresh() compares a model against
         self._blob = blob
         h = C.c_void_p()
         create = lib.azmi_net_create2 if isinstance(self.desc, NetDesc2C) else lib.azmi_net_create    # dense trunk
@@ -566,6 +632,61 @@ class HipLeafNet:
                                        row_count.data_ptr(), int(max_rows), C.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(lib.azmi_net_last_error().decode())
+
+    def refresh(self, net, stream=None):
+        """The weights of the trained `net` (a torch_net.LeafNet on this net's GPU) written into THIS net in place
+        (azmi_net_refresh): HIP kernels read the float32 parameters and buffers where they are, fold the BatchNorms in float64 and
+        lay the image out, byte for byte the blob fold(net, precision) makes; nothing is copied to the host, nothing waits for the
+        device, the handle and every engine, MCTSBatch or pipeline view holding it stay valid.  Returns self.
+        Order: enqueued on `stream` (a raw HIP stream handle, default the current one).  A forward enqueued on that stream before the
+        call sees the old weights whole, one enqueued after it the new ones whole; a forward on ANOTHER stream is the caller's to
+        order against the refresh.  The model's tensors are read when the stream gets there: an optimiser step on another stream
+        must be ordered behind it too.
+        Refusals, all before any launch (the weights stay what they were): a spec that differs from the one this net was built with
+        (ValueError naming the first differing field); a tensor that is missing, not float32, not contiguous or not on this net's
+        device (RuntimeError naming it); a family refresh is not built for - the spatial-head tiles, the dense spatial tile, the dense
+        layer-norm instance, the fp32 tier - (RuntimeError naming it: build a new HipLeafNet).
+        A position cache filled under the old weights keeps serving the old answers: start a new one (selfplay.refresh_net)."""
+        names = refresh_names(self.spec, self.precision)
+        spec = getattr(net, "spec", None)
+        if spec is None:
+            raise ValueError("refresh: the model has no spec (a torch_net.LeafNet is expected)")
+        for f in dataclasses.fields(self.spec):
+            old, new = getattr(self.spec, f.name), getattr(spec, f.name)
+            if (tuple(old) if isinstance(old, (list, tuple)) else old) != (tuple(new) if isinstance(new, (list, tuple)) else new):
+                raise ValueError(f"refresh: the model's spec differs from the one this net was built with in {f.name}: {new!r}, built with {old!r}")
+        tensors = dict(net.named_parameters())
+        tensors.update(net.named_buffers())
+        table = (NetParamC * len(names))()
+        for rec, name in zip(table, names):
+            t = tensors.get(name)
+            if t is None:
+                raise RuntimeError(f"refresh: the model has no tensor {name}")
+            if not t.is_cuda or t.device.index != self.device:
+                raise RuntimeError(f"refresh: {name} is on {t.device}, this net is on cuda:{self.device}")
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"refresh: {name} is {t.dtype}, float32 is expected")
+            if not t.is_contiguous():
+                raise RuntimeError(f"refresh: {name} is not contiguous")
+            prefix, _, leaf = name.rpartition(".")
+            module = net.get_submodule(prefix)
+            rec.data, rec.count, rec.kind = t.data_ptr(), t.numel(), _param_kind(module, leaf)
+            rec.eps = float(module.eps) if leaf == "running_var" else 0.0
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        if lib.azmi_net_refresh(self._h, table, len(names), C.c_void_p(int(stream))) != 0:
+            raise RuntimeError(lib.azmi_net_last_error().decode())
+        self._blob = None      # (the image of the constructor's model: no longer what the device holds)
+        return self
+
+    def blob(self):
+        """The live weight image read back from the device (azmi_net_blob_read; synchronises: tests and debugging).  The fp32 tier
+        keeps its image to itself and raises RuntimeError."""
+        n = blob_bytes(self.desc)
+        out = C.create_string_buffer(n)
+        if lib.azmi_net_blob_read(self._h, out, n) != 0:
+            raise RuntimeError(lib.azmi_net_last_error().decode())
+        return out.raw
 
     @property
     def trunk_channels(self):

@@ -215,6 +215,23 @@ def training_batches(window, batch_rows, sample_rate=1.0, pass_seed=0):
     return window.batches(batch_rows, sample_rate=sample_rate, pass_seed=pass_seed)
 
 
+def refresh_net(hip, model, caches=(), stream=None):
+    """The hand-off from training back to self-play (game_runner.py:2043-2051 loads the iteration's checkpoint): hip.refresh(model) -
+    the trained LeafNet's weights written into the live HipLeafNet on the device, no new handle - and then clear() on every cache
+    given: a position cache filled under the old weights serves stale answers (the reference builds a fresh cache per self_play
+    call, game_runner.py:2013-2060).  ShardedS3FIFOCache has no clear(): a caller that keeps one across iterations builds a new one
+    instead of passing it here, and an engine (PlayManager with max_cache_size > 0, MCTSBatch given a cache) that outlives the
+    refresh keeps its own cache with the old answers in it: build the engine anew, as self_play does per call.  A cache without
+    clear() is a TypeError before anything is refreshed.  Returns hip."""
+    for c in caches:
+        if not callable(getattr(c, "clear", None)):
+            raise TypeError(f"refresh_net: {type(c).__name__} has no clear(); build a new cache after the refresh instead")
+    hip.refresh(model, stream=stream)
+    for c in caches:
+        c.clear()
+    return hip
+
+
 def window_effective_rank(window, net, rows=512, seed=0):
     """The effective-rank diagnostic game_runner tracks after every iteration (game_runner.py:4462-4491: _sample_recent_history_batch,
     then NNWrapper.effective_rank; `effective_rank_enabled` with 512 positions by default): effective_rank of `net` (an fp32

@@ -201,6 +201,7 @@ int upload(const void* blob, size_t blob_bytes, int device, azmi_net** out) {
 void release(azmi_net* net) {
   (void)hipSetDevice(net->device);
   delete net->family;
+  free_refresh(net->refresh);
   (void)hipFree(net->blob);
   net->free_scratch();
   delete net;
@@ -372,6 +373,16 @@ void azmi_net_eval_host(const float* canonical, uint32_t n, float* v, float* pi,
   ok = ok && hipMemcpyAsync(pi, ctx.pi, static_cast<size_t>(n) * m * 4, hipMemcpyDeviceToHost, ctx.st) == hipSuccess;
   ok = ok && hipStreamSynchronize(ctx.st) == hipSuccess;
   if (!ok) poison();
+}
+
+int azmi_net_blob_read(azmi_net* net, void* host_out, size_t bytes) {
+  if (!net || !host_out) return nfail(AZMI_ERR_INVALID, "null argument");
+  if (!net->blob) return nfail(AZMI_ERR_INVALID, "azmi_net_blob_read: the fp32 tier keeps its weight image to itself");
+  if (bytes != net->blob_bytes) return nfail(AZMI_ERR_INVALID, "azmi_net_blob_read: %zu bytes asked for, the weight image has %zu", bytes, net->blob_bytes);
+  if (hipSetDevice(net->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(host_out, net->blob, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return nfail(AZMI_ERR_NO_DEVICE, "azmi_net_blob_read: reading the weight image back failed");
+  return AZMI_OK;
 }
 
 int azmi_net_c4_view_get(const azmi_net* net, azmi_net_c4_view* out) {

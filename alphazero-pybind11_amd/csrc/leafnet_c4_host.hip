@@ -82,6 +82,41 @@ struct C4Family : Family {
     out->lds_bytes = x3 ? tier->big.lds : tier->small.lds;   // (bf16: the engine's fused launch runs the small tile)
     return 1;
   }
+  // layout() again, as what each section is made FROM (alphazero/hip_net.py fold; the table order is hip_net.refresh_names)
+  bool refresh_plan(azmi_refresh::Plan* plan) const override {
+    using namespace azmi_refresh;
+    PlanBuilder b{*plan};
+    const uint32_t cin = nd.C_in, pix = nd.H * nd.W, hd = nd.v_hidden, p1 = nd.num_players + 1, m = nd.num_moves;
+    const uint32_t n3 = x3 ? 3 : 1, lo3 = x3 ? 4 : 0;      // trunk and heads: high, high, low parts; the stem: high, low
+    const uint32_t conv1 = b.param("conv1.weight", CH * cin * 9, AZMI_PARAM_CONV_W);
+    const uint32_t bn1 = b.bn("bn1", CH);
+    b.frag(frag_of(conv1, bn1, CH, MT, 2, cin, 0, cin, 9, x3 ? 2 : 1, x3 ? 2 : 0), 1);      // k = tap * C_in + ci, zero behind 9 * C_in
+    b.f32(F32_BN_B, bn1, CH, CH);
+    for (int i = 0; i < nd.depth; ++i) {
+      const std::string pre = "conv_layers." + std::to_string(i) + ".";
+      const uint32_t n1 = b.bn(pre + "bn1", CH);
+      const uint32_t w1 = b.param(pre + "conv1.weight", CH * CH * 9, AZMI_PARAM_CONV_W);
+      const uint32_t n2 = b.bn(pre + "bn2", CH);
+      const uint32_t w2 = b.param(pre + "conv2.weight", CH * CH * 9, AZMI_PARAM_CONV_W);
+      b.f32(F32_BN_A, n1, CH, CH); b.f32(F32_BN_B, n1, CH, CH); b.f32(F32_BN_B, n2, CH, CH);
+      b.frag(frag_of(w1, n2, CH, MT, 2, CH, 1, CH, 9, n3, lo3), 9);      // one chunk per tap: k = tap * 64 + ci
+      b.frag(frag_of(w2, NO_BN, CH, MT, 2, CH, 1, CH, 9, n3, lo3), 9);
+    }
+    const uint32_t vc = b.param("v_conv.weight", HC * CH, AZMI_PARAM_CONV_W);
+    const uint32_t vb = b.bn("v_bn", HC);
+    const uint32_t pc = b.param("pi_conv.weight", HC * CH, AZMI_PARAM_CONV_W);
+    const uint32_t pb = b.bn("pi_bn", HC);
+    b.frag(head_frag(vc, vb, pc, pb, 2, CH, n3, lo3), 1);
+    b.f32(F32_BN_B, vb, HC, HC); b.f32(F32_BN_B, pb, HC, HC);
+    b.f32(F32_FRAG, b.param("v_fc1.weight", hd * HC, AZMI_PARAM_FC_W), hd * HC, hd * HC, HC);
+    b.f32(F32_COPY, b.param("v_fc1.bias", hd, AZMI_PARAM_FC_B), hd, hd);
+    b.f32(F32_COPY, b.param("v_fc2.weight", p1 * hd, AZMI_PARAM_FC_W), p1 * hd, p1 * hd);
+    b.f32(F32_COPY, b.param("v_fc2.bias", p1, AZMI_PARAM_FC_B), p1, p1);
+    // per pixel p the high parts of W_p[m][c] = W[m][c * HW + p], then the low parts: W as [m][32 channels][HW "taps"], chunk = p
+    b.frag(frag_of(b.param("pi_fc1.weight", m * HC * pix, AZMI_PARAM_FC_W), NO_BN, m, 1, 1, HC, 1, HC, pix, 2, 2), pix);
+    b.f32(F32_COPY, b.param("pi_fc1.bias", m, AZMI_PARAM_FC_B), m, m);
+    return true;
+  }
 };
 
 int make(const azmi_net_desc* d, azmi_net* net) {

@@ -66,6 +66,40 @@ struct DenseFamily : Family {
     return AZMI_OK;
   }
   void dims(uint32_t* chw, uint32_t* p1, uint32_t* m) const override { *chw = dd.C_in * dn::PIX; *p1 = dd.num_players + 1; *m = dd.num_moves; }
+  // layout<false>() again, as what each section is made FROM (alphazero/hip_net.py fold_dense; the table order is
+  // hip_net.refresh_names).  The layer-norm instance folds nothing and has no plan
+  bool layer = false;
+  bool refresh_plan(azmi_refresh::Plan* plan) const override {
+    using namespace azmi_refresh;
+    if (layer) return false;
+    PlanBuilder b{*plan};
+    const uint32_t g = dd.G, kk = dd.K * dd.K, cf = dd.CF, cfp = dd.CFP, hd = dd.v_hidden, p1 = dd.num_players + 1, m = dd.num_moves;
+    const uint32_t m1 = dn::round_up(4 * dd.G, 16), k2 = dn::round_up(4 * dd.G, 32);
+    for (int i = 0; i < dd.depth; ++i) {
+      const std::string pre = "conv_layers." + std::to_string(i) + ".";
+      const uint32_t ci = dd.C_in + dd.G * i, cip = dn::round_up(dd.C_in + dd.G * i, 32);
+      const uint32_t n1 = b.bn(pre + "bn1", ci);
+      const uint32_t w1 = b.param(pre + "conv1.weight", 4 * g * ci, AZMI_PARAM_CONV_W);
+      const uint32_t n2 = b.bn(pre + "bn2", 4 * g);
+      const uint32_t w2 = b.param(pre + "conv2.weight", g * 4 * g * kk, AZMI_PARAM_CONV_W);
+      b.f32(F32_BN_A, n1, cfp, ci); b.f32(F32_BN_B, n1, cfp, ci); b.f32(F32_BN_B, n2, 64, 4 * g);
+      b.frag(frag_of(w1, n2, 4 * g, m1 / 16, cip / 32, cip, 0, ci, 1), 1);      // rows = bn2-scaled conv1, k = input channel
+      b.frag(frag_of(w2, NO_BN, g, 1, k2 / 32, k2, 1, 4 * g, kk), kk);           // per tap: rows = the G outputs, k = bottleneck channel
+    }
+    const uint32_t vc = b.param("v_conv.weight", dn::HC1 * cf, AZMI_PARAM_CONV_W);
+    const uint32_t vb = b.bn("v_bn", dn::HC1);
+    const uint32_t pc = b.param("pi_conv.weight", dn::HC1 * cf, AZMI_PARAM_CONV_W);
+    const uint32_t pb = b.bn("pi_bn", dn::HC1);
+    b.f32(F32_BN_B, vb, dn::HC1, dn::HC1); b.f32(F32_BN_B, pb, dn::HC1, dn::HC1);
+    b.frag(head_frag(vc, vb, pc, pb, cfp / 32, cf), 1);
+    b.f32(F32_COPY, b.param("v_fc1.weight", hd * dn::HC1, AZMI_PARAM_FC_W), hd * dn::HC1, hd * dn::HC1);
+    b.f32(F32_COPY, b.param("v_fc1.bias", hd, AZMI_PARAM_FC_B), hd, hd);
+    b.f32(F32_COPY, b.param("v_fc2.weight", p1 * hd, AZMI_PARAM_FC_W), p1 * hd, p1 * hd);
+    b.f32(F32_COPY, b.param("v_fc2.bias", p1, AZMI_PARAM_FC_B), p1, p1);
+    b.f32(F32_COPY, b.param("pi_fc1.weight", m * dn::HC1 * dn::PIX, AZMI_PARAM_FC_W), m * dn::HC1 * dn::PIX, m * dn::HC1 * dn::PIX);
+    b.f32(F32_COPY, b.param("pi_fc1.bias", m, AZMI_PARAM_FC_B), m, m);
+    return true;
+  }
 };
 
 template <bool LAYER>
@@ -75,6 +109,7 @@ int make(const azmi_net_desc* d, azmi_net* net) {
   f->dd = dense_desc(d);
   BlobCursor c{static_cast<const uint8_t*>(net->blob)};
   f->dp = layout<LAYER>(d, c);
+  f->layer = LAYER;
   f->kernel = &dn::k_leafnet_dense<LAYER>;
   f->lds = dn::lds_bytes(f->dd);
   // the kernel is shared by every dense net of the process: the attribute is what the widest accepted net asks for

@@ -16,6 +16,7 @@
 #include "../../include/azmi.h"
 #include "host_error.h"
 #include "leafnet_c4_types.h"
+#include "leafnet_refresh_types.h"
 
 namespace azmi_net_host {
 
@@ -41,7 +42,12 @@ struct Family {
   // the trunk read-out: refused (leafnet.hip, kTrunkOnTile) unless the family keeps its trunk's output in memory
   virtual int trunk_channels(uint32_t* cf);
   virtual int trunk_features(const float* canon, float* features, uint32_t batch, void* stream);
+  // azmi_net_refresh: the family's parameter list and the region map of its image; false = refresh is not built for this family
+  virtual bool refresh_plan(azmi_refresh::Plan* plan) const { return false; }
 };
+// what azmi_net_refresh keeps per net from its first call on (leafnet_refresh.hip): plan, table, scratch, staging image
+struct RefreshState;
+void free_refresh(RefreshState* state);
 
 // A matrix-core family, registered once (leafnet.hip, resolve / resolve2 name the records).  azmi_net_create* calls refusal,
 // compares the blob with blob_bytes - both before the device is touched - uploads the image and calls make.
@@ -77,6 +83,8 @@ struct azmi_net {
   void* blob = nullptr;      // the weight image on the device (the fp32 tier keeps its own: leafnet_f32.hip)
   size_t blob_bytes = 0;
   azmi_net_host::Family* family = nullptr;
+  std::mutex refresh_mu;
+  azmi_net_host::RefreshState* refresh = nullptr;
   // Scratch between the kernels of one forward: PER STREAM - engines on different streams share one net object and run
   // their forwards concurrently (round 1 kept one buffer per net: the value heads of concurrent shards read each other's
   // pooled features)

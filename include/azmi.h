@@ -867,6 +867,35 @@ int azmi_net_forward_rows(azmi_net* net, const float* dev_canonical, float* dev_
  * naming precision='fp32', before any launch. */
 int azmi_net_trunk_channels(azmi_net* net, uint32_t* cf);
 int azmi_net_trunk_features(azmi_net* net, const float* dev_canonical, float* dev_features, uint32_t batch, void* stream);
+/* The hand-off from training back to self-play without the host (the reference reloads a checkpoint once per iteration,
+ * game_runner.py:2043-2051): the weight image of a LIVE net rewritten in place from the trained model's float32 parameters where
+ * they are in device memory.  Kernels fold the BatchNorms in float64 (a = w / sqrt(var + eps), b = bias - mean * a), lay out the MFMA
+ * fragments (double -> float32 -> bf16, both to nearest even; bf16x3: high and low parts) and write the image into a staging copy
+ * allocated by the first call; one device-to-device copy on `stream` moves it into the live image.  The result is byte for byte the
+ * blob alphazero/hip_net.py::fold() makes of the same parameters.  The handle, its device pointers (azmi_net_c4_view) and every
+ * engine holding them stay valid.
+ *   params       HOST array, one record per tensor the family's fold reads, in the family's order (alphazero/hip_net.py
+ *                refresh_names): `data` = device pointer to contiguous float32 on the net's device, `count` = elements, `kind` as
+ *                below, `eps` = the BatchNorm's eps on its running_var record (0 elsewhere), `reserved` = 0.  The count, every kind,
+ *                every element count and every pointer's device are checked BEFORE anything is enqueued: a mismatch is
+ *                AZMI_ERR_INVALID with a message naming the tensor, and the weights are untouched.
+ *   stream       the order: a forward enqueued on `stream` before the call reads the old weights whole, one enqueued after it the new
+ *                ones whole.  No host synchronisation (the table goes up as one small pinned copy on the stream) - except that a
+ *                call first waits for the previous refresh OF THE SAME NET to finish, whose table and staging image it reuses.  A
+ *                forward on ANOTHER stream is the caller's to order against the refresh (an event), as for any write to shared memory.
+ * Built for the two Connect4 families self-play runs: the ResNet flat-head tile (precision 0 and 2) and the dense Connect4 tile's
+ * batch-norm instance.  Every other family - the spatial-head tiles, the dense spatial tile, the dense layer-norm instance, the fp32
+ * tier - answers AZMI_ERR_INVALID "refresh is not built for this family" before any launch: create a new net for those.  A position
+ * cache filled under the old weights still serves the old answers: the caller starts a new one (the reference builds one per
+ * self_play call, game_runner.py:2013-2060). */
+enum { AZMI_PARAM_CONV_W = 0, AZMI_PARAM_BN_WEIGHT = 1, AZMI_PARAM_BN_BIAS = 2, AZMI_PARAM_BN_MEAN = 3, AZMI_PARAM_BN_VAR = 4,
+       AZMI_PARAM_FC_W = 5, AZMI_PARAM_FC_B = 6 };
+typedef struct azmi_net_param { const void* data; uint64_t count; uint32_t kind; uint32_t reserved; double eps; } azmi_net_param;
+int azmi_net_refresh(azmi_net* net, const azmi_net_param* params, uint32_t n_params, void* stream);
+/* The live weight image read back into host_out (tests and debugging): synchronises the device.  `bytes` must be the image's size
+ * (azmi_net_blob_bytes*): anything else is AZMI_ERR_INVALID and nothing is written; so is a net of the fp32 tier, which keeps its
+ * image to itself. */
+int azmi_net_blob_read(azmi_net* net, void* host_out, size_t bytes);
 /* NNWrapper.process on HOST arrays (neural_net.py:800-823 behind game_runner.py:651-726's batcher -> gpu_loop -> result_worker):
  * canonical [n,C,H,W] -> v [n,P+1], pi [n,M]; copies in, runs the net, copies out, synchronously, on a stream and staging
  * buffers private to the calling thread (any number of host threads may call it at once).  The signature is that of a
