@@ -27,7 +27,7 @@ from .search_batch_pool import pool_unique
 from .search_batch import MCTSBatch
 from .opening_tree import build_opening_tree, OpeningTree, OpeningNode, temperature_at_depth, node_seed
 from .evaluators import dumb_eval, playout_eval_batch, playout_eval
-from .cache import ShardedS3FIFOCache, S3FIFOCache
+from .cache import ShardedS3FIFOCache, S3FIFOCache, cached_forward
 from .play_manager import GameData, PlayManager, _f32
 from .drivers import (run_rounds, run_rounds_groups, pipeline_supported, pipeline_supported_groups, run_pipeline, run_pipeline_groups,
                       _pipe_stats, _PIPE_KEYS, pipeline_log_duplicates, cache_find_group, cache_insert_locked, rng_probe, tracy_is_enabled, tracy_frame_mark,

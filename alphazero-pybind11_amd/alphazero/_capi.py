@@ -184,6 +184,10 @@ SYMBOLS = {
     "azmi_cache_find_many": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP]),
     "azmi_cache_stats": (C.c_int, [_VP, _VP]),
     "azmi_cache_last_error": (C.c_char_p, []),
+    "azmi_cache_find_rows": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "azmi_cache_insert_rows": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint32, _VP]),
+    "azmi_net_forward_cached": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
+    "azmi_search_leaf_keys": (C.c_int, [_VP, _VP, _PP(C.c_void_p), _PP(C.c_uint32)]),
     "azmi_run_rounds": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP]),
     "azmi_run_rounds_groups": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "azmi_run_pipeline": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint64, _VP, _VP]),

@@ -10,7 +10,7 @@ class _Span:
         }
 
 
-_TYPESTR = {"torch.float32": "<f4", "torch.uint32": "<u4", "torch.int32": "<i4", "torch.uint8": "|u1"}
+_TYPESTR = {"torch.float32": "<f4", "torch.int64": "<i8", "torch.uint32": "<u4", "torch.int32": "<i4", "torch.uint8": "|u1"}
 
 
 def device_tensor(ptr, shape, dtype, device):

@@ -358,6 +358,26 @@ class MCTSBatch(_Sweep, _Pool, _Frontier):
         return (device_tensor(pc.value, (n.value,) + self._chw, torch.float32, dev),
                 device_tensor(pt.value, (n.value,), torch.int32, dev))
 
+    def leaf_keys(self):
+        """The engine key (hash_game_state) of every row of the last find_leaves(), in row order: an int64 CUDA tensor [n_rows]
+        (the key's 64 bits; a view of the object's buffer, valid until the next find_leaves).  The find kernel hashed every leaf
+        it handed out - the device hash search() and capture_roots() use - and one launch brings the keys into row order, so a
+        step with a cache reads
+            canonical, tree = mb.find_leaves()
+            v, pi, hit = alphazero.cached_forward(net, cache, canonical, mb.leaf_keys())
+            mb.process_results(v, pi)
+        (with leaves_per_step > 1 a key of 0 reads 0x9E3779B97F4A7C15, the value every cache stores it as)."""
+        if self._rows is None:
+            raise RuntimeError("leaf_keys: no leaf batch is pending; call find_leaves first")
+        import torch
+        from ._torch_view import device_tensor
+        pk, n = C.c_void_p(), C.c_uint32()
+        check(lib.azmi_search_leaf_keys(self._h, _ENGINE_STREAM, C.byref(pk), C.byref(n)))
+        dev = torch.device("cuda", self._device)
+        if n.value == 0:
+            return torch.zeros(0, dtype=torch.int64, device=dev)
+        return device_tensor(pk.value, (n.value,), torch.int64, dev)
+
     def process_results(self, v, pi, root_noise=False):
         """The evaluator's answers for the rows of the last find_leaves(): v [n_rows, P+1], pi [n_rows, M] probabilities,
         device tensors or numpy arrays."""

@@ -10,7 +10,9 @@
 
 #include "../../include/azmi.h"
 #include "cache_host.h"
+#include "cache_rows_kernels.h"
 #include "host_error.h"
+#include "leafnet_host.h"
 
 using namespace azmi;
 
@@ -120,6 +122,51 @@ int find_many(azmi_cache* c, uint32_t group_lanes, const uint64_t* hashes, uint3
   return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "cache find: %s", hipGetErrorString(e));
 }
 
+// ---- the device-pointer entries: scratch and launches (cache_rows_kernels.h) -----------------------------------------------------
+// the scratch of `n` rows: the first call and a larger n only (synchronous, outside the steady state, like the leaf nets'
+// per-stream staging); every other call finds it there
+int rows_reserve(azmi_cache* c, uint32_t n) {
+  if (c->rows_scratch && n <= c->rows_cap) return AZMI_OK;
+  (void)hipDeviceSynchronize();      // an earlier call may still be using the old block
+  if (c->rows_scratch) (void)hipFree(c->rows_scratch);
+  c->rows_scratch = nullptr; c->rows_cap = 0;
+  const size_t words = 1 + static_cast<size_t>(n) + rows_groups(n);
+  if (hipMalloc(reinterpret_cast<void**>(&c->rows_scratch), words * 4) != hipSuccess) return cfail(AZMI_ERR_OOM, "hipMalloc(cache row scratch) failed");
+  c->rows_cap = n;
+  return AZMI_OK;
+}
+uint32_t* rows_miss_count(azmi_cache* c) { return c->rows_scratch; }
+uint32_t* rows_miss_rows(azmi_cache* c) { return c->rows_scratch + 1; }
+uint32_t* rows_offs(azmi_cache* c) { return c->rows_scratch + 1 + c->rows_cap; }
+
+// find (+ the ordered miss list when miss_rows is given) enqueued on st; arguments checked by the callers
+int enqueue_find_rows(azmi_cache* c, const uint64_t* keys, uint32_t n, uint8_t* hit, float* pi, float* v, uint32_t* miss_rows, uint32_t* miss_count,
+                      hipStream_t st) {
+  if (wave_layout(c->c)) k_cache_find_rows<true><<<(n + 31u) / 32u, 256, 0, st>>>(c->c, keys, n, hit, pi, v);
+  else k_cache_find_rows<false><<<(n + 255u) / 256u, 256, 0, st>>>(c->c, keys, n, hit, pi, v);
+  if (miss_rows) {
+    k_cache_miss_scan<<<1, kRowsScanThreads, 0, st>>>(hit, n, rows_offs(c), miss_count);
+    k_cache_miss_scatter<<<(n + 255u) / 256u, 256, 0, st>>>(hit, n, rows_offs(c), miss_rows);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "cache find_rows launch: %s", hipGetErrorString(e));
+}
+
+int enqueue_insert_rows(azmi_cache* c, const uint64_t* keys, const float* pi, const float* v, const uint32_t* rows, const uint32_t* row_count,
+                        uint32_t n_max, hipStream_t st) {
+  if (wave_layout(c->c)) {
+    const uint32_t chunks = rows_chunks(n_max, kApplyMax);      // in order on the one stream; a chunk behind *row_count exits at once
+    for (uint32_t k = 0; k < chunks; ++k) {
+      const uint32_t m = std::min<uint32_t>(kApplyMax, n_max - k * kApplyMax);
+      k_cache_insert_rows_wave<<<(m + 3) / 4, 256, 0, st>>>(c->c, keys, pi, v, rows, row_count, n_max, k);
+    }
+  } else {
+    k_cache_insert_rows<<<(c->c.shards + 63) / 64, 64, 0, st>>>(c->c, keys, pi, v, rows, row_count, n_max);
+  }
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? AZMI_OK : cfail(AZMI_ERR_NO_DEVICE, "cache insert_rows launch: %s", hipGetErrorString(e));
+}
+
 }  // namespace
 
 
@@ -177,6 +224,61 @@ int azmi_cache_find_many(azmi_cache* c, const uint64_t* hashes, uint32_t n, uint
   if (!c || (n && (!hashes || !hit || !policy || !value))) return cfail(AZMI_ERR_INVALID, "null argument");
   if (n == 0) return AZMI_OK;
   return find_many(c, wave_layout(c->c) ? 8u : 0u, hashes, n, hit, policy, value);
+}
+
+int azmi_cache_find_rows(azmi_cache* c, const uint64_t* d_keys, uint32_t n, uint8_t* d_hit, float* d_pi, float* d_v, uint32_t* d_miss_rows,
+                         uint32_t* d_miss_count, void* stream) {
+  if (!c) return cfail(AZMI_ERR_INVALID, "azmi_cache_find_rows: null argument: cache");
+  if (n == 0) return AZMI_OK;
+  if (!d_keys) return cfail(AZMI_ERR_INVALID, "azmi_cache_find_rows: null argument: d_keys");
+  if (!d_hit) return cfail(AZMI_ERR_INVALID, "azmi_cache_find_rows: null argument: d_hit");
+  if (!d_pi) return cfail(AZMI_ERR_INVALID, "azmi_cache_find_rows: null argument: d_pi");
+  if (!d_v) return cfail(AZMI_ERR_INVALID, "azmi_cache_find_rows: null argument: d_v");
+  if (!d_miss_rows != !d_miss_count)
+    return cfail(AZMI_ERR_INVALID, "azmi_cache_find_rows: d_miss_rows and d_miss_count go together (both, or neither for no compaction)");
+  if (n > kRowsMax) return cfail(AZMI_ERR_INVALID, "azmi_cache_find_rows: n = %u, at most 2^30 rows per call", n);
+  if (hipSetDevice(c->device) != hipSuccess) return cfail(AZMI_ERR_NO_DEVICE, "hipSetDevice failed");
+  if (d_miss_rows) { const int rc = rows_reserve(c, n); if (rc != AZMI_OK) return rc; }
+  return enqueue_find_rows(c, d_keys, n, d_hit, d_pi, d_v, d_miss_rows, d_miss_count, static_cast<hipStream_t>(stream));
+}
+
+int azmi_cache_insert_rows(azmi_cache* c, const uint64_t* d_keys, const float* d_pi, const float* d_v, const uint32_t* d_rows,
+                           const uint32_t* d_row_count, uint32_t n_max, void* stream) {
+  if (!c) return cfail(AZMI_ERR_INVALID, "azmi_cache_insert_rows: null argument: cache");
+  if (n_max == 0) return AZMI_OK;
+  if (!d_keys) return cfail(AZMI_ERR_INVALID, "azmi_cache_insert_rows: null argument: d_keys");
+  if (!d_pi) return cfail(AZMI_ERR_INVALID, "azmi_cache_insert_rows: null argument: d_pi");
+  if (!d_v) return cfail(AZMI_ERR_INVALID, "azmi_cache_insert_rows: null argument: d_v");
+  if (n_max > kRowsMax) return cfail(AZMI_ERR_INVALID, "azmi_cache_insert_rows: n_max = %u, at most 2^30 rows per call", n_max);
+  if (hipSetDevice(c->device) != hipSuccess) return cfail(AZMI_ERR_NO_DEVICE, "hipSetDevice failed");
+  return enqueue_insert_rows(c, d_keys, d_pi, d_v, d_rows, d_row_count, n_max, static_cast<hipStream_t>(stream));
+}
+
+int azmi_net_forward_cached(azmi_net* net, azmi_cache* c, const float* d_canon, const uint64_t* d_keys, uint32_t n, float* d_v, float* d_pi,
+                            uint8_t* d_hit, void* stream) {
+  if (!net) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: null argument: net");
+  if (!c) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: null argument: cache");
+  if (n == 0) return AZMI_OK;
+  if (!d_canon) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: null argument: d_canon");
+  if (!d_keys) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: null argument: d_keys");
+  if (!d_v) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: null argument: d_v");
+  if (!d_pi) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: null argument: d_pi");
+  if (!d_hit) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: null argument: d_hit");
+  if (n > kRowsMax) return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: n = %u, at most 2^30 rows per call", n);
+  uint32_t chw, p1, m;
+  net->family->dims(&chw, &p1, &m);
+  if (c->c.np != m || c->c.nv != p1)
+    return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: cache: num_policy = %u, num_value = %u, but the net answers %u moves and %u values",
+                 c->c.np, c->c.nv, m, p1);
+  if (c->device != net->device)
+    return cfail(AZMI_ERR_INVALID, "azmi_net_forward_cached: cache: it lives on device %d, the net on device %d", c->device, net->device);
+  if (hipSetDevice(c->device) != hipSuccess) return cfail(AZMI_ERR_NO_DEVICE, "hipSetDevice failed");
+  int rc = rows_reserve(c, n); if (rc != AZMI_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  rc = enqueue_find_rows(c, d_keys, n, d_hit, d_pi, d_v, rows_miss_rows(c), rows_miss_count(c), st); if (rc != AZMI_OK) return rc;
+  rc = azmi_net_forward_rows(net, d_canon, d_v, d_pi, rows_miss_rows(c), rows_miss_count(c), n, stream);
+  if (rc != AZMI_OK) return cfail(rc, "azmi_net_forward_cached: leaf net: %s", azmi_net_last_error());
+  return enqueue_insert_rows(c, d_keys, d_pi, d_v, rows_miss_rows(c), rows_miss_count(c), n, st);
 }
 
 int azmi_debug_cache_find_group(azmi_cache* c, uint32_t group_lanes, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy, float* value) {
@@ -251,6 +353,7 @@ int azmi_debug_shard_index(int device, uint32_t shards, const uint64_t* hashes, 
 int azmi_cache_stats(azmi_cache* c, uint64_t out[6]) {
   if (!c || !out) return cfail(AZMI_ERR_INVALID, "null argument");
   (void)hipSetDevice(c->device);
+  (void)hipDeviceSynchronize();      // the device-pointer entries run on the caller's streams: read behind all of them
   std::vector<unsigned long long> st(static_cast<size_t>(c->c.shards) * 4);
   std::vector<uint32_t> state(static_cast<size_t>(c->c.shards) * 8);
   if (hipMemcpy(st.data(), c->c.stats, st.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||

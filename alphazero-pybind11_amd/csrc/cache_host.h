@@ -48,5 +48,12 @@ struct azmi_cache {
   std::vector<void*> allocs;
   int device = 0;
   uint32_t max_size = 0;
-  ~azmi_cache() { for (void* p : allocs) (void)hipFree(p); }
+  // scratch of the device-pointer entries (azmi_cache_find_rows / azmi_net_forward_cached, cache.hip): [0] the miss count, then
+  // rows_cap miss rows, then one prefix per group of 64 rows.  Allocated by the first such call, regrown only by a larger one
+  uint32_t* rows_scratch = nullptr;
+  uint32_t rows_cap = 0;
+  ~azmi_cache() {
+    for (void* p : allocs) (void)hipFree(p);
+    if (rows_scratch) (void)hipFree(rows_scratch);
+  }
 };

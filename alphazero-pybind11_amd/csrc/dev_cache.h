@@ -480,22 +480,25 @@ __device__ __forceinline__ void wave_copy_row(float* __restrict__ dst, const flo
     for (uint32_t u = 0; u < U; ++u) { const uint32_t e = e0 + u * 64 + lane; if (e < n) dst[e] = t[u]; }
   }
 }
-template <bool ZERO_IS_KEY = false>
+template <bool ZERO_IS_KEY = false, bool ROWS = false>
 __device__ __forceinline__ void cache_apply_batch(const CacheView& c, const uint64_t* keys, const float* policy,
                                                    const float* value, uint32_t n, uint32_t* s_sid,
-                                                   const uint8_t* groups = nullptr, uint32_t group = 0) {
+                                                   const uint8_t* groups = nullptr, uint32_t group = 0,
+                                                   const uint32_t* rows = nullptr) {
   const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const uint32_t i = blockIdx.x * (blockDim.x >> 6) + wave;
+  // ROWS (cache_rows_kernels.h): element j of the batch is row rows[j] of keys / policy / value; else row j itself
+  auto src = [rows](uint32_t j) -> size_t { if constexpr (ROWS) return rows[j]; else return j; };
   // this wave's own element - key and, when a row is at most one load per lane, the payload - is requested together with the
   // batch's keys: the insert below is a chain of dependent round trips (keys, shard state, key again, payload), and in the
   // common case of one element per shard the last two are these registers
   const bool own_rows = c.np <= 64 && c.nv <= 64;
-  const uint64_t own_key = i < n ? keys[i] : 0ull;
-  const float own_p = (i < n && own_rows && lane < c.np) ? policy[static_cast<size_t>(i) * c.np + lane] : 0.0f;
-  const float own_v = (i < n && own_rows && lane < c.nv) ? value[static_cast<size_t>(i) * c.nv + lane] : 0.0f;
+  const uint64_t own_key = i < n ? keys[src(i)] : 0ull;
+  const float own_p = (i < n && own_rows && lane < c.np) ? policy[src(i) * c.np + lane] : 0.0f;
+  const float own_v = (i < n && own_rows && lane < c.nv) ? value[src(i) * c.nv + lane] : 0.0f;
   for (uint32_t j = tid; j < n; j += blockDim.x) {
     const bool ours = !(groups && groups[j] != group);                 // elements of another model group are not ours
-    const uint64_t k = keys[j];
+    const uint64_t k = keys[src(j)];
     s_sid[j] = (ours && (ZERO_IS_KEY || k)) ? shard_of(c, k) : 0xFFFFFFFFu;
   }
   __syncthreads();
@@ -513,7 +516,7 @@ __device__ __forceinline__ void cache_apply_batch(const CacheView& c, const uint
       const uint32_t b = __builtin_ctzll(m);
       m &= m - 1;
       const uint32_t jj = base + b;
-      const int slot = ws.insert(jj == i ? own_key : keys[jj]);
+      const int slot = ws.insert(jj == i ? own_key : keys[src(jj)]);
       if (slot >= 0) {
         float* dp = c.policy + (static_cast<size_t>(my) * kWaveCap + slot) * c.np;
         float* dv = c.value + (static_cast<size_t>(my) * kWaveCap + slot) * c.nv;
@@ -521,8 +524,8 @@ __device__ __forceinline__ void cache_apply_batch(const CacheView& c, const uint
           if (lane < c.np) dp[lane] = own_p;
           if (lane < c.nv) dv[lane] = own_v;
         } else {
-          wave_copy_row<32>(dp, policy + static_cast<size_t>(jj) * c.np, c.np, lane);   // a StarGambit row in one round trip
-          for (uint32_t e = lane; e < c.nv; e += 64) dv[e] = value[static_cast<size_t>(jj) * c.nv + e];
+          wave_copy_row<32>(dp, policy + src(jj) * c.np, c.np, lane);   // a StarGambit row in one round trip
+          for (uint32_t e = lane; e < c.nv; e += 64) dv[e] = value[src(jj) * c.nv + e];
         }
       }
     }

@@ -16,6 +16,7 @@
 #include "search_pool_kernels.h"
 #include "search_frontier_kernels.h"
 #include "search_sweep_metrics_kernels.h"
+#include "search_leaf_keys_kernels.h"
 
 using namespace azmi;
 
@@ -224,4 +225,12 @@ void sb_launch_sweep_mean(azmi_search* s, uint32_t J, const SweepMetricsOut& o, 
 void sb_launch_policy_divergences(const float* d_p, const float* d_q, uint32_t rows, uint32_t M, double* d_out, hipStream_t st) {
   if (M <= 8) k_policy_divergences<8><<<(rows + 31u) / 32u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
   else k_policy_divergences<64><<<(rows + 3u) / 4u, 256, 0, st>>>(d_p, d_q, rows, M, d_out);
+}
+
+// ---- the step API's leaf keys: the kernel of search_leaf_keys_kernels.h, behind everything else ------------------------------------
+void sb_launch_leaf_keys(azmi_search* s, hipStream_t st) {
+  const uint32_t cap = s->n * s->k_leaves;
+  if (s->k_leaves > 1) k_sb_leaf_keys<<<(cap + 255u) / 256u, 256, 0, st>>>(s->wu.keys, s->wu.rows, s->sb.n_rows, cap, s->d_leaf_keys);
+  else k_sb_leaf_keys<<<(cap + 255u) / 256u, 256, 0, st>>>(s->pm->ar.leaf_key, s->sb.rows, s->sb.n_rows, cap, s->d_leaf_keys);
+  s->launches += 1;
 }

@@ -88,6 +88,7 @@ void azmi_search_destroy(azmi_search* s) {
   wu_free(s);        // (hipFree waits for the device)
   if (s->sw_block.p) (void)hipFree(s->sw_block.p);
   if (s->sm_block.p) (void)hipFree(s->sm_block.p);
+  if (s->leaf_keys_block.p) (void)hipFree(s->leaf_keys_block.p);
   if (s->fr_trees) (void)hipFree(s->fr_trees);
   if (s->fr_records.p) (void)hipFree(s->fr_records.p);
   if (s->fr_host) (void)hipHostFree(s->fr_host);

@@ -86,6 +86,9 @@ struct azmi_search {
   // sweep metrics (azmi_search_sweep_metrics): allocated by the first call, regrown when a sweep brings more checkpoints
   DevBlock sm_block;                  // sb_cut_sweep_metrics
   uint32_t sm_cap = 0;                // checkpoints the block has room for
+  // the step API's leaf keys (azmi_search_leaf_keys): allocated by the first call, regrown when leaves_per_step grows
+  DevBlock leaf_keys_block;
+  uint64_t* d_leaf_keys = nullptr;    // [K * N] the keys of the pending step's rows, in row order
 };
 
 // ---- defined in search_batch_steps.hip -----------------------------------------------------------------------------------------------
@@ -158,4 +161,6 @@ void sb_launch_frontier_emit(azmi_search* s, hipStream_t st);
 void sb_launch_sweep_metrics(azmi_search* s, const azmi_search* ref, uint32_t anchor, int32_t raw, const double* d_outcomes,
                              const azmi::SweepMetricsOut& o, hipStream_t st);
 void sb_launch_sweep_mean(azmi_search* s, uint32_t J, const azmi::SweepMetricsOut& o, hipStream_t st);
+// the step API's leaf keys into s->d_leaf_keys, in row order
+void sb_launch_leaf_keys(azmi_search* s, hipStream_t st);
 void sb_launch_policy_divergences(const float* d_p, const float* d_q, uint32_t rows, uint32_t M, double* d_out, hipStream_t st);

@@ -254,6 +254,24 @@ int azmi_search_leaves_to_host(azmi_search* s, float* canonical, uint32_t* tree_
   return AZMI_OK;
 }
 
+int azmi_search_leaf_keys(azmi_search* s, void* stream, uint64_t** dev_keys, uint32_t* n_rows) {
+  if (!s || !dev_keys || !n_rows) return SB_FAIL(AZMI_ERR_INVALID, "leaf_keys: null argument");
+  if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "leaf_keys: no leaf batch is pending; call find_leaves first");
+  azmi_pm* pm = s->pm;
+  SB_TRY(hipSetDevice(pm->device));
+  const size_t need = static_cast<size_t>(s->n) * s->k_leaves * 8;
+  if (!s->leaf_keys_block.p || need > s->leaf_keys_block.bytes) {      // the first call / a larger leaves_per_step only
+    if (s->leaf_keys_block.reserve(need) != hipSuccess) return SB_FAIL(AZMI_ERR_OOM, "leaf_keys: %zu bytes of device memory", need);
+    s->d_leaf_keys = static_cast<uint64_t*>(s->leaf_keys_block.p);
+  }
+  hipStream_t st = pm->pick(stream);
+  sb_launch_leaf_keys(s, st);
+  SB_TRY(hipGetLastError());
+  SB_TRY(hipStreamSynchronize(st));      // the caller's evaluator runs on a stream of its own
+  *dev_keys = s->d_leaf_keys; *n_rows = s->step_rows;
+  return AZMI_OK;
+}
+
 int azmi_search_process_results(azmi_search* s, const float* dev_v, const float* dev_pi, int root_noise_enabled, void* stream) {
   int rc = sb_begin_step(s, "process_results"); if (rc) return rc;
   if (!s->step_pending) return SB_FAIL(AZMI_ERR_STATE, "process_results: no leaf batch is pending; call find_leaves first");

@@ -573,6 +573,13 @@ int azmi_search_reset(azmi_search* s, const uint8_t* init, uint32_t init_stride,
 int azmi_search_find_leaves(azmi_search* s, void* stream, float** dev_canonical, uint32_t** dev_tree_index, uint32_t* n_rows);
 int azmi_search_process_results(azmi_search* s, const float* dev_v, const float* dev_pi, int root_noise_enabled, void* stream);
 int azmi_search_leaves_to_host(azmi_search* s, float* canonical, uint32_t* tree_index);
+/* the engine key (hash_game_state, game_state.h:141-156; cache_utils.py:24) of every row of the pending find_leaves step, in row
+ * order: *dev_keys = [*n_rows] uint64 in a buffer of the object, valid until the next find_leaves.  The find kernel hashed every
+ * leaf it handed out (the hash search and capture_roots use); one launch brings the keys into row order, then `stream` is
+ * synchronised, since the caller's evaluator runs on a stream of its own.  With leaves_per_step > 1 the keys are the ones a search
+ * with a cache would insert under: a key of 0 reads 0x9E3779B97F4A7C15, the value every cache stores it as.  AZMI_ERR_STATE when no
+ * step is pending. */
+int azmi_search_leaf_keys(azmi_search* s, void* stream, uint64_t** dev_keys, uint32_t* n_rows);
 int azmi_search_process_results_host(azmi_search* s, const float* v, const float* pi, int root_noise_enabled);
 typedef struct azmi_net azmi_net;
 int azmi_search_run(azmi_search* s, azmi_net* net, azmi_cache* cache, uint32_t visits, int root_noise_enabled, void* stream);
@@ -930,6 +937,34 @@ int azmi_cache_insert_many(azmi_cache* cache, const uint64_t* hashes, const floa
 int azmi_cache_find_many(azmi_cache* cache, const uint64_t* hashes, uint32_t n, uint8_t* hit, float* policy, float* value);
 int azmi_cache_stats(azmi_cache* cache, uint64_t out[6]);
 const char* azmi_cache_last_error(void);
+/* The same cache on rows that are already in device memory: every pointer below is a DEVICE pointer on the cache's device, the
+ * launches are enqueued on `stream` (a HIP stream or NULL) and nothing is read back or waited for.  The only synchronous path is
+ * the scratch of the miss list (one prefix per 64 rows, and the list itself for azmi_net_forward_cached): allocated by the first
+ * call that needs it and regrown only when a larger n arrives.  A cache is used from ONE stream at a time: two streams on one
+ * cache are the caller's to order (an event), as for the host-array entries.  Argument errors are AZMI_ERR_INVALID before any
+ * launch, the message (azmi_cache_last_error) naming the argument; n == 0 is AZMI_OK and launches nothing; at most 2^30 rows.
+ *   find_rows    S3FIFOCache.find (py_wrapper.cc:226-236 over s3fifo_cache.h:41-59; cache_utils.py:26 `cache.find(h, ...)`) for n
+ *                keys: d_hit[i] = 1 / 0; a hit writes rows i of d_pi [n][num_policy] and d_v [n][num_value], a miss leaves them
+ *                untouched.  Counters, frequency bump and ghost "reinsert" accounting are azmi_cache_find_many's; hash 0 is a key.
+ *                d_miss_rows [n] / d_miss_count [1] (both, or both NULL for no compaction): the rows that missed, ascending, and
+ *                their number.  The order is a prefix over hit[], never a ticket: it does not depend on scheduling.
+ *   insert_rows  S3FIFOCache.insert (py_wrapper.cc:237-242; cache_utils.py:35 `cache.insert(h, pi, v)`) for the rows
+ *                d_rows[0 .. min(*d_row_count, n_max)) of d_keys / d_pi / d_v, in list order: the state
+ *                insert_many(keys[rows], pi[rows], v[rows]) leaves (list order is kept inside a shard, s3fifo_cache.h:259-286).
+ *                The count is read on the device.  d_rows == NULL: the rows 0 .. n_max - 1 themselves; d_row_count == NULL: n_max.
+ *                Every listed index must be a row of the arrays.  ceil(n_max / 8192) launches on 64-entry shards, one otherwise.
+ *   azmi_net_forward_cached
+ *                cache_utils.cached_inference (cache_utils.py:19-36) for a batch: find_rows, azmi_net_forward_rows over the miss
+ *                list, insert_rows over the same list, on one stream.  d_v [n][P+1] and d_pi [n][M] hold every row's answer
+ *                afterwards - the cached bits for a hit, the net's for a miss - and d_hit [n] says which.  A key that occurs
+ *                several times among the misses of one batch is evaluated every time and inserted once.  Refused: a cache whose
+ *                num_policy / num_value are not the net's M / P + 1, a cache on another device than the net. */
+int azmi_cache_find_rows(azmi_cache* cache, const uint64_t* d_keys, uint32_t n, uint8_t* d_hit, float* d_pi, float* d_v,
+                         uint32_t* d_miss_rows, uint32_t* d_miss_count, void* stream);
+int azmi_cache_insert_rows(azmi_cache* cache, const uint64_t* d_keys, const float* d_pi, const float* d_v, const uint32_t* d_rows,
+                           const uint32_t* d_row_count, uint32_t n_max, void* stream);
+int azmi_net_forward_cached(azmi_net* net, azmi_cache* cache, const float* d_canon, const uint64_t* d_keys, uint32_t n, float* d_v,
+                            float* d_pi, uint8_t* d_hit, void* stream);
 
 /* ---- native round driver (the counterpart of GameRunner's batcher / gpu_loop / result_worker
  *      threads, game_runner.py:483-552, 651-726): `rounds` times, for each of the `k` engines in turn:
